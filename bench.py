@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: ResNet-18, CIFAR-10-shape synthetic data, PowerSGD r=4 (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -32,6 +32,12 @@ ddp_powersgd_distillBERT_IMDb/ddp_init.py:92).
 
 Rank 0 prints ONE JSON line.  ``value`` = whole-job samples/s (max step time over ranks).
 ``bytes_per_step`` = bytes all-reduced per rank per step with the reference's accounting.
+
+A plain run does only what that line needs: set-up, ``--warmup`` steps, ``--steps`` timed
+steps, the health checks that make the number trustworthy, and (``--dump-outputs DIR``) the
+arrays the last timed step left.  Everything else is opt-in (``--weak-too``, ``--link``,
+``--amp``, ...); ``--full`` is the switch for measurements beyond the headline and currently
+has none to add.
 """
 from __future__ import annotations
 
@@ -85,6 +91,13 @@ def parse(argv=None):
                          "link is emulated)")
     ap.add_argument("--no-overlap", action="store_true", help="= --overlap off")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step left a caller "
+                         "(parameters, model buffers, loss) as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure.  A plain run already does "
+                         "only set-up, warm-up, the timed steps and the result line (the extra arms are "
+                         "opt-in flags of their own: --weak-too, --link, --amp, ...), so today this adds nothing")
     ap.add_argument("--no-supervise", action="store_true",
                     help="run the step in this process (no supervisor / fallback; for profilers)")
     ap.add_argument("--level", type=int, default=0, help="first fallback level to try (see FALLBACKS_*)")
@@ -348,6 +361,46 @@ def health_check(wl, world: int, where: str) -> dict:
     return {"replicas_equal": equal, "flag_errors": flag_errors, "checksum": sums[0]}
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # all of --dump-outputs together (ResNet-18: 46.8 MB of parameters, whole)
+
+
+def dump_outputs(wl, directory: str, mean_loss: float) -> dict:
+    """Write what the last timed step left a caller of the training step, as ``<name>.npy``:
+
+    params   every parameter after the step, flattened in ``named_parameters()`` order (float32)
+    buffers  every model buffer (BatchNorm running statistics, step counters), same layout (float32)
+    loss     [mean loss over warm-up + timed steps, loss accumulator] (float64)
+
+    Model init, data and step order are seeded (``worker``), so two builds run with the same
+    arguments see identical inputs and can be compared array for array.  If the arrays exceed
+    ``DUMP_BUDGET_BYTES`` each is cut to the same fraction of its elements, picked by a seeded
+    (run-independent) permutation and kept in index order.  Returns {name: element count}."""
+    import numpy as np
+    import torch
+
+    def flat(tensors):
+        parts = [t.detach().reshape(-1).float() for t in tensors]
+        return torch.cat(parts).cpu() if parts else torch.zeros(0)
+
+    arrays = {"params": flat(p for _, p in wl.model.named_parameters()),
+              "buffers": flat(b for _, b in wl.model.named_buffers())}
+    total = sum(4 * a.numel() for a in arrays.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for k, (name, a) in enumerate(arrays.items()):
+        if keep < 1.0:
+            g = torch.Generator().manual_seed(20240 + k)
+            idx = torch.randperm(a.numel(), generator=g)[: int(a.numel() * keep)].sort().values
+            a = a[idx]
+        np.save(os.path.join(directory, name + ".npy"), a.numpy().astype(np.float32, copy=False))
+        written[name] = int(a.numel())
+    np.save(os.path.join(directory, "loss.npy"),
+            np.array([mean_loss, float(wl.loss_acc.item())], dtype=np.float64))
+    written["loss"] = 2
+    return written
+
+
 def worker(args, level: int, world: int, rank: int, local: int) -> None:
     """One configuration level on this rank (a supervised child, or in-process unsupervised)."""
     from network_distributed_pytorch_amd.utils.supervisor import Heartbeat
@@ -397,6 +450,10 @@ def worker(args, level: int, world: int, rank: int, local: int) -> None:
     health = health_check(wl, world, "after the timed steps")
     comm_stats = wl.comm.stats.as_dict()
     final_loss = float(wl.loss_acc.item()) / max(1, args.warmup + args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before any extra arm trains the model further
+        hb.beat("dump outputs", 300)
+        dumped = dump_outputs(wl, os.path.abspath(args.dump_outputs), final_loss)
 
     weak = None
     if args.weak_too == "on" and args.scaling == "strong" and not wl.is_bert:
@@ -410,7 +467,7 @@ def worker(args, level: int, world: int, rank: int, local: int) -> None:
 
     if rank == 0:
         line = json.dumps(record(args, a, wl, world, per_gpu, elapsed, comm_stats, final_loss, health, level,
-                                 weak))
+                                 weak, dumped))
         hb.result(line)
         if not hb.enabled:
             print(line, flush=True)
@@ -424,7 +481,7 @@ def worker(args, level: int, world: int, rank: int, local: int) -> None:
         dist.destroy_process_group()
 
 
-def record(args, a, wl, world, per_gpu, elapsed, comm_stats, final_loss, health, level, weak) -> dict:
+def record(args, a, wl, world, per_gpu, elapsed, comm_stats, final_loss, health, level, weak, dumped=None) -> dict:
     global_batch = per_gpu * world
     sps = global_batch * args.steps / elapsed
     is_bert = wl.is_bert
@@ -481,6 +538,8 @@ def record(args, a, wl, world, per_gpu, elapsed, comm_stats, final_loss, health,
     }
     if weak is not None:
         rec["weak_scaling"] = weak
+    if dumped is not None:
+        rec["dumped_outputs"] = dumped
     return rec
 
 

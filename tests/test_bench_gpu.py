@@ -25,15 +25,30 @@ def _bench(args, env_extra=None, timeout=280):
 
 
 @pytest.mark.timeout(300)
-def test_bench_two_gloo_ranks_on_one_gpu(device):
+def test_bench_two_gloo_ranks_on_one_gpu(device, tmp_path):
     """`bench.py --gpus 2` self-launches two ranks (gloo lets them share the GPU); the line
-    says n_gpus 2 and the cross-rank parameter checksum agrees."""
-    p, rec = _bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--global-batch", "64"],
-                    {"NDP_BACKEND": "gloo"})
+    says n_gpus 2 and the cross-rank parameter checksum agrees.  `--dump-outputs` leaves rank 0's
+    parameters, buffers and loss of the last timed step, and the parameters are the ones the
+    line's checksum was taken of."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    p, rec = _bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--global-batch", "64",
+                     "--dump-outputs", str(out), "--full"], {"NDP_BACKEND": "gloo"})
     assert p.returncode == 0 and rec is not None, (p.stdout + p.stderr)[-4000:]
     assert rec["n_gpus"] == 2 and rec["replicas_equal"] is True and rec["flag_errors"] == 0
     assert rec["config"]["per_gpu_batch"] == 32 and rec["comm_backend"] == "c10d-gloo"
     assert rec["supervisor"]["failed"] == []
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["buffers.npy", "loss.npy", "params.npy"]
+    params, loss = np.load(out / "params.npy"), np.load(out / "loss.npy")
+    assert params.dtype == np.float32 and params.size == rec["dense_bytes_per_step"] // 4
+    assert rec["dumped_outputs"]["params"] == params.size and np.isfinite(params).all()
+    # param_checksum is an fp64 sum over the flat parameter arena (alignment padding is zero): the
+    # two sums differ by their order only, at most n * 2^-53 * sum|x|
+    bound = params.size * 2.0 ** -53 * float(np.abs(params).sum(dtype=np.float64))
+    assert abs(float(params.sum(dtype=np.float64)) - rec["param_checksum"]) <= bound
+    assert loss.dtype == np.float64 and abs(loss[0] - rec["mean_loss"]) <= 1e-5
 
 
 @pytest.mark.timeout(300)
