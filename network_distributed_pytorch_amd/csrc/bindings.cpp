@@ -1453,6 +1453,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_pair_bwd", &bn_pair_bwd);
   m.def("wino_set_enabled", &ndp::wino_set_enabled);
   m.def("conv_set_stem_psplit", &ndp::conv_set_stem_psplit);
+  m.def("conv_set_wgrad_stage", [](int n) {
+    TORCH_CHECK(ndp::conv_set_wgrad_stage(n), "conv_set_wgrad_stage: 0 (auto), 1 or 4 images per stage; ", n,
+                " is not built");
+  });
+  m.def("conv_pair_launches", &ndp::conv_pair_launches);
+  m.def("wino_set_wgrad_prefetch", &ndp::wino_set_wgrad_prefetch);
   m.def("bn_slices", &bn_slices);
   m.def("slab_sum", &slab_sum);
   m.def("bn_part_numel", &bn_part_numel);

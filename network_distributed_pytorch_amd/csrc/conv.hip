@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <string>
+
 #include "ndp_kernels.h"
 #include "wino_dpp.h"
 
@@ -921,25 +923,36 @@ struct ConvWgCfg {
   static constexpr size_t MAIN_BYTES = 2 * (size_t)(A_SZ + B_SZ) * sizeof(float);
   static constexpr size_t EPI_BYTES = TAPMAJ ? (size_t)BM * LDJ * sizeof(float) : 0;
   static constexpr size_t LDS_BYTES = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
+  // IPS images per stage (conv_wgrad_body): both stage buffers hold IPS images' tiles
+  static constexpr size_t lds_bytes(int ips) { return ips * MAIN_BYTES > EPI_BYTES ? ips * MAIN_BYTES : EPI_BYTES; }
   static_assert(MB * JB == NW * NBPW, "every wave owns NBPW 32x32 blocks");
   static_assert(P % 2 == 0 && PQ % 4 == 0 && HW % 4 == 0 && NSTEP % KB == 0, "pixel pairing / float4 loads");
 };
 
 // (a device function of the workgroup's grid coordinates: the layer2 backward pairs run it on
 // one part of a combined grid, launch_conv_dgrad)
-template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB>
+// IPS = images per stage; only the layer2 3x3 class (4x4 maps) is built with IPS > 1 (wgrad_staged).
+// One image of that class is only PQ / 2 = 8 k-steps: as the span between two barriers and the
+// whole prefetch distance that is shorter than a trip to HBM, and the waves (one per SIMD) stood
+// waiting at every image.  A stage of IPS images
+// issues its IPS x (A_PER_T + B_PER_T) float4 loads, runs the MFMAs of the previous stage's images
+// in image order, writes its tiles to LDS and meets ONE barrier: IPS times the work per barrier and
+// per load round trip, the same MFMAs in the same order on every accumulator (bitwise the one-image
+// loop's result).  The slice's image count must be a multiple of IPS: the dispatch (wgrad_staged)
+// never gives a slice another IPS, there is no predicated last stage.
+template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB, int IPS = 1>
 __device__ __forceinline__ void conv_wgrad_body(const float* __restrict__ x, const float* __restrict__ dy,
                                                 float* __restrict__ part, int Cin, int Kout, int imgs_per_slice,
                                                 const uint3 bid, float* __restrict__ smem) {
   using G = ConvWgCfg<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  float* As = smem;                 // [2][A_SZ]
-  float* Bs = smem + 2 * G::A_SZ;   // [2][B_SZ]
+  float* As = smem;                       // [2][IPS][A_SZ]
+  float* Bs = smem + 2 * IPS * G::A_SZ;   // [2][IPS][B_SZ]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l32 = lane & 31;
   const int slice = bid.x, m0 = bid.y * BM, c0 = bid.z * CB;
   const int bb = slice * imgs_per_slice;
 
-  for (int i = tid; i < 2 * G::B_SZ; i += G::NT) Bs[i] = 0.f;
+  for (int i = tid; i < 2 * IPS * G::B_SZ; i += G::NT) Bs[i] = 0.f;  // every buffer's zero border, once
 
   int a_base[NBPW], b_base[NBPW];
 #pragma unroll
@@ -954,48 +967,55 @@ __device__ __forceinline__ void conv_wgrad_body(const float* __restrict__ x, con
     b_base[t] = (j < G::J) ? c * G::HWp + r * G::Wp + s + h * (G::P / 2) * ST * G::Wp : 0;
   }
 
-  f32x4c ra[G::A_PER_T], rb[G::B_PER_T];
+  // a stage = images [b, b + IPS) in registers, then in LDS buffer `buf` (slots [buf][0 .. IPS))
+  f32x4c ra[IPS][G::A_PER_T], rb[IPS][G::B_PER_T];
   auto load = [&](int b) {
 #pragma unroll
-    for (int i = 0; i < G::A_PER_T; ++i) {
-      const int e = tid + G::NT * i;
-      f32x4c v = {0.f, 0.f, 0.f, 0.f};
-      if (e < G::A4) v = *reinterpret_cast<const f32x4c*>(dy + ((int64_t)b * Kout + m0) * G::PQ + 4 * e);
-      ra[i] = v;
-    }
+    for (int ii = 0; ii < IPS; ++ii) {
 #pragma unroll
-    for (int i = 0; i < G::B_PER_T; ++i) {
-      const int e = tid + G::NT * i;
-      f32x4c v = {0.f, 0.f, 0.f, 0.f};
-      if (e < G::B4 && c0 + (4 * e) / G::HW < Cin)
-        v = *reinterpret_cast<const f32x4c*>(x + ((int64_t)b * Cin + c0) * G::HW + 4 * e);
-      rb[i] = v;
+      for (int i = 0; i < G::A_PER_T; ++i) {
+        const int e = tid + G::NT * i;
+        f32x4c v = {0.f, 0.f, 0.f, 0.f};
+        if (e < G::A4) v = *reinterpret_cast<const f32x4c*>(dy + ((int64_t)(b + ii) * Kout + m0) * G::PQ + 4 * e);
+        ra[ii][i] = v;
+      }
+#pragma unroll
+      for (int i = 0; i < G::B_PER_T; ++i) {
+        const int e = tid + G::NT * i;
+        f32x4c v = {0.f, 0.f, 0.f, 0.f};
+        if (e < G::B4 && c0 + (4 * e) / G::HW < Cin)
+          v = *reinterpret_cast<const f32x4c*>(x + ((int64_t)(b + ii) * Cin + c0) * G::HW + 4 * e);
+        rb[ii][i] = v;
+      }
     }
   };
   auto store = [&](int buf) {
-    float* A = As + buf * G::A_SZ;
-    float* B = Bs + buf * G::B_SZ;
 #pragma unroll
-    for (int i = 0; i < G::A_PER_T; ++i) {
-      const int e = tid + G::NT * i;
-      if (e < G::A4) {
-        const int m = (4 * e) / G::PQ, pq = 4 * e - m * G::PQ;
-        float* d = A + m * G::LDY + pq;
-        if constexpr (G::AVW) {
-          *reinterpret_cast<f32x4c*>(d) = ra[i];
-        } else {
-          d[0] = ra[i].x; d[1] = ra[i].y; d[2] = ra[i].z; d[3] = ra[i].w;
+    for (int ii = 0; ii < IPS; ++ii) {
+      float* A = As + (buf * IPS + ii) * G::A_SZ;
+      float* B = Bs + (buf * IPS + ii) * G::B_SZ;
+#pragma unroll
+      for (int i = 0; i < G::A_PER_T; ++i) {
+        const int e = tid + G::NT * i;
+        if (e < G::A4) {
+          const int m = (4 * e) / G::PQ, pq = 4 * e - m * G::PQ;
+          float* d = A + m * G::LDY + pq;
+          if constexpr (G::AVW) {
+            *reinterpret_cast<f32x4c*>(d) = ra[ii][i];
+          } else {
+            d[0] = ra[ii][i].x; d[1] = ra[ii][i].y; d[2] = ra[ii][i].z; d[3] = ra[ii][i].w;
+          }
         }
       }
-    }
 #pragma unroll
-    for (int i = 0; i < G::B_PER_T; ++i) {
-      const int e = tid + G::NT * i;
-      if (e < G::B4) {
-        const int c = (4 * e) / G::HW, hw = 4 * e - c * G::HW;
-        const int hh = hw / W, ww = hw - hh * W;
-        float* d = B + c * G::HWp + (hh + PD) * G::Wp + ww + PD;
-        d[0] = rb[i].x; d[1] = rb[i].y; d[2] = rb[i].z; d[3] = rb[i].w;
+      for (int i = 0; i < G::B_PER_T; ++i) {
+        const int e = tid + G::NT * i;
+        if (e < G::B4) {
+          const int c = (4 * e) / G::HW, hw = 4 * e - c * G::HW;
+          const int hh = hw / W, ww = hw - hh * W;
+          float* d = B + c * G::HWp + (hh + PD) * G::Wp + ww + PD;
+          d[0] = rb[ii][i].x; d[1] = rb[ii][i].y; d[2] = rb[ii][i].z; d[3] = rb[ii][i].w;
+        }
       }
     }
   };
@@ -1010,44 +1030,48 @@ __device__ __forceinline__ void conv_wgrad_body(const float* __restrict__ x, con
   __syncthreads();
   store(0);
   __syncthreads();
-  for (int i = 0; i < imgs_per_slice; ++i) {
+  const int stages = imgs_per_slice / IPS;
+  for (int i = 0; i < stages; ++i) {
     const int cur = i & 1;
-    if (i + 1 < imgs_per_slice) load(bb + i + 1);
-    const float* A = As + cur * G::A_SZ;
-    const float* B = Bs + cur * G::B_SZ;
-    float av[2][KB][NBPW], bv[2][KB][NBPW];
-    auto fetch = [&](int blk, int slot) {
+    if (i + 1 < stages) load(bb + (i + 1) * IPS);
 #pragma unroll
-      for (int k = 0; k < KB; ++k) {
-        const int t = blk * KB + k;
-        const int p = t / G::Q, q = t - p * G::Q;
+    for (int ii = 0; ii < IPS; ++ii) {
+      const float* A = As + (cur * IPS + ii) * G::A_SZ;
+      const float* B = Bs + (cur * IPS + ii) * G::B_SZ;
+      float av[2][KB][NBPW], bv[2][KB][NBPW];
+      auto fetch = [&](int blk, int slot) {
 #pragma unroll
-        for (int u = 0; u < NBPW; ++u) {
-          if constexpr (!G::AVW) av[slot][k][u] = A[a_base[u] + t];
-          bv[slot][k][u] = B[b_base[u] + p * ST * G::Wp + q * ST];
-        }
-      }
-      if constexpr (G::AVW) {
+        for (int k = 0; k < KB; ++k) {
+          const int t = blk * KB + k;
+          const int p = t / G::Q, q = t - p * G::Q;
 #pragma unroll
-        for (int u = 0; u < NBPW; ++u)
-#pragma unroll
-          for (int q4 = 0; q4 < KB / 4; ++q4) {
-            const f32x4c v = *reinterpret_cast<const f32x4c*>(A + a_base[u] + blk * KB + 4 * q4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) av[slot][4 * q4 + j][u] = v[j];
+          for (int u = 0; u < NBPW; ++u) {
+            if constexpr (!G::AVW) av[slot][k][u] = A[a_base[u] + t];
+            bv[slot][k][u] = B[b_base[u] + p * ST * G::Wp + q * ST];
           }
+        }
+        if constexpr (G::AVW) {
+#pragma unroll
+          for (int u = 0; u < NBPW; ++u)
+#pragma unroll
+            for (int q4 = 0; q4 < KB / 4; ++q4) {
+              const f32x4c v = *reinterpret_cast<const f32x4c*>(A + a_base[u] + blk * KB + 4 * q4);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) av[slot][4 * q4 + j][u] = v[j];
+            }
+        }
+      };
+      fetch(0, 0);
+#pragma unroll
+      for (int blk = 0; blk < G::NBLK; ++blk) {
+        if (blk + 1 < G::NBLK) fetch(blk + 1, (blk + 1) & 1);
+#pragma unroll
+        for (int k = 0; k < KB; ++k)
+#pragma unroll
+          for (int u = 0; u < NBPW; ++u) acc[u] = mfma32(av[blk & 1][k][u], bv[blk & 1][k][u], acc[u]);
       }
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int blk = 0; blk < G::NBLK; ++blk) {
-      if (blk + 1 < G::NBLK) fetch(blk + 1, (blk + 1) & 1);
-#pragma unroll
-      for (int k = 0; k < KB; ++k)
-#pragma unroll
-        for (int u = 0; u < NBPW; ++u) acc[u] = mfma32(av[blk & 1][k][u], bv[blk & 1][k][u], acc[u]);
     }
-    if (i + 1 < imgs_per_slice) store(cur ^ 1);
+    if (i + 1 < stages) store(cur ^ 1);
     __syncthreads();
   }
 
@@ -1103,20 +1127,21 @@ __device__ __forceinline__ void conv_wgrad_body(const float* __restrict__ x, con
   }
 }
 
-template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB>
+template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB, int IPS = 1>
 __global__ __launch_bounds__(64 * NW) void conv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                              float* __restrict__ part, int Cin, int Kout,
                                                              int imgs_per_slice) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  conv_wgrad_body<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>(x, dy, part, Cin, Kout, imgs_per_slice,
-                                                           make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), smem);
+  conv_wgrad_body<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>(x, dy, part, Cin, Kout, imgs_per_slice,
+                                                                make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), smem);
 }
 
 // A layer2 backward pair in ONE launch: workgroups [0, n_dgrad) run the Winograd grad-x
 // (wino_dpp.h; 4x4 maps, or the 3x3/2 conv's zero-inserted 8x8 dY), the rest the direct grad-W of
 // the same conv (64 NW threads: the surplus wave leaves before any barrier, which then waits for
 // the live waves only).  Both read only dY / x / the weights and write disjoint outputs.
-template <int WH, int IUPS, int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB>
+template <int WH, int IUPS, int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB,
+          int IPS = 1>
 __global__ __launch_bounds__(256, 2) void wino_direct_pair_kernel(WinoConvArgs A, uint3 ga, const float* __restrict__ x,
                                                                   const float* __restrict__ dy, float* __restrict__ part,
                                                                   int Cin, int Kout, int imgs, uint3 gw) {
@@ -1129,7 +1154,7 @@ __global__ __launch_bounds__(256, 2) void wino_direct_pair_kernel(WinoConvArgs A
   } else {
     if (threadIdx.x >= 64 * NW) return;
     b -= na;
-    conv_wgrad_body<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>(
+    conv_wgrad_body<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>(
         x, dy, part, Cin, Kout, imgs, make_uint3(b % gw.x, (b / gw.x) % gw.y, b / (gw.x * gw.y)), smem);
   }
 }
@@ -1370,19 +1395,49 @@ void launch_slab_sum(const float* part, float* out, int64_t n, int nslab, hipStr
                      addend);
 }
 
-template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB>
+// Images per stage of the direct grad-W (conv_wgrad_body IPS): kWgIps for the layer2 3x3 class
+// (class 1: 4 images = 57 KB of tiles, two workgroups per CU as before, 8 float4 of staging
+// registers) when the slice holds at least two such stages, else the one-image loop — so per-GPU
+// batch 64 (4-image slices) runs what it ran.  NDP_FUSION_OFF=wgrad_pipe (A/B arm) and
+// conv_set_wgrad_stage(1) give the one-image loop everywhere; conv_set_wgrad_stage(0) = auto.
+// Measured and not built (profiles/r7/README.md): 2 images per stage, and stages for the 3x3/2 and
+// 1x1/2 classes.  conv_set_wgrad_stage accepts 0, 1 and kWgIps only (the binding rejects the rest).
+constexpr int kWgIps = 4;
+static int g_wgrad_stage = 0;
+bool conv_set_wgrad_stage(int n) {
+  if (n != 0 && n != 1 && n != kWgIps) return false;
+  g_wgrad_stage = n;
+  return true;
+}
+// pair launches made so far (a conv's grad-x and its held-back grad-W in one launch): lets a test
+// tell a pair from the two launches it replaces
+static int64_t g_pair_launches = 0;
+int64_t conv_pair_launches() { return g_pair_launches; }
+static bool wgrad_staged(int imgs) {
+  const bool on = g_wgrad_stage ? g_wgrad_stage == kWgIps : !wgrad_pipe_off();
+  return on && imgs % kWgIps == 0 && imgs >= 2 * kWgIps;
+}
+
+template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB, int IPS = 1>
 static void run_wgrad(const float* x, const float* dy, float* part, float* dw, int B, int Cin, int Kout,
                       int imgs, hipStream_t s) {
   using G = ConvWgCfg<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  auto k = conv_wgrad_kernel<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
+  auto k = conv_wgrad_kernel<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>;
+  constexpr size_t lds = G::lds_bytes(IPS);
   static bool attr = false;
-  if (!attr) { set_lds(k, G::LDS_BYTES); attr = true; }
+  if (!attr) { set_lds(k, lds); attr = true; }
   const int slices = B / imgs;
-  hipLaunchKernelGGL(k, dim3(slices, Kout / BM, (Cin + CB - 1) / CB), dim3(G::NT), G::LDS_BYTES, s, x, dy, part, Cin,
+  hipLaunchKernelGGL(k, dim3(slices, Kout / BM, (Cin + CB - 1) / CB), dim3(G::NT), lds, s, x, dy, part, Cin,
                      Kout, imgs);
   if (dw == nullptr) return;  // partials only: the caller sums the slabs (batched, ops/gradfinish.py)
   const int64_t n = (int64_t)Kout * Cin * G::RS;  // multiple of 4 for every class
   hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((n / 4 + 15) / 16)), dim3(256), 0, s, part, dw, n, slices);
+}
+// the layer2 3x3 class: staged where the slice allows (wgrad_staged)
+static void run_wgrad_c1(const float* x, const float* dy, float* part, float* dw, int B, int Cin, int Kout, int imgs,
+                         hipStream_t s) {
+  if (wgrad_staged(imgs)) run_wgrad<3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4, kWgIps>(x, dy, part, dw, B, Cin, Kout, imgs, s);
+  else run_wgrad<3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4>(x, dy, part, dw, B, Cin, Kout, imgs, s);
 }
 
 // Shape classes with a direct kernel (everything else stays on MIOpen / the Toeplitz path)
@@ -1431,6 +1486,11 @@ static int pow2_floor(int v) {
 // Round 5 (Winograd grad-W, deferred batched slab sums): doubling the layer1 (Winograd), 3x3/2 and
 // stem slices halves their slabs — ResNet-18 r=4 batch 512 1.5118 / 1.5129 -> 1.4977 / 1.4957 ms;
 // doubling layer2's (class 1) was slower, 1.5043 -> 1.5165 (profiles/r5/bench_wgrad_slices.jsonl).
+// Round 7 (pipelined operand feeding: LDS prefetch in the layer1 Winograd grad-W, 4-image stages in
+// layer2's): the slice sizes re-measured at batch 512 and left as they were — layer1 32-image
+// 1.3774 / 1.3784 vs 1.3574 / 1.3605 ms (16), layer2 16-image 1.3745 / 1.3724 and 64-image 1.4457 /
+// 1.4447 (32), 3x3/2 32-image 1.3779 / 1.3748 (16) (profiles/r7/bench_wgrad_slices.jsonl; the
+// slice overrides of those arms were removed after the runs).
 int conv_wgrad_imgs(int cls, const ConvGeom& g, int B) {
   // (the geometry test only, not the runtime Winograd switch: the slicing stays fixed for a shape,
   // so scratch sized from a cached plan fits whichever grad-W kernel runs)
@@ -1450,6 +1510,7 @@ int conv_wgrad_imgs(int cls, const ConvGeom& g, int B) {
     // slabs of 8-image slices, two workgroups per CU at 512.  ResNet-18 r=4, ms/step: batch 512
     // 1.3866 / 1.3908 vs 1.4043 / 1.4021 (8-image, 2-wave), batch 256 0.9942 / 0.9993 vs 1.0035 /
     // 1.0046 (8-image, 1-wave); 32-image slices 1.4103 (profiles/r6/bench_l1_wgrad_slices.jsonl)
+    // (32-image slices lose with the prefetched feeding too: the round-7 note above)
     return 16;
   }
   // layer2 (class 1) from batch 512: 32-image slices, half the slabs.  Its grad-W now runs in one
@@ -1699,12 +1760,13 @@ void hold_pending(const PendingWgrad& q) {
 }
 
 // grad-x of a layer2 class on the Winograd kernel + the held-back direct grad-W, one launch
-template <int WH, int IUPS, int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB>
+template <int WH, int IUPS, int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB,
+          int IPS = 1>
 void run_pair(const float* dy, const float* u, float* dx, int B, int inC, int outC, const float* addend,
               const ConvBnStats& st, int ks, float* part_x, const PendingWgrad& p, hipStream_t s) {
   using G = ConvWgCfg<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  auto k = wino_direct_pair_kernel<WH, IUPS, R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  constexpr size_t lds = kWLds > G::LDS_BYTES ? kWLds : G::LDS_BYTES;
+  auto k = wino_direct_pair_kernel<WH, IUPS, R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>;
+  constexpr size_t lds = kWLds > G::lds_bytes(IPS) ? kWLds : G::lds_bytes(IPS);
   static bool attr = false;
   if (!attr) { set_lds(k, lds); attr = true; }
   const WinoConvArgs a{dy, u + 16 * (int64_t)inC * outC,  // the grad-x half of the transforms
@@ -1714,6 +1776,7 @@ void run_pair(const float* dy, const float* u, float* dx, int B, int inC, int ou
   const uint3 gw = make_uint3((unsigned)(p.B / p.imgs), (unsigned)(p.g.Co / BM), (unsigned)((p.g.C + CB - 1) / CB));
   const unsigned n = ga.x * ga.y * ga.z + gw.x * gw.y * gw.z;
   hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, s, a, ga, p.x, p.dy, p.part, p.g.C, p.g.Co, p.imgs, gw);
+  ++g_pair_launches;
 }
 // the 1x1 stride-2 grad-x (run_fwd's UPS = 2 path, incl. its split-K slab sum) + the held-back direct
 // grad-W of the same conv, one launch
@@ -1737,6 +1800,7 @@ int run_direct_pair(const float* dy, const float* w, float* dx, int B, int Cin, 
   const uint3 gw = make_uint3((unsigned)(p.B / p.imgs), (unsigned)(p.g.Co / BM), (unsigned)((p.g.C + CB - 1) / CB));
   const unsigned n = ga.x * ga.y * ga.z + gw.x * gw.y * gw.z;
   hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, s, a, ga, p.x, p.dy, p.part, p.g.C, p.g.Co, p.imgs, gw);
+  ++g_pair_launches;
   if (ksplit > 1)
     hipLaunchKernelGGL((conv_slab_sum_ups_kernel<GF::P, GF::Q>), dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, s,
                        part, dx, slab, ksplit, addend);
@@ -1745,7 +1809,7 @@ int run_direct_pair(const float* dy, const float* w, float* dx, int B, int Cin, 
 
 void launch_pending(const PendingWgrad& p) {
   if (p.cls == 0) launch_wino_wgrad(p.x, p.dy, p.part, p.B, p.g.C, p.g.Co, p.g.H, p.imgs, p.s);
-  else if (p.cls == 1) run_wgrad<3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4>(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
+  else if (p.cls == 1) run_wgrad_c1(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
   else if (p.cls == 2) run_wgrad<3, 3, 2, 1, 8, 8, 32, 32, 3, 3, 4>(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
   else if (p.cls == 4) run_wgrad<1, 1, 2, 0, 8, 8, 32, 32, 1, 1, 4>(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
   else run_wgrad<1, 1, 2, 0, 4, 4, 32, 32, 1, 1, 2>(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
@@ -1776,8 +1840,12 @@ int launch_conv_dgrad(const float* dy, const float* w, float* dx, int B, const C
       // this conv's grad-W is waiting: both in one launch
       const PendingWgrad p = *pp;
       *pp = PendingWgrad{};
-      if (cls == 0)
+      if (cls == 0) {
         launch_wino_bwd_pair(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, p.x, p.part, p.imgs, s);
+        ++g_pair_launches;
+      } else if (cls == 1 && wgrad_staged(p.imgs))
+        run_pair<4, 1, 3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4, kWgIps>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, p,
+                                                                  s);
       else if (cls == 1)
         run_pair<4, 1, 3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, p, s);
       else
@@ -1860,7 +1928,7 @@ void launch_conv_wgrad(const float* x, const float* dy, float* part, float* dw, 
   }
   switch (cls) {
     case 0: run_wgrad<3, 3, 1, 1, 8, 8, 32, 32, 3, 3, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
-    case 1: run_wgrad<3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
+    case 1: run_wgrad_c1(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
     case 2: run_wgrad<3, 3, 2, 1, 8, 8, 32, 32, 3, 3, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
     case 3: run_wgrad<7, 7, 2, 3, 32, 32, 3, 32, 5, 1, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
     case 4: run_wgrad<1, 1, 2, 0, 8, 8, 32, 32, 1, 1, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;

@@ -351,6 +351,13 @@ bool wino_wgrad_red(int B, int imgs);
 bool wino_wgrad_ok(int C, int Co, int H);
 void launch_wino_wgrad(const float* x, const float* dy, float* part, int B, int C, int Co, int H, int imgs,
                        hipStream_t s);
+// grad-W operand pipelining (fusion `wgrad_pipe`; A/B overrides): the layer1 Winograd grad-W's LDS
+// prefetch of the next image, and the layer2 3x3 direct grad-W's images per stage (0 = auto, 1 = the
+// one-image loop, 4 = staged where the slice allows; 2-image stages measured slower and are not built)
+bool wgrad_pipe_off();  // NDP_FUSION_OFF=wgrad_pipe
+void wino_set_wgrad_prefetch(bool on);
+bool conv_set_wgrad_stage(int n);  // false: a value that is not built (nothing changed)
+int64_t conv_pair_launches();
 // several layers' transforms in one launch (ops/conv.py WinoBank)
 constexpr int kMaxWino = 16;
 struct WinoBatch {

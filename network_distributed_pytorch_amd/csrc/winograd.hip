@@ -74,8 +74,24 @@ struct WinoWgradArgs {
   int Cin, Cout, imgs;
 };
 constexpr size_t kWgRedLds = (size_t)3 * 16 * 64 * sizeof(f32x4w);  // RED = 4: waves 1..3's blocks
-template <int H, int RED = 1>
+// PF (8x8 maps): the next image's operands — the wave's 16 x-channels and 16 dY-channels, 4 KB
+// contiguous each — land in a wave-private LDS zone by LDS-DMA while the current image is
+// transformed and multiplied from registers.  8 fully coalesced 1 KB instructions per image replace
+// the 12 register loads whose 64 lanes each read 16 B of a different 128-B line (and x's halo rows
+// twice); every lane then takes its 12 float4 (4 x rows, 2 dY rows) from the zone with ds_read_b128.
+// Chunk c (16 B; c = 2 row + half) of channel ch sits at 16-B slot 16 ch + (c ^ ch): the 16 lanes
+// that read one (row, half) of 16 channels fall on 16 different bank groups.  LDS-DMA writes
+// lane-linear, so the XOR is applied to the per-lane SOURCE address and again to the read address.
+// 8 KB per wave, inside the kWgRedLds the RED sum uses (reused behind a barrier).  Only the issuing
+// wave reads its zone, so its own vmcnt orders the ds_read: no barrier in the loop.  The operands,
+// and the order of every accumulator's MFMAs, are those of PF = false.
+constexpr int kWgZone = 2 * 16 * 64;  // floats per wave: [x, dY][16 channels][64]
+static_assert((size_t)4 * kWgZone * sizeof(float) <= kWgRedLds, "landing zones fit the RED buffer");
+#define NDP_WG_GLOBAL __attribute__((address_space(1)))
+#define NDP_WG_LDS __attribute__((address_space(3)))
+template <int H, int RED = 1, bool PF = false>
 __device__ __forceinline__ void wino_wgrad_body(const WinoWgradArgs& A, const uint3 bid, float* __restrict__ smem) {
+  static_assert(!PF || H == 8, "the LDS landing zone is laid out for the 8x8 maps");
   const float* __restrict__ x = A.x;
   const float* __restrict__ dy = A.dy;
   float* __restrict__ part = A.part;
@@ -120,6 +136,51 @@ __device__ __forceinline__ void wino_wgrad_body(const WinoWgradArgs& A, const ui
 #pragma unroll
         for (int k = 0; k < 4; ++k) gv[r][4 * c4 + k] = v[k];
       }
+  };
+  // PF: issue(n) = the 8 LDS-DMA loads of image n.  Instruction j, lane l fills slot 64 j + l: channel
+  // 4 j + l / 16, chunk (l % 16) ^ channel.  Every address lies inside the two 4 KB blocks.
+  float* zone = smem + wave * kWgZone;
+  const int pch = lane >> 4, pck = ((lane & 15) ^ pch) * 4;  // (the XOR with 4 j leaves pch's two bits alone)
+  auto issue = [&](int n) __attribute__((always_inline)) {
+    if constexpr (PF) {
+      const float* xa = x + ((int64_t)(b0 + n) * Cin + cib * 16) * HW;
+      const float* ga = dy + ((int64_t)(b0 + n) * Cout + cob * 16) * HW;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int off = (4 * j + pch) * HW + (pck ^ (16 * j));  // chunk ^ (4 j + pch), in floats
+        __builtin_amdgcn_global_load_lds((const NDP_WG_GLOBAL void*)(xa + off), (NDP_WG_LDS void*)(zone + j * 256), 16,
+                                         0, 0);
+        __builtin_amdgcn_global_load_lds((const NDP_WG_GLOBAL void*)(ga + off),
+                                         (NDP_WG_LDS void*)(zone + 16 * HW + j * 256), 16, 0, 0);
+      }
+    }
+  };
+  // land(): rows outside the image read the clamped row (an address inside the zone) and are zeroed
+  auto land = [&](float (&xv)[4][H], float (&gv)[2][H]) __attribute__((always_inline)) {
+    if constexpr (PF) {
+      const float* zx = zone + i * HW;
+      const float* zg = zone + 16 * HW + i * HW;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 2 * ty - 1 + r;
+        const bool ok = row >= 0 && row < H;
+        const int rc = row < 0 ? 0 : (row >= H ? H - 1 : row);
+#pragma unroll
+        for (int c4 = 0; c4 < H / 4; ++c4) {
+          const f32x4w v = *reinterpret_cast<const f32x4w*>(zx + 4 * ((2 * rc + c4) ^ i));
+#pragma unroll
+          for (int k = 0; k < 4; ++k) xv[r][4 * c4 + k] = ok ? v[k] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c4 = 0; c4 < H / 4; ++c4) {
+          const f32x4w v = *reinterpret_cast<const f32x4w*>(zg + 4 * ((2 * (2 * ty + r) + c4) ^ i));
+#pragma unroll
+          for (int k = 0; k < 4; ++k) gv[r][4 * c4 + k] = v[k];
+        }
+    }
   };
   f32x4w acc[16];
 #pragma unroll
@@ -192,7 +253,22 @@ __device__ __forceinline__ void wino_wgrad_body(const WinoWgradArgs& A, const ui
       if (n + 2 < imgs) load(n + 2, xr[0], gr[0]);
       step(xr[1], gr[1]);
     }
-  } else {  // 8x8: the 48 raw values of a second image in flight spill; two waves per SIMD hide it
+  } else if constexpr (PF) {
+    // 8x8, prefetched: image n + 1 lands in the zone (no registers: a second register set of 48 raw
+    // values spills) while image n, already in registers, runs its transforms and 64 MFMAs
+    issue(0);
+    for (int n = 0; n < imgs; ++n) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // image n has landed (this wave's own loads)
+      land(xr[0], gr[0]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ... and left the zone before it is refilled
+      __builtin_amdgcn_sched_barrier(0);
+      if (n + 1 < imgs) issue(n + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      step(xr[0], gr[0]);
+    }
+    // the RED sum below reuses the zones of all four waves
+    if constexpr (RED > 1) __syncthreads();
+  } else {  // 8x8, unpipelined (one image per wave, or the switch off): a second wave per SIMD hides the load
     for (int n = 0; n < imgs; ++n) {
       load(n, xr[0], gr[0]);
       step(xr[0], gr[0]);
@@ -246,10 +322,10 @@ __device__ __forceinline__ void wino_wgrad_body(const WinoWgradArgs& A, const ui
   }
 }
 
-template <int H, int RED = 1>
+template <int H, int RED = 1, bool PF = false>
 __global__ __launch_bounds__(256, 2) void wino_wgrad_kernel(WinoWgradArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  wino_wgrad_body<H, RED>(A, make_uint3(blockIdx.x, blockIdx.y, 0), smem);
+  wino_wgrad_body<H, RED, PF>(A, make_uint3(blockIdx.x, blockIdx.y, 0), smem);
 }
 
 // The layer1 backward pair in ONE launch: workgroups [0, n_dgrad) run the grad-x (wino_dpp_body on
@@ -257,7 +333,7 @@ __global__ __launch_bounds__(256, 2) void wino_wgrad_kernel(WinoWgradArgs A) {
 // dY / x / U and write disjoint outputs).  At the small per-GPU batches each of the two launches
 // fills about half of the CUs; together they run side by side instead of one after the other.
 // The grid is linearised x-fastest per part (the hardware's own dispatch order).
-template <int RED>
+template <int RED, bool PF = false>
 __global__ __launch_bounds__(256, 2) void wino_bwd_pair_kernel(WinoConvArgs A, uint3 ga, WinoWgradArgs W, uint3 gw) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const unsigned na = ga.x * ga.y * ga.z;
@@ -267,7 +343,7 @@ __global__ __launch_bounds__(256, 2) void wino_bwd_pair_kernel(WinoConvArgs A, u
     wino_dpp_body<8, 1>(A, id, ga, smem);
   } else {
     b -= na;
-    wino_wgrad_body<8, RED>(W, make_uint3(b % gw.x, b / gw.x, 0), smem);
+    wino_wgrad_body<8, RED, PF>(W, make_uint3(b % gw.x, b / gw.x, 0), smem);
   }
 }
 
@@ -350,6 +426,16 @@ bool wino_disabled() {
   return g_wino == 0;
 }
 void wino_set_enabled(bool on) { g_wino = on ? 1 : 0; }
+// NDP_FUSION_OFF=wgrad_pipe: the grad-W operand pipelining of both files (the LDS prefetch below, the
+// layer2 direct grad-W's 4-image stages in conv.hip) off for an A/B arm
+bool wgrad_pipe_off() {
+  static const bool off = [] {
+    const char* e = getenv("NDP_FUSION_OFF");
+    const std::string s = std::string(",") + (e ? e : "") + ",";
+    return s.find(",wgrad_pipe,") != std::string::npos || s.find(",all,") != std::string::npos;
+  }();
+  return off;
+}
 
 void launch_wino_weights(const float* w, float* u, int Co, int C, hipStream_t s) {
   hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)((Co / 16) * (C / 16)), 4), dim3(256), 0, s, w, u, Co, C);
@@ -399,28 +485,48 @@ bool wino_wgrad_ok(int C, int Co, int H) { return H == 8 && C % 16 == 0 && Co % 
 bool wino_wgrad_red(int B, int imgs) { return imgs % 4 == 0 && (B <= 128 || (B >= 256 && imgs == 16)); }
 // waves per (co, ci) block: 4 (above); 2 from batch 512 — the slice's images split over two waves
 // summed through LDS: twice the workgroups of RED = 1 at the same slab count, two waves per SIMD
-// instead of one (the 8x8 kernel keeps one image's operands in flight and relies on a second wave
-// to hide the loads).  ResNet-18 r=4 batch 512: alone even (1.4143 / 1.4147 vs 1.4184 / 1.4140 ms),
+// instead of one (measured while the 8x8 kernel kept one image's operands in flight and relied on a
+// second wave to hide the loads; it now prefetches the next image through LDS, wgrad_prefetch
+// below).  ResNet-18 r=4 batch 512: alone even (1.4143 / 1.4147 vs 1.4184 / 1.4140 ms),
 // with the layer1 grad-x pair it enables 1.3934 / 1.3966; batch 256: 1.0141 vs 0.9998 (kept at 1)
 static int wgrad_red(int B, int C, int Co, int imgs) {
   if (wino_wgrad_red(B, imgs)) return 4;
   return (B >= 512 && imgs % 2 == 0 && ((Co / 16) * (C / 16)) % 2 == 0) ? 2 : 1;
 }
+// The LDS prefetch of the next image (wino_wgrad_body PF) where a wave has one to prefetch: from two
+// images per wave and slice.  Off with NDP_FUSION_OFF=wgrad_pipe (A/B arm) or wino_set_wgrad_prefetch.
+static int g_wgrad_pf = -1;  // -1: by the switch
+static bool wgrad_prefetch(int imgs, int red) {
+  return (g_wgrad_pf < 0 ? !wgrad_pipe_off() : g_wgrad_pf == 1) && imgs / red >= 2;
+}
+void wino_set_wgrad_prefetch(bool on) { g_wgrad_pf = on ? 1 : 0; }
+
+template <int RED, bool PF>
+static void run_wino_wgrad(const WinoWgradArgs& a, int B, int nb, hipStream_t s) {
+  const dim3 grid((unsigned)(B / a.imgs), (unsigned)((nb + 4 / RED - 1) / (4 / RED)));
+  hipLaunchKernelGGL((wino_wgrad_kernel<8, RED, PF>), grid, dim3(256), (RED > 1 || PF) ? kWgRedLds : 0, s, a);
+}
 void launch_wino_wgrad(const float* x, const float* dy, float* part, int B, int C, int Co, int H, int imgs,
                        hipStream_t s) {
   if (H != 8) return;
   const WinoWgradArgs a{x, dy, part, C, Co, imgs};
-  const int red = wgrad_red(B, C, Co, imgs);
-  if (red == 4) {
-    const dim3 grid((unsigned)(B / imgs), (unsigned)((Co / 16) * (C / 16)));
-    hipLaunchKernelGGL((wino_wgrad_kernel<8, 4>), grid, dim3(256), kWgRedLds, s, a);
-  } else if (red == 2) {
-    const dim3 grid((unsigned)(B / imgs), (unsigned)((Co / 16) * (C / 16) / 2));
-    hipLaunchKernelGGL((wino_wgrad_kernel<8, 2>), grid, dim3(256), kWgRedLds, s, a);
-  } else {
-    const dim3 grid((unsigned)(B / imgs), (unsigned)(((Co / 16) * (C / 16) + 3) / 4));
-    hipLaunchKernelGGL((wino_wgrad_kernel<8, 1>), grid, dim3(256), 0, s, a);
+  const int red = wgrad_red(B, C, Co, imgs), nb = (Co / 16) * (C / 16);
+  const bool pf = wgrad_prefetch(imgs, red);
+  if (red == 4) pf ? run_wino_wgrad<4, true>(a, B, nb, s) : run_wino_wgrad<4, false>(a, B, nb, s);
+  else if (red == 2) pf ? run_wino_wgrad<2, true>(a, B, nb, s) : run_wino_wgrad<2, false>(a, B, nb, s);
+  else pf ? run_wino_wgrad<1, true>(a, B, nb, s) : run_wino_wgrad<1, false>(a, B, nb, s);
+}
+
+template <int RED, bool PF>
+static void run_wino_pair(unsigned n, size_t lds, hipStream_t s, const WinoConvArgs& a, uint3 ga,
+                          const WinoWgradArgs& w, uint3 gw) {
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(wino_bwd_pair_kernel<RED, PF>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr = true;
   }
+  hipLaunchKernelGGL((wino_bwd_pair_kernel<RED, PF>), dim3(n), dim3(256), lds, s, a, ga, w, gw);
 }
 
 // grad-x (layer1 class, unsplit or split-K into `part_x`) and grad-W slabs of one conv in one launch
@@ -440,19 +546,11 @@ void launch_wino_bwd_pair(const float* dy, const float* u, float* dx, int B, int
   const uint3 gw = make_uint3((unsigned)(B / imgs), (unsigned)(red == 4 ? nb : red == 2 ? nb / 2 : (nb + 3) / 4), 1);
   const unsigned n = ga.x * ga.y * ga.z + gw.x * gw.y;
   const size_t lds = kWLds > kWgRedLds ? kWLds : kWgRedLds;
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(wino_bwd_pair_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(wino_bwd_pair_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(wino_bwd_pair_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds);
-    attr = true;
-  }
-  if (red == 4) hipLaunchKernelGGL(wino_bwd_pair_kernel<4>, dim3(n), dim3(256), lds, s, a, ga, w, gw);
-  else if (red == 2) hipLaunchKernelGGL(wino_bwd_pair_kernel<2>, dim3(n), dim3(256), lds, s, a, ga, w, gw);
-  else hipLaunchKernelGGL(wino_bwd_pair_kernel<1>, dim3(n), dim3(256), lds, s, a, ga, w, gw);
+  const bool pf = wgrad_prefetch(imgs, red);
+  if (red == 4) pf ? run_wino_pair<4, true>(n, lds, s, a, ga, w, gw) : run_wino_pair<4, false>(n, lds, s, a, ga, w, gw);
+  else if (red == 2)
+    pf ? run_wino_pair<2, true>(n, lds, s, a, ga, w, gw) : run_wino_pair<2, false>(n, lds, s, a, ga, w, gw);
+  else pf ? run_wino_pair<1, true>(n, lds, s, a, ga, w, gw) : run_wino_pair<1, false>(n, lds, s, a, ga, w, gw);
 }
 
 }  // namespace ndp
