@@ -1192,6 +1192,38 @@ void ce_bwd(torch::Tensor dl, torch::Tensor g, torch::Tensor scratch, torch::Ten
   check_launch("launch_ce_bwd");
 }
 
+// fused evaluation metrics: state (fp64 [4]) += [loss sum, valid rows, top-1 correct, top-k correct];
+// rowbuf: fp32 scratch of >= 2 * B elements; pred (optional int64 [B]): first-maximum index.
+// Dtype / size checks come before the device checks, so they also answer for host tensors.
+void cls_metrics(torch::Tensor x, torch::Tensor tgt, torch::Tensor state, torch::Tensor rowbuf, torch::Tensor ctr,
+                 int64_t ignore_index, int64_t k, c10::optional<torch::Tensor> pred) {
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32, "cls_metrics: logits must be float32");
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), "cls_metrics: logits must be contiguous [B, K]");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) < (1LL << 30) && x.size(1) >= 1 && x.size(1) < (1LL << 31),
+              "cls_metrics: empty batch");
+  TORCH_CHECK(tgt.scalar_type() == torch::kInt64 && tgt.dim() == 1 && tgt.is_contiguous() && tgt.numel() == x.size(0),
+              "cls_metrics: target must be contiguous int64 [B]");
+  TORCH_CHECK(k >= 1 && k <= x.size(1), "cls_metrics: k must satisfy 1 <= k <= K (k = ", k, ", K = ", x.size(1), ")");
+  TORCH_CHECK(state.scalar_type() == torch::kFloat64 && state.numel() == 4 && state.is_contiguous(),
+              "cls_metrics: state must be a contiguous float64 tensor of 4 elements");
+  TORCH_CHECK(rowbuf.scalar_type() == torch::kFloat32 && rowbuf.is_contiguous() && rowbuf.numel() >= 2 * x.size(0),
+              "cls_metrics: rowbuf must be contiguous float32 of >= 2 * B elements");
+  TORCH_CHECK(ctr.scalar_type() == torch::kInt32 && ctr.numel() >= 1, "cls_metrics: int32 counter");
+  int64_t* pp = nullptr;
+  if (pred.has_value()) {
+    TORCH_CHECK(pred->scalar_type() == torch::kInt64 && pred->is_contiguous() && pred->numel() == x.size(0),
+                "cls_metrics: pred must be contiguous int64 [B]");
+    check_dev(*pred, "pred");
+    pp = pred->data_ptr<int64_t>();
+  }
+  check_dev(x, "logits"); check_dev(tgt, "target"); check_dev(state, "state"); check_dev(rowbuf, "rowbuf");
+  check_dev(ctr, "ctr");
+  ndp::launch_cls_metrics(x.data_ptr<float>(), tgt.data_ptr<int64_t>(), (int)x.size(0), (int)x.size(1), ignore_index,
+                          (int)k, state.data_ptr<double>(), rowbuf.data_ptr<float>(),
+                          reinterpret_cast<unsigned*>(ctr.data_ptr<int32_t>()), pp, cur_stream());
+  check_launch("launch_cls_metrics");
+}
+
 // fused residual add + LayerNorm (last dim D): y, s (= a + b), mean, rstd are outputs
 // LayerNorm hash dropout: mode 0 none / 1 on the input a / 2 on the output (layernorm.hip)
 static ndp::LnDrop ln_drop(int64_t mode, double p, const c10::optional<torch::Tensor>& seed,
@@ -1533,6 +1565,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_bwd_wgs", [](int64_t R) { return (int64_t)ndp::ln_bwd_wgs(R); });
   m.def("colsum_chunks", [](int64_t M, int64_t N) { return (int64_t)ndp::colsum_chunks(M, (int)N); });
   m.def("ce_bwd", &ce_bwd);
+  m.def("cls_metrics", &cls_metrics, py::arg("x"), py::arg("tgt"), py::arg("state"), py::arg("rowbuf"),
+        py::arg("ctr"), py::arg("ignore_index"), py::arg("k"), py::arg("pred") = py::none());
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   register_comm(m);

@@ -132,6 +132,165 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ d
   }
 }
 
+// ---- fused evaluation metrics: loss sum, valid rows, top-1 / top-k correct -----------------
+// ATen spends about eight launches and a host sync per batch on cross_entropy + topk + eq + sum
+// + .item().  One launch of the ce_fwd shape (one wave per row, 4 rows per workgroup) instead:
+//   lse as in ce_fwd, row loss = lse - x[t] (fp32), and the target's rank
+//     rank = #{j : x[j] > x[t]} + #{j < t : x[j] == x[t]}
+//   (top-1 correct iff rank == 0, which is "first maximum == t", top-k correct iff rank < k: ties
+//   resolve towards the lower index, deterministically).  A row that holds a NaN or whose target
+//   is outside [0, K) is incorrect at every k (rank = K) and its loss is NaN.  pred[b] (optional)
+//   is the index of the first maximum (a NaN counts as the maximum, like torch.argmax);
+//   rows whose target is ignore_index get pred = ignore_index and contribute nothing.
+//   (loss, rank) per row cross workgroups through sc1 stores; the last-arriving workgroup (the
+//   ce_fwd ticket, re-armed) adds them in a fixed order, the loss in fp64, and does
+//   state += [loss_sum, n_valid, correct1, correctk]: a whole validation pass accumulates on
+//   the device with no host sync, bitwise reproducible and hipGraph-replay safe.
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// argmax key: larger value first (NaN above everything, -0 == +0), then the lower index
+__device__ __forceinline__ unsigned long long argmax_key(float v, int k) {
+  unsigned u;
+  if (v != v) {
+    u = 0xffffffffu;
+  } else {
+    const unsigned bits = __float_as_uint(v + 0.f);
+    u = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+  }
+  return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - k);
+}
+
+__global__ __launch_bounds__(256) void cls_metrics_kernel(const float* __restrict__ x,
+                                                          const int64_t* __restrict__ tgt, int B, int K,
+                                                          int64_t ignore, int topk, double* __restrict__ state,
+                                                          float* __restrict__ rowbuf, unsigned* __restrict__ ctr,
+                                                          int64_t* __restrict__ pred) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x * kCeRowsPerWg + wave;
+  int* rowrank = reinterpret_cast<int*>(rowbuf + B);
+  if (b < B) {
+    const float* xr = x + (int64_t)b * K;
+    const int64_t t = tgt[b];
+    const bool valid = t != ignore;
+    const bool in_range = t >= 0 && t < K;
+    float rl = 0.f;
+    int rank = -1;  // ignored row
+    if (valid) {    // wave-uniform
+      const float xt = in_range ? xr[t] : __builtin_nanf("");
+      float m = -INFINITY, s = 0.f, lse;
+      int cnt = 0, bad = 0;
+      unsigned long long best = 0ull;
+      if (K <= 64 * kCeRegs) {  // the row in registers: one load pass
+        float v[kCeRegs];
+#pragma unroll
+        for (int i = 0; i < kCeRegs; ++i) {
+          const int k = lane + 64 * i;
+          v[i] = k < K ? xr[k] : -INFINITY;
+          m = fmaxf(m, v[i]);
+          if (k < K) {
+            const unsigned long long key = argmax_key(v[i], k);
+            best = key > best ? key : best;
+            bad |= v[i] != v[i];
+            cnt += (v[i] > xt || (v[i] == xt && k < t)) ? 1 : 0;
+          }
+        }
+        m = wave_max_f(m);
+#pragma unroll
+        for (int i = 0; i < kCeRegs; ++i) s += lane + 64 * i < K ? expf(v[i] - m) : 0.f;
+      } else {
+        for (int k = lane; k < K; k += 64) {
+          const float xv = xr[k];
+          m = fmaxf(m, xv);
+          const unsigned long long key = argmax_key(xv, k);
+          best = key > best ? key : best;
+          bad |= xv != xv;
+          cnt += (xv > xt || (xv == xt && k < t)) ? 1 : 0;
+        }
+        m = wave_max_f(m);
+        for (int k = lane; k < K; k += 64) s += expf(xr[k] - m);
+      }
+      s = wave_sum_f(s);
+      lse = m + logf(s);
+      cnt = wave_sum_i(cnt);
+      bad = wave_sum_i(bad);
+      best = wave_max_u64(best);
+      const bool ok = in_range && bad == 0;
+      rl = ok ? lse - xt : __builtin_nanf("");
+      rank = ok ? cnt : K;
+      if (pred != nullptr && lane == 0) pred[b] = (int64_t)(0x7fffffff - (int)(unsigned)(best & 0xffffffffull));
+    } else if (pred != nullptr && lane == 0) {
+      pred[b] = ignore;
+    }
+    if (lane == 0) {  // sc1 (write-through) stores: read back by the last workgroup below
+      __hip_atomic_store(rowbuf + b, rl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(rowrank + b, rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  // last-arriving workgroup: the ce_fwd ticket (sc1 stores drained before it, no release /
+  // acquire fence), then a fixed-order sum over the rows, the loss in fp64
+  __shared__ int last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned prev = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = prev == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler order only: the loads below are sc1
+  __shared__ double redl[4];
+  __shared__ int redc[3][4];
+  double a = 0.0;
+  int n = 0, c1 = 0, ck = 0;
+  for (int r = threadIdx.x; r < B; r += 256) {
+    const int rk = __hip_atomic_load(rowrank + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float l = __hip_atomic_load(rowbuf + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (rk >= 0) {
+      a += (double)l;
+      n += 1;
+      c1 += rk == 0 ? 1 : 0;
+      ck += rk < topk ? 1 : 0;
+    }
+  }
+  a = wave_sum_d(a);
+  n = wave_sum_i(n);
+  c1 = wave_sum_i(c1);
+  ck = wave_sum_i(ck);
+  if (lane == 0) {
+    redl[wave] = a;
+    redc[0][wave] = n;
+    redc[1][wave] = c1;
+    redc[2][wave] = ck;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    state[0] += ((redl[0] + redl[1]) + redl[2]) + redl[3];
+    state[1] += (double)(redc[0][0] + redc[0][1] + redc[0][2] + redc[0][3]);
+    state[2] += (double)(redc[1][0] + redc[1][1] + redc[1][2] + redc[1][3]);
+    state[3] += (double)(redc[2][0] + redc[2][1] + redc[2][2] + redc[2][3]);
+    __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 void launch_ce_fwd(const float* x, const int64_t* tgt, int B, int K, int64_t ignore, float* dl, float* rowloss,
                    float* loss, float* inv, unsigned* ctr, hipStream_t s, float* acc) {
   const unsigned wgs = (unsigned)((B + kCeRowsPerWg - 1) / kCeRowsPerWg);
@@ -142,6 +301,13 @@ void launch_ce_fwd(const float* x, const int64_t* tgt, int B, int K, int64_t ign
 void launch_ce_bwd(const float* dl, const float* g, const float* inv, float* dx, int64_t n, hipStream_t s) {
   const int64_t n4 = (n + 3) / 4;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dl, g, inv, dx, n);
+}
+
+void launch_cls_metrics(const float* x, const int64_t* tgt, int B, int K, int64_t ignore, int k, double* state,
+                        float* rowbuf, unsigned* ctr, int64_t* pred, hipStream_t s) {
+  const unsigned wgs = (unsigned)((B + kCeRowsPerWg - 1) / kCeRowsPerWg);
+  hipLaunchKernelGGL(cls_metrics_kernel, dim3(wgs), dim3(256), 0, s, x, tgt, B, K, ignore, k, state, rowbuf, ctr,
+                     pred);
 }
 
 }  // namespace ndp

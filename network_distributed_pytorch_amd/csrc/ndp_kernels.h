@@ -228,6 +228,11 @@ void launch_ce_fwd(const float* x, const int64_t* tgt, int B, int K, int64_t ign
                    float* loss, float* inv, unsigned* ctr, hipStream_t s, float* acc = nullptr);
 // dx = dl * (g[0] * inv[0])
 void launch_ce_bwd(const float* dl, const float* g, const float* inv, float* dx, int64_t n, hipStream_t s);
+// fused evaluation metrics: state[4] (fp64) += [loss sum, valid rows, top-1 correct, top-k correct]
+// over the rows whose target is not `ignore`; rowbuf [2 * B] scratch (row loss, then the target's
+// rank as int32 bits), ctr: one zeroed uint32 (re-armed), pred (nullable) [B]: first-maximum index
+void launch_cls_metrics(const float* x, const int64_t* tgt, int B, int K, int64_t ignore, int k, double* state,
+                        float* rowbuf, unsigned* ctr, int64_t* pred, hipStream_t s);
 }  // namespace ndp
 
 // ---- fused residual add + LayerNorm over the last dim (layernorm.hip) --------------------

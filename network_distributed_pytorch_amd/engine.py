@@ -14,7 +14,8 @@ print; the PowerSGD Algorithm-2 update and the dense SGD(momentum) update.
 Fixed / added: rank-0 parameter broadcast (Q3/Q4), a rank-identical
 IMDb split (Q2), a private PowerSGD RNG (Q1), configurable ``n_workers`` / batch
 (Q11/Q12), synthetic device-resident data, JSONL metrics, checkpoint/resume,
-replica-divergence checks, link emulation and hipGraph step capture.
+replica-divergence checks, link emulation, hipGraph step capture, and held-out evaluation
+(``eval_every``: :func:`evaluate`, the fused loss / top-1 / top-k pass of ops/metrics.py).
 """
 from __future__ import annotations
 
@@ -30,17 +31,19 @@ import torch.distributed as dist
 
 from .ops import gemm_tuning
 from .ops.loss import CrossEntropyLoss
+from .ops.metrics import ClassificationMetrics
 from .models import build_model
 from .parallel.comm import LINK_PRESETS, Communicator
 from .parallel.trainer import build_grad_sync
 from .utils.checkpoint import load_checkpoint, save_checkpoint
 from .utils.config import validate_config
-from .utils.data import DeviceLoader, SyntheticCIFAR10, SyntheticIMDb, train_val_split
+from .utils.data import (DeviceLoader, SyntheticCIFAR10, SyntheticIMDb, SyntheticMLPData, TensorDictDataset,
+                         train_val_split)
 from .utils.divergence import ReplicaChecker
-from .utils.metrics import JsonlLogger, PhaseTimer, print_epoch
+from .utils.metrics import JsonlLogger, PhaseTimer, print_epoch, print_eval
 from .utils.partition_helper import DataPartitioner
 
-__all__ = ["setup", "run_task", "cleanup", "device_for", "default_config"]
+__all__ = ["setup", "run_task", "cleanup", "device_for", "default_config", "evaluate", "Evaluator"]
 
 
 def default_config(**over) -> Dict[str, Any]:
@@ -57,6 +60,8 @@ def default_config(**over) -> Dict[str, Any]:
         # MIOpen's deterministic solver for any conv the native kernels do not cover (bitwise
         # resume); restored to the caller's setting by cleanup()
         deterministic=True,
+        # held-out evaluation every N epochs (0 = off), held-out size, k of the top-k accuracy
+        eval_every=0, eval_size=None, eval_topk=5,
     )
     cfg.update(over)
     return cfg
@@ -141,14 +146,22 @@ def _world():
 
 
 def _build_data(config, device, world, rank):
+    """(this rank's training partition, per-rank batch, held-out set or None).  Held-out data is
+    built only when ``eval_every`` > 0, and never changes the training data."""
     task = config["task"]
     seed = config["data_seed"]
+    want_val = bool(config.get("eval_every"))
+    eval_size = config.get("eval_size")
     if task == "cifar":
         n = config["dataset_size"] or 50000
-        ds = SyntheticCIFAR10(n=n, seed=seed, device=device)
+        val = None
+        if want_val:
+            ds, val = SyntheticCIFAR10(n=n, seed=seed, device=device, holdout=eval_size or 10000)
+        else:
+            ds = SyntheticCIFAR10(n=n, seed=seed, device=device)
         bsz = int(config["global_batch"] / float(world))
         part = DataPartitioner(ds, [1.0 / world for _ in range(world)]).use(rank)
-        return part, bsz, None
+        return part, bsz, val
     if task == "imdb":
         n = config["dataset_size"] or 25000
         seq = config.get("seq_len", 512)
@@ -157,18 +170,21 @@ def _build_data(config, device, world, rank):
         total_batch = config.get("global_batch") or 16 * world
         bsz = int(total_batch / float(world))
         part = DataPartitioner(train, [1.0 / world for _ in range(world)]).use(rank)
+        if not want_val:
+            val = None
+        elif eval_size is not None and eval_size < len(val):  # cap on the 20 % validation split
+            val = TensorDictDataset({k: v[:eval_size] for k, v in val.columns.items()}, val.as_tuple)
         return part, bsz, val
     if task == "mlp":
         n = config["dataset_size"] or 1024
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        from .utils.data import TensorDictDataset
-        x = torch.randn(n, 32, generator=g)
-        w = torch.randn(32, 4, generator=g)
-        y = (x @ w).argmax(1)
-        ds = TensorDictDataset({"data": x.to(device), "target": y.to(device)}, as_tuple=("data", "target"))
+        val = None
+        if want_val:
+            ds, val = SyntheticMLPData(n=n, seed=seed, device=device, holdout=eval_size or 256)
+        else:
+            ds = SyntheticMLPData(n=n, seed=seed, device=device)
         bsz = int(config["global_batch"] / float(world))
         part = DataPartitioner(ds, [1.0 / world for _ in range(world)]).use(rank)
-        return part, bsz, None
+        return part, bsz, val
     raise ValueError(f"unknown task {task!r}")
 
 
@@ -182,6 +198,120 @@ def _loss_fn(config, model, crit):
             data, target = batch
             return crit(model(data), target)
     return f
+
+
+class Evaluator:
+    """Held-out evaluation of ``model`` on ``dataset``: loss, top-1 and top-k by the fused metrics
+    kernel (ops/metrics.py), accumulated on the device; one fp64[4] all-reduce and one host sync
+    close the pass.
+
+    * runs under ``model.eval()`` and ``torch.no_grad()`` and puts the model back in the mode it
+      found; no buffer of the model changes;
+    * rank r evaluates ``index[r::world]``: every sample exactly once, none duplicated;
+    * batches are cut at ``batch`` (the per-rank TRAINING batch size: the same conv plans and
+      weight-bank schedule as training, one shape for the whole pass); the ragged last batch is
+      padded with zero inputs and ``target = ignore_index``, which the kernel drops;
+    * ``graph_mode != "none"`` on device: one eager warm-up batch, then forward + metrics launch
+      captured once as a linear graph on static inputs and replayed per batch; the graph is kept
+      on the evaluator and reused by later calls (the model's weights are read by the graph at
+      replay time, weight transforms included, so it always sees the current parameters);
+    * DistilBERT-style datasets (``input_ids`` / ``attention_mask`` / ``labels`` columns) call the
+      model without ``labels``; its logits feed the kernel.
+    """
+
+    def __init__(self, model, dataset, *, batch: int, comm=None, device=None, topk: int = 5,
+                 graph_mode: str = "none", ignore_index: int = -100):
+        first = next(iter(dataset.columns.values()))
+        self.device = torch.device(device) if device is not None else first.device
+        self.model = model
+        self.comm = comm
+        self.batch = int(batch)
+        assert self.batch >= 1, "evaluate: batch >= 1"
+        self.ignore_index = int(ignore_index)
+        self.ds = dataset if first.device == self.device else dataset.to(self.device)
+        world = comm.world_size if comm is not None else 1
+        rank = comm.rank if comm is not None else 0
+        self.index = torch.arange(len(dataset), device=self.device)[rank::world]
+        self.total = len(dataset)
+        if dataset.as_tuple:
+            self.inputs, self.target_key = [dataset.as_tuple[0]], dataset.as_tuple[1]
+        else:
+            self.inputs, self.target_key = ["input_ids", "attention_mask"], "labels"
+        cols = self.ds.columns
+        self.static = {k: torch.zeros((self.batch,) + tuple(cols[k].shape[1:]), dtype=cols[k].dtype,
+                                      device=self.device) for k in self.inputs}
+        self.static_target = torch.full((self.batch,), self.ignore_index, dtype=torch.int64, device=self.device)
+        self.metrics = ClassificationMetrics(k=topk, ignore_index=self.ignore_index, device=self.device)
+        self.graph_mode = graph_mode if self.device.type == "cuda" else "none"
+        self.graph = None
+        self.replays = 0
+
+    def _forward(self):
+        if len(self.inputs) == 1:
+            logits = self.model(self.static[self.inputs[0]])
+        else:
+            logits = self.model(self.static["input_ids"], attention_mask=self.static["attention_mask"])[-1]
+        self.metrics.update(logits, self.static_target)
+
+    def _load(self, idx: torch.Tensor):
+        m = int(idx.numel())
+        for k in self.inputs:
+            self.static[k][:m].copy_(self.ds.columns[k].index_select(0, idx))
+        self.static_target[:m].copy_(self.ds.columns[self.target_key].index_select(0, idx))
+        if m < self.batch:  # ragged tail: zero inputs, ignored targets
+            for k in self.inputs:
+                self.static[k][m:].zero_()
+            self.static_target[m:].fill_(self.ignore_index)
+
+    def _capture(self):
+        import gc
+
+        torch.cuda.synchronize()
+        gc.collect()  # no cyclic GC while capturing (see utils/graph.StepRunner.capture)
+        was = gc.isenabled()
+        gc.disable()
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._forward()
+        finally:
+            if was:
+                gc.enable()
+        self.graph = g
+
+    def __call__(self) -> Dict[str, Any]:
+        t0 = time.perf_counter()
+        was_training = self.model.training
+        self.model.eval()
+        self.metrics.reset()
+        try:
+            with torch.no_grad():
+                for s in range(0, len(self.index), self.batch):
+                    self._load(self.index[s: s + self.batch])
+                    if self.graph is not None:
+                        self.graph.replay()
+                        self.replays += 1
+                    else:
+                        self._forward()
+                        if self.graph_mode != "none":  # that was the eager warm-up batch
+                            state = self.metrics.state.clone()
+                            self._capture()  # a capture enqueues nothing: the state is untouched,
+                            self.metrics.state.copy_(state)  # restored all the same
+                rec = self.metrics.compute(self.comm)
+        finally:
+            self.model.train(was_training)
+        rec["comm_bytes"] = self.metrics.comm_bytes
+        rec["eval_s"] = time.perf_counter() - t0
+        return rec
+
+
+def evaluate(model, dataset, *, batch: int, comm=None, device=None, topk: int = 5, graph_mode: str = "none",
+             ignore_index: int = -100) -> Dict[str, Any]:
+    """One held-out pass (see :class:`Evaluator`): ``{"loss", "top1", "topk", "n", "k",
+    "comm_bytes", "eval_s"}``; ``topk`` is None when ``k`` is not below the class count.  Build an
+    :class:`Evaluator` yourself to reuse its captured graph across passes."""
+    return Evaluator(model, dataset, batch=batch, comm=comm, device=device, topk=topk, graph_mode=graph_mode,
+                     ignore_index=ignore_index)()
 
 
 def _batch_len(batch) -> int:
@@ -198,7 +328,7 @@ def run_task(config) -> Dict[str, Any]:
     _log(config, ">>>>> Run Designated Task <<<<<")
     device = device_for(config)
     world, rank = _world()
-    part, bsz, _val = _build_data(config, device, world, rank)
+    part, bsz, val = _build_data(config, device, world, rank)
     graph_mode = config.get("graph_mode", "auto")
     if device.type != "cuda":
         graph_mode = "none"
@@ -268,6 +398,13 @@ def run_task(config) -> Dict[str, Any]:
     health_every = int(config.get("check_health_every") or 0)
 
     timer = PhaseTimer() if (config.get("trace_phases") and runner is None) else None
+    eval_every = int(config.get("eval_every") or 0)
+    evaluator = None
+    if eval_every and val is not None:
+        evaluator = Evaluator(model, val, batch=bsz, comm=comm, device=device, topk=config.get("eval_topk", 5),
+                              graph_mode=graph_mode)
+    evals = []
+    eval_s = 0.0
     losses = []
     t_start = time.perf_counter()
     samples = 0
@@ -357,9 +494,21 @@ def run_task(config) -> Dict[str, Any]:
         if config.get("checkpoint_dir"):
             save_checkpoint(os.path.join(config["checkpoint_dir"], "last.pt"), model, sync, epoch=epoch, step=step,
                             rank=rank, world=world)
+        if evaluator is not None and (epoch + 1) % eval_every == 0:
+            # after runner.join() above: the pass reads the parameters of the last update.  Its
+            # all-reduce is accounted in the record, not in comm.stats / bytes_per_step, and its
+            # time is kept out of the training throughput
+            rec = dict(evaluator(), epoch=epoch)
+            if device.type == "cuda":
+                torch.cuda.synchronize()
+            eval_s += rec["eval_s"]
+            evals.append(rec)
+            if config.get("verbose", True):
+                print_eval(rank, epoch, rec)
+            logger.log(kind="eval", **rec)
     if device.type == "cuda":
         torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t_start
+    elapsed = time.perf_counter() - t_start - eval_s  # training time: evaluation is reported as eval_s
     _log(config, "All Task Finished")
     _log(config, "==============================\n")
     flat = getattr(getattr(sync, "opt", None), "x", None)
@@ -372,6 +521,9 @@ def run_task(config) -> Dict[str, Any]:
                "bytes_per_step": getattr(sync, "bytes_per_step", None), "comm": comm.stats.as_dict(),
                "comm_backend": comm.backend, "world_size": world, "per_rank_batch": bsz, "graph_mode": graph_mode,
                "param_checksum": float(flat.double().sum().item())}
+    if eval_every:
+        summary["eval"] = evals
+        summary["eval_s"] = eval_s
     logger.log(kind="summary", **{k: v for k, v in summary.items()})
     logger.close()
     summary["model"] = model

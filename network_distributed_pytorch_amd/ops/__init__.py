@@ -27,6 +27,8 @@ __all__ = [
     "upload",
     "SegPlan",
     "upload_epoch",
+    "classification_metrics",
+    "ClassificationMetrics",
 ]
 
 
@@ -263,3 +265,6 @@ def checksum(x: torch.Tensor) -> float:
         ext().checksum(x.reshape(-1), out)
         return float(out[0].item())
     return float(x.double().sum().item())
+
+
+from .metrics import ClassificationMetrics, classification_metrics  # noqa: E402  (fused eval metrics, csrc/loss.hip)

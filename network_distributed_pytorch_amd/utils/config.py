@@ -74,6 +74,10 @@ class TrainConfig:
     trace_phases: bool = False
     toy_mlp_steps: int = 0
     deterministic: bool = True  # MIOpen's deterministic solver while the run lasts (engine.setup)
+    # held-out evaluation (engine.evaluate): fused loss / top-1 / top-k pass over data never trained on
+    eval_every: int = 0  # evaluate every N epochs; 0 = off (no held-out data is built)
+    eval_size: Optional[int] = None  # held-out size (cifar 10,000, mlp 256; imdb: cap on its validation split)
+    eval_topk: int = 5  # k of the top-k accuracy
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -141,6 +145,8 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError("graph capture needs reuse_query=True (the per-step query re-draw is host-side)")
     if c["log_every"] < 1 or c["training_epochs"] < 0 or c["timeout_s"] <= 0:
         raise ConfigError("log_every >= 1, training_epochs >= 0, timeout_s > 0 required")
+    if c["eval_every"] < 0 or c["eval_topk"] < 1 or (c["eval_size"] is not None and c["eval_size"] < 1):
+        raise ConfigError("eval_every >= 0, eval_topk >= 1 and eval_size >= 1 (or None) required")
     if unknown:
         config["_unknown_keys"] = unknown
     return config

@@ -28,7 +28,8 @@ import torch
 
 from .partition_helper import Partition
 
-__all__ = ["SyntheticCIFAR10", "SyntheticIMDb", "train_val_split", "DeviceLoader", "TensorDictDataset"]
+__all__ = ["SyntheticCIFAR10", "SyntheticMLPData", "SyntheticIMDb", "train_val_split", "DeviceLoader",
+           "TensorDictDataset"]
 
 
 class TensorDictDataset:
@@ -57,20 +58,53 @@ class TensorDictDataset:
         return TensorDictDataset({k: v.to(device) for k, v in self.columns.items()}, self.as_tuple)
 
 
-def SyntheticCIFAR10(n: int = 50000, seed: int = 0, device=None, num_classes: int = 10,
-                     noise: float = 0.6) -> TensorDictDataset:
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    labels = torch.randint(0, num_classes, (n,), generator=g)
-    patterns = torch.rand(num_classes, 3, 4, 4, generator=g) * 2 - 1
-    base = torch.nn.functional.interpolate(patterns, size=(32, 32), mode="bilinear", align_corners=False)
+def _cifar_images(labels: torch.Tensor, base: torch.Tensor, noise: float, g: torch.Generator) -> torch.Tensor:
+    n = len(labels)
     imgs = torch.empty(n, 3, 32, 32)
     chunk = 8192
     for s in range(0, n, chunk):
         e = min(n, s + chunk)
         x = base[labels[s:e]] * (1 - noise) + (torch.rand(e - s, 3, 32, 32, generator=g) * 2 - 1) * noise
         imgs[s:e] = x.clamp_(-1, 1)
+    return imgs
+
+
+def SyntheticCIFAR10(n: int = 50000, seed: int = 0, device=None, num_classes: int = 10,
+                     noise: float = 0.6, holdout: int = 0):
+    """``holdout > 0``: returns ``(train, val)``; the ``holdout`` held-out labels and noise images
+    are drawn AFTER the training images from the same generator and class patterns, so ``train``
+    is bitwise the dataset of ``holdout=0`` (the patterns depend on how much of the generator
+    the labels consumed: never draw ``n + holdout`` labels in one go)."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    labels = torch.randint(0, num_classes, (n,), generator=g)
+    patterns = torch.rand(num_classes, 3, 4, 4, generator=g) * 2 - 1
+    base = torch.nn.functional.interpolate(patterns, size=(32, 32), mode="bilinear", align_corners=False)
+    imgs = _cifar_images(labels, base, noise, g)
     ds = TensorDictDataset({"data": imgs, "target": labels}, as_tuple=("data", "target"))
-    return ds.to(device) if device is not None else ds
+    ds = ds.to(device) if device is not None else ds
+    if not holdout:
+        return ds
+    vlabels = torch.randint(0, num_classes, (int(holdout),), generator=g)
+    val = TensorDictDataset({"data": _cifar_images(vlabels, base, noise, g), "target": vlabels},
+                            as_tuple=("data", "target"))
+    return ds, (val.to(device) if device is not None else val)
+
+
+def SyntheticMLPData(n: int = 1024, seed: int = 0, device=None, holdout: int = 0):
+    """The toy MLP task: 32 Gaussian features, 4 classes = argmax of a fixed random linear map.
+    ``holdout > 0``: ``(train, val)``, the held-out features drawn after the training draws from
+    the same generator and labelled by the same map (``train`` is bitwise the ``holdout=0`` data)."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    x = torch.randn(n, 32, generator=g)
+    w = torch.randn(32, 4, generator=g)
+    y = (x @ w).argmax(1)
+    ds = TensorDictDataset({"data": x, "target": y}, as_tuple=("data", "target"))
+    ds = ds.to(device) if device is not None else ds
+    if not holdout:
+        return ds
+    xv = torch.randn(int(holdout), 32, generator=g)
+    val = TensorDictDataset({"data": xv, "target": (xv @ w).argmax(1)}, as_tuple=("data", "target"))
+    return ds, (val.to(device) if device is not None else val)
 
 
 def SyntheticIMDb(n: int = 25000, seq_len: int = 512, vocab: int = 30522, seed: int = 0, device=None,

@@ -7,6 +7,7 @@
   lazily, so timing adds no host synchronisation inside the step.
 * :func:`print_epoch` — the reference's "Rank r, epoch e: mean loss" line
   (ddp_powersgd_guide_cifar10/ddp_init.py:183-184).
+* :func:`print_eval` — the held-out evaluation banner line (engine.evaluate), same style.
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-__all__ = ["JsonlLogger", "PhaseTimer", "print_epoch"]
+__all__ = ["JsonlLogger", "PhaseTimer", "print_epoch", "print_eval"]
 
 
 class JsonlLogger:
@@ -93,3 +94,9 @@ class PhaseTimer:
 
 def print_epoch(rank: int, epoch: int, mean_loss: float):
     print("     Rank ", rank, ", epoch ", epoch, ": ", mean_loss, flush=True)
+
+
+def print_eval(rank: int, epoch: int, rec: dict):
+    topk = "" if rec.get("topk") is None else ", top-{} {:.4f}".format(rec["k"], rec["topk"])
+    print("     Rank ", rank, ", epoch ", epoch, " eval: loss {:.6f}, top-1 {:.4f}{} over {} samples ({:.3f} s)".format(
+        rec["loss"], rec["top1"], topk, rec["n"], rec.get("eval_s", 0.0)), flush=True)

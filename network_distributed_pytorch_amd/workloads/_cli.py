@@ -8,7 +8,8 @@ default).  Additions: ``-spawn`` launches all ranks locally (127.0.0.1 rendezvou
 (PowerSGD rank), ``-batch`` (global batch), ``-graph_mode``, ``-link``, ``-backend``,
 ``-checkpoint_dir``, ``-resume``, ``-log_file`` (``{rank}`` in the path = one file per rank),
 ``-log_every``, ``-dataset_size``, ``-check_replicas``, ``-bucket_mb``, ``-reuse_query``,
-``-overlap``, ``-psgd_groups``, ``-emulate_world``.
+``-overlap``, ``-psgd_groups``, ``-emulate_world``, ``-eval_every`` / ``-eval_size`` / ``-eval_topk``
+(held-out evaluation every N epochs: loss, top-1, top-k).
 """
 from __future__ import annotations
 
@@ -53,6 +54,9 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-emulate_world", type=int, default=None, help="link emulation: charge an N-rank ring")
     p.add_argument("-log_every", type=int, default=None, help="per-step JSONL record cadence (0 = off)")
     p.add_argument("-seq_len", type=int, default=None, help="DistilBERT sequence length (reference 512)")
+    p.add_argument("-eval_every", type=int, default=None, help="held-out evaluation every N epochs (0 = off)")
+    p.add_argument("-eval_size", type=int, default=None, help="held-out samples (cifar 10000, mlp 256, imdb: cap)")
+    p.add_argument("-eval_topk", type=int, default=None, help="k of the top-k accuracy (default 5)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -64,7 +68,8 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "checkpoint_dir": "checkpoint_dir", "resume": "resume", "log_file": "log_file",
         "dataset_size": "dataset_size", "check_replicas": "check_replicas_every", "toy_steps": "toy_mlp_steps",
         "bucket_mb": "bucket_mb", "psgd_groups": "psgd_groups", "emulate_world": "emulate_world",
-        "log_every": "log_every", "seq_len": "seq_len"}
+        "log_every": "log_every", "seq_len": "seq_len", "eval_every": "eval_every", "eval_size": "eval_size",
+        "eval_topk": "eval_topk"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
