@@ -45,8 +45,12 @@ torch::Tensor to_bytes(const std::vector<T>& v) {
   return t;
 }
 
-py::dict build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank) {
-  ndp::Plan pl = ndp::build_plan(shapes, rank);
+// supports (empty, or one (T, mask) per matrix; T = 0: none): live conv taps for dead-tap compaction
+py::dict build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank,
+                    const std::vector<std::pair<int64_t, int64_t>>& supports) {
+  std::vector<ndp::TapSupport> sup;
+  for (const auto& s : supports) sup.push_back(ndp::TapSupport{(int32_t)s.first, (uint32_t)s.second});
+  ndp::Plan pl = ndp::build_plan(shapes, rank, sup);
   py::dict d;
   d["geom"] = to_bytes(pl.geom);
   d["p_items"] = to_bytes(pl.p_items);
@@ -81,7 +85,7 @@ py::dict build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int 
   d["q_item_start"] = starts(pl.q_items);
   d["u_item_start"] = starts(pl.u_items);
   d["orth_item_start"] = starts(pl.orth_items);
-  py::list rs, poff, qoff, ppoff, qpoff, pch, qch, qrows;
+  py::list rs, poff, qoff, ppoff, qpoff, pch, qch, qrows, tapT, tapL, ccols;
   for (size_t i = 0; i < pl.geom.size(); ++i) {
     rs.append(pl.geom[i].r);
     poff.append(pl.geom[i].p_off);
@@ -91,7 +95,13 @@ py::dict build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int 
     pch.append(pl.geom[i].p_chunks);
     qch.append(pl.geom[i].q_chunks);
     qrows.append(pl.q_rows[i]);
+    tapT.append(pl.geom[i].tap_T);
+    tapL.append(pl.geom[i].tap_L);
+    ccols.append(ndp::compact_cols(pl.geom[i]));
   }
+  d["tap_T"] = tapT;  // 0: the matrix is not compacted
+  d["tap_L"] = tapL;
+  d["compact_cols"] = ccols;
   d["ranks"] = rs;
   d["p_offs"] = poff;
   d["q_offs"] = qoff;
@@ -177,7 +187,7 @@ unsigned long long* ctr_ptr(const torch::Tensor& c, int64_t need, const char* wh
 // rank-1 pack run by the same launch's extra blocks
 void psgd_p(torch::Tensor geom, torch::Tensor ptrs, torch::Tensor items, torch::Tensor q_warm,
             torch::Tensor p_part, bool fuse_ef, int max_rank, OptT p_prev, OptT p_out, OptT p_ctr,
-            OptT seg_entries, OptT seg_prefix, int64_t seg_n, int64_t seg_blocks, int64_t p_cols) {
+            OptT seg_entries, OptT seg_prefix, int64_t seg_n, int64_t seg_blocks, int64_t p_cols, OptT err) {
   check_dev(geom, "geom"); check_dev(ptrs, "ptrs"); check_dev(items, "items");
   check_f32(q_warm, "q_warm"); check_f32(p_part, "p_part");
   const float* pp = nullptr;
@@ -188,6 +198,11 @@ void psgd_p(torch::Tensor geom, torch::Tensor ptrs, torch::Tensor items, torch::
   }
   const int n_items = (int)n_of(items, sizeof(PItem));
   ndp::PFin fin{};
+  if (err.has_value()) {  // the orth counters: the sticky error word is the low half of the last
+    check_dev(*err, "err");
+    TORCH_CHECK(err->scalar_type() == torch::kInt64 && err->numel() >= 1, "psgd_p: err is the int64 counter tensor");
+    fin.err = reinterpret_cast<unsigned*>(err->data_ptr<int64_t>() + err->numel() - 1);
+  }
   if (p_out.has_value()) {
     TORCH_CHECK(max_rank <= ndp::kUWideMaxRank, "psgd_p: in-kernel split-K finish needs rank <= 16");
     TORCH_CHECK(p_ctr.has_value(), "psgd_p: p_out needs p_ctr");
@@ -1438,7 +1453,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("SIZEOF_MATPTRS") = (int)sizeof(MatPtrs);
   m.attr("SIZEOF_SEGENTRY") = (int)sizeof(SegEntry);
   m.attr("MAX_RANK") = ndp::kMaxRank;
-  m.def("build_plan", &build_plan, "Build the PowerSGD execution plan (host)");
+  m.def("build_plan", &build_plan, "Build the PowerSGD execution plan (host)", py::arg("shapes"), py::arg("rank"),
+        py::arg("supports") = std::vector<std::pair<int64_t, int64_t>>{});
   m.def("patch_geom_vec", &patch_geom_vec);
   m.def("make_mat_ptrs", &make_mat_ptrs);
   m.def("make_seg_table", &make_seg_table);
@@ -1446,7 +1462,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("psgd_p", &psgd_p, py::arg("geom"), py::arg("ptrs"), py::arg("items"), py::arg("q_warm"), py::arg("p_part"),
         py::arg("fuse_ef"), py::arg("max_rank"), py::arg("p_prev") = OptT(), py::arg("p_out") = OptT(),
         py::arg("p_ctr") = OptT(), py::arg("seg_entries") = OptT(), py::arg("seg_prefix") = OptT(),
-        py::arg("seg_n") = 0, py::arg("seg_blocks") = 0, py::arg("p_cols") = (int64_t)ndp::kPKW);
+        py::arg("seg_n") = 0, py::arg("seg_blocks") = 0, py::arg("p_cols") = (int64_t)ndp::kPKW,
+        py::arg("err") = OptT());
   m.def("psgd_q", &psgd_q, py::arg("geom"), py::arg("ptrs"), py::arg("items"), py::arg("p_hat"), py::arg("q_part"),
         py::arg("max_rank"), py::arg("q_out") = OptT(), py::arg("q_ctr") = OptT(), py::arg("q_fin_max") = 1 << 30);
   m.def("psgd_orth", &psgd_orth, py::arg("geom"), py::arg("items"), py::arg("p"), py::arg("p_div"),

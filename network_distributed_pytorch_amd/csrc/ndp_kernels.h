@@ -20,8 +20,20 @@ struct MatGeom {
   int32_t p_off, q_off; // element offsets into the flat P / Q buffers (reference order)
   int32_t pp_off, qp_off;     // element offsets into the P / Q split-K partial scratch
   int32_t p_chunks, q_chunks; // number of split-K slabs for P (over m) and Q (over n)
-  int32_t pad[6];
+  // Dead-tap compaction (wide plans only; tap_T == 0: none).  The matrix is a conv weight whose
+  // columns repeat with period tap_T = KH*KW, and only tap_L of those taps can ever receive
+  // gradient.  Its error memory and momentum are then stored as [n, (m / tap_T) * tap_L]:
+  // compact column j is full column (j / tap_L) * tap_T + tap[j % tap_L].  The parameter, its
+  // gradient and the P / Q buffers keep the full layout.  With tap_T != 0, `vec` is two bits:
+  // 1 = float4 on the full-width gradient (P pass), 2 = float4 on the compact M (Q pass).
+  int32_t tap_T, tap_L;
+  uint32_t taps[2];           // live taps, ascending, 4 bits each (tap_T <= kMaxTapPeriod)
+  uint32_t tap_mask;          // bit t set = tap t is live
+  int32_t pad;
 };
+constexpr int kMaxTapPeriod = 16;
+// live taps of one matrix for the plan builder: period T (0 = no support known) and bitmask
+struct TapSupport { int32_t T; uint32_t mask; };
 
 // ---- per-matrix bound pointers (64 B) -------------------------------------------
 // engine mode : min = grad, e = error memory (M = g + e is written back into e),
@@ -85,6 +97,7 @@ constexpr int kSegBlockElems = 2048;  // elements per workgroup in seg_reduce
 // the partials for a separate seg_reduce.  P's extra blocks [n_items, grid) run a seg table (the
 // rank-1 group's pack into the comm buffer), so the P stage is ONE launch.
 struct PFin {
+  unsigned* err;                 // sticky error word: |= kErrDeadTapGrad on a nonzero dead-tap gradient
   float* out;                    // final P (comm buffer, MatGeom.p_off)
   unsigned long long* ctr;       // [n row blocks]
   const SegEntry* seg;           // optional reduce-copy table run by the extra blocks
@@ -123,6 +136,9 @@ int orth_rows_per_thread(int max_rank);
 // workgroups of ONE matrix the MGS barrier may span: occupancy x CUs / 2 (-1: no device)
 int orth_coresident_cap(int max_rank);
 constexpr unsigned kOrthMaxSpins = 1u << 25;  // ~seconds of s_sleep 2
+// bits of the sticky device error word shared by the orth and P kernels
+constexpr unsigned kErrOrthTimeout = 1u;
+constexpr unsigned kErrDeadTapGrad = 2u;
 // mode 0 = api (out/mem), 1 = engine (EF + momentum + SGD), 2 = engine + write grad,
 // 3 = e -= p_hat q_sum^T / q_div only (materialise the lazy error, rank <= kUWideMaxRank);
 // p_prev (modes 1 / 2, rank <= kUWideMaxRank): lazy error feedback — e is not written, the

@@ -35,7 +35,29 @@ int64_t p_item_cols(int plan_rank) {
 
 static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-Plan build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank) {
+// the dead-tap layout of one matrix (MatGeom tap_*), or nothing when it does not qualify
+static void set_taps(MatGeom& g, const TapSupport& s) {
+  if (s.T < 2 || s.T > kMaxTapPeriod || g.m % s.T != 0) return;
+  const uint32_t mask = s.mask & ((1u << s.T) - 1u);
+  int L = 0;
+  uint32_t taps[2] = {0u, 0u};
+  for (int t = 0; t < s.T; ++t)
+    if (mask >> t & 1u) {
+      taps[L >> 3] |= (uint32_t)t << (4 * (L & 7));
+      ++L;
+    }
+  if (L < 1 || L >= s.T) return;  // nothing live is not a conv; nothing dead saves nothing
+  g.tap_T = s.T;
+  g.tap_L = L;
+  g.taps[0] = taps[0];
+  g.taps[1] = taps[1];
+  g.tap_mask = mask;
+}
+
+Plan build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank,
+                const std::vector<TapSupport>& supports) {
+  if (!supports.empty() && supports.size() != shapes.size())
+    throw std::invalid_argument("PowerSGD plan: one tap support per matrix");
   if (rank < 1 || rank > kMaxRank)
     throw std::invalid_argument("PowerSGD rank must be in [1, 64]");
   Plan pl;
@@ -67,6 +89,9 @@ Plan build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank
     g.q_chunks = (int32_t)cdiv(n, rc);
     g.pp_off = (int32_t)pp_off;
     g.qp_off = (int32_t)qp_off;
+    // dead-tap compaction: wide kernels only; the Q and update items then tile the compact columns
+    if (wide && !supports.empty()) set_taps(g, supports[i]);
+    const int64_t mc = compact_cols(g);
     pl.geom.push_back(g);
     pl.q_rows.push_back((int32_t)rc);
 
@@ -84,7 +109,7 @@ Plan build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank
     // a column block's row chunks are consecutive in the grid, so the in-kernel finishes
     // (last arriver per column block) are spread over the launch instead of all at its end
     const int32_t cb0 = (int32_t)pl.n_q_blocks;
-    for (int64_t col0 = 0; col0 < m; col0 += kQCols)
+    for (int64_t col0 = 0; col0 < mc; col0 += kQCols)
       for (int64_t c = 0; c < g.q_chunks; ++c) {
         QItem it{};
         it.mat = (int32_t)i;
@@ -95,9 +120,9 @@ Plan build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank
         it.cb = cb0 + (int32_t)(col0 / kQCols);
         pl.q_items.push_back(it);
       }
-    pl.n_q_blocks += cdiv(m, kQCols);
+    pl.n_q_blocks += cdiv(mc, kQCols);
     for (int64_t row0 = 0; row0 < n; row0 += u_rows)
-      for (int64_t col0 = 0; col0 < m; col0 += u_cols) {
+      for (int64_t col0 = 0; col0 < mc; col0 += u_cols) {
         UItem it{};
         it.mat = (int32_t)i;
         it.row0 = (int32_t)row0;

@@ -21,8 +21,29 @@ struct Plan {
   int32_t p_cols = kPKW;  // columns per P item (wide plans)
 };
 
-// shapes[i] = (n_i, m_i) of every >1-D tensor, in model.parameters() order
-Plan build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank);
+// shapes[i] = (n_i, m_i) of every >1-D tensor, in model.parameters() order.
+// supports (empty, or one per matrix): the live taps of conv weights; a matrix with dead taps in a
+// wide plan (max rank <= kUWideMaxRank) keeps its error memory and momentum compact (MatGeom
+// tap_*): its Q and update items tile the compact columns, its P items are unchanged.
+Plan build_plan(const std::vector<std::pair<int64_t, int64_t>>& shapes, int rank,
+                const std::vector<TapSupport>& supports = {});
+
+// columns of a matrix's error-memory / momentum slot (m unless compacted)
+inline int64_t compact_cols(const MatGeom& g) {
+  return g.tap_T ? (int64_t)(g.m / g.tap_T) * g.tap_L : (int64_t)g.m;
+}
+// full column of compact column j (identity unless compacted), and the inverse (-1: dead tap)
+inline int64_t full_col(const MatGeom& g, int64_t j) {
+  if (!g.tap_T) return j;
+  const int64_t k = j % g.tap_L;
+  return (j / g.tap_L) * g.tap_T + (g.taps[k >> 3] >> (4 * (k & 7)) & 15u);
+}
+inline int64_t compact_col(const MatGeom& g, int64_t b) {
+  if (!g.tap_T) return b;
+  const int t = (int)(b % g.tap_T);
+  if (!(g.tap_mask >> t & 1u)) return -1;
+  return (b / g.tap_T) * g.tap_L + __builtin_popcount(g.tap_mask & ((1u << t) - 1u));
+}
 
 // multi-workgroup MGS work list for the given matrices (rows split in 256*RPT blocks)
 std::vector<OrthItem> build_orth_items(const std::vector<MatGeom>& geom, int max_rank);

@@ -13,9 +13,11 @@
 //    v_mfma_f32_16x16x4_f32 (exact f32, k-ordered fmaf chain), the small operand (Q or P)
 //    is staged in LDS and shared by the 4 waves of a workgroup, the big operand (M) is
 //    streamed straight to VGPRs with 16-B loads (cdna_hip_programming.md §5 'GEMV' row).
-//  * Split-K partials are written to slabs and summed in a fixed order by seg_reduce,
-//    so P and Q are bitwise reproducible: every rank computes the identical P-hat and the
-//    identical decompressed gradient (SURVEY.md §7.4 hard part 1).  No float atomics.
+//  * Split-K partials are written to slabs and summed in chunk order — by the last-arriving
+//    workgroup of the same launch (PFin / QFin below), or by a separate seg_reduce for the
+//    narrow kernels and for matrices with more row chunks than QFin::max_chunks — so P and Q
+//    are bitwise reproducible: every rank computes the identical P-hat and the identical
+//    decompressed gradient (SURVEY.md §7.4 hard part 1).  No float atomics.
 //  * M = g + e is formed on the fly in the P pass and written back into e, so the Q and
 //    update passes read one array; the update pass fuses decompression, error feedback,
 //    momentum and the parameter update (one read-modify-write of e, m, x).
@@ -60,6 +62,29 @@ __device__ __forceinline__ GPtrs gptrs(const MatPtrs& p) {
 }
 __device__ __forceinline__ f32x4 ld4(const float NDP_GLOBAL* p) { return *reinterpret_cast<const f32x4 NDP_GLOBAL*>(p); }
 __device__ __forceinline__ void st4(float NDP_GLOBAL* p, f32x4 v) { *reinterpret_cast<f32x4 NDP_GLOBAL*>(p) = v; }
+
+// ---- dead-tap compaction (MatGeom tap_*; plan.cpp) --------------------------------------
+// columns of the compact error-memory / momentum slot
+__device__ __forceinline__ int tap_cols(const MatGeom& g) { return (g.m / g.tap_T) * g.tap_L; }
+// full column of compact column j
+__device__ __forceinline__ int tap_full(const MatGeom& g, int j) {
+  const int q = j / g.tap_L, k = j - q * g.tap_L;
+  const uint32_t w = k < 8 ? g.taps[0] : g.taps[1];
+  return q * g.tap_T + (int)(w >> (4 * (k & 7)) & 15u);
+}
+// compact columns of the full columns b .. b + 3 below `end` (-1: dead tap or past the end)
+__device__ __forceinline__ void tap_compact4(const MatGeom& g, int b, int end, int (&cx)[4]) {
+  int q = b / g.tap_T, t = b - q * g.tap_T;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool live = (g.tap_mask >> t & 1u) != 0u && b + j < end;
+    cx[j] = live ? q * g.tap_L + __popc(g.tap_mask & ((1u << t) - 1u)) : -1;
+    if (++t == g.tap_T) {
+      t = 0;
+      ++q;
+    }
+  }
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
   // xor butterfly: every lane ends with the bitwise-identical total (fp add commutes)
@@ -199,8 +224,11 @@ __device__ __forceinline__ void wave_reduce_spread(float (&v)[V], int lane) {
     const bool upper = (lane & o) != 0;
 #pragma unroll
     for (int k = 0; k < c / 2; ++k) {
-      const float send = upper ? v[k] : v[k + c / 2];
-      const float keep = upper ? v[k + c / 2] : v[k];
+      // (both values read first: a select between the two array elements' addresses can keep the
+      // array from being split into registers)
+      const float lo = v[k], hi = v[k + c / 2];
+      const float send = upper ? lo : hi;
+      const float keep = upper ? hi : lo;
       v[k] = keep + __shfl_xor(send, o, 64);
     }
   }
@@ -281,8 +309,15 @@ __device__ __forceinline__ bool last_arrival(unsigned long long* ctr, int chunks
   return last;
 }
 
+// waves per SIMD each instance reached before the dead-tap paths were added; the compiler is held
+// to them (the tap state costs SGPRs, and SGPRs spilled to VGPR lanes cost a wave at 96 / 128)
+constexpr int p_wide_waves(int RQ, int NS, int SB) {
+  return RQ <= 4 ? (NS <= 2 ? 5 : 3) : RQ <= 8 ? (NS <= 2 ? 4 : 2) : (NS == 1 ? 3 : NS == 2 ? 2 : 1);
+}
+
 template <int RQ, int NT = 0, int NS = kPKW / 256, int SB = (RQ <= 4 ? NS : (NS < 2 ? NS : 2))>
-__global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restrict__ geom,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(p_wide_waves(RQ, NS, SB))))
+void psgd_p_wide_kernel(const MatGeom* __restrict__ geom,
                                                           const MatPtrs* __restrict__ ptrs,
                                                           const PItem* __restrict__ items,
                                                           const float* __restrict__ q_warm,
@@ -306,6 +341,12 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
   const bool active = arow0 < n;  // inactive waves still reach the finish's barriers
   const float* Q = q_warm + g.q_off;
   const bool q4 = (r & 3) == 0 && (g.q_off & 3) == 0;
+  // Dead-tap compaction: g, Q and the whole fmaf sequence keep the full columns (the dead
+  // gradient entries are real zeros, so P is bitwise the full layout's); only the e / M_prev
+  // loads and the M stores go to the compact slot, one predicated 4-byte access per live column.
+  const bool tapped = g.tap_T != 0;
+  const int mc = tapped ? tap_cols(g) : m;
+  const bool gvec = (g.vec & 1) != 0;
 
   float acc[V];
 #pragma unroll
@@ -315,10 +356,18 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
   // not for the whole e stream's write acknowledgements.
   constexpr bool kLateE = SB == NS;
   f32x4 late[kLateE ? 4 : 1][kLateE ? SB : 1];
+  // (one uniform base and 32-bit lane offsets: 4 mc < 2^32, and no row pointer held in SGPRs)
+  auto store_c = [&](int i, const int (&cx)[4], f32x4 v) {
+    if (arow0 + i >= n) return;
+    float NDP_GLOBAL* base = pt.e + (int64_t)arow0 * mc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (cx[j] >= 0) base[(unsigned)i * (unsigned)mc + (unsigned)cx[j]] = v[j];
+  };
   auto store_e = [&](int i, int b, f32x4 v) {
     if (arow0 + i >= n) return;
     const int64_t o = (int64_t)(arow0 + i) * m + b;
-    if (g.vec) {
+    if (gvec) {
       if (b < it.k1) {
         if constexpr (NT >= 2) __builtin_nontemporal_store(v, reinterpret_cast<f32x4 NDP_GLOBAL*>(pt.e + o));
         else st4(pt.e + o, v);
@@ -331,7 +380,15 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
   };
   auto store_late = [&]() {
     if constexpr (kLateE) {
-      if (active && fuse_ef) {
+      if (active && fuse_ef && tapped) {
+#pragma unroll
+        for (int sb = 0; sb < SB; ++sb) {
+          int cx[4];
+          tap_compact4(g, it.k0 + 256 * sb + 4 * lane, it.k1, cx);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) store_c(i, cx, late[i][sb]);
+        }
+      } else if (active && fuse_ef) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -346,7 +403,8 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
     // the HBM stream of SB slices first: g and e of the wave's 4 rows (combined below, once
     // the lane's Q rows are in registers: the lazy correction needs them)
     f32x4 mv[4][SB], ev[4][SB];
-    if (g.vec) {
+    const bool ld_e = fuse_ef && !tapped;
+    if (gvec) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -357,11 +415,11 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
           if constexpr (NT >= 1) {
             mv[i][sb] = ok ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(pt.min + o))
                            : f32x4{0.f, 0.f, 0.f, 0.f};
-            ev[i][sb] = (ok && fuse_ef) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(pt.e + o))
-                                        : f32x4{0.f, 0.f, 0.f, 0.f};
+            ev[i][sb] = (ok && ld_e) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(pt.e + o))
+                                     : f32x4{0.f, 0.f, 0.f, 0.f};
           } else {
             mv[i][sb] = ok ? ld4(pt.min + o) : f32x4{0.f, 0.f, 0.f, 0.f};
-            ev[i][sb] = (ok && fuse_ef) ? ld4(pt.e + o) : f32x4{0.f, 0.f, 0.f, 0.f};
+            ev[i][sb] = (ok && ld_e) ? ld4(pt.e + o) : f32x4{0.f, 0.f, 0.f, 0.f};
           }
         }
     } else {
@@ -377,12 +435,33 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
             if (arow0 + i < n && b + j < it.k1) {
               const int64_t o = (int64_t)(arow0 + i) * m + b + j;
               t[j] = pt.min[o];
-              if (fuse_ef) u[j] = pt.e[o];
+              if (ld_e) u[j] = pt.e[o];
             }
           }
           mv[i][sb] = f32x4{t[0], t[1], t[2], t[3]};
           ev[i][sb] = f32x4{u[0], u[1], u[2], u[3]};
         }
+    }
+    if (tapped) {  // e / M_prev of the live columns from the compact slot; dead columns: e = +0
+      bool dead_grad = false;  // a nonzero gradient in a dead tap: the support was wrong
+#pragma unroll
+      for (int sb = 0; sb < SB; ++sb) {
+        int cx[4];
+        tap_compact4(g, it.k0 + 256 * (s0 + sb) + 4 * lane, it.k1, cx);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const bool rok = arow0 + i < n;
+          const float NDP_GLOBAL* base = pt.e + (int64_t)arow0 * mc;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (fuse_ef && rok && cx[j] >= 0) ev[i][sb][j] = base[(unsigned)i * (unsigned)mc + (unsigned)cx[j]];
+            // rows past n and columns past k1 were loaded as 0
+            if (cx[j] < 0 && mv[i][sb][j] != 0.f) dead_grad = true;
+          }
+        }
+      }
+      if (dead_grad && fin.err != nullptr)
+        __hip_atomic_fetch_or(fin.err, kErrDeadTapGrad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // Q rows of this lane's columns (L2-resident: m x r floats per matrix)
 #pragma unroll
@@ -405,6 +484,8 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
         }
       }
       if (fuse_ef) {
+        int cx[4];
+        if (!kLateE && tapped) tap_compact4(g, b, it.k1, cx);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           f32x4 e4 = ev[i][sb];
@@ -423,6 +504,7 @@ __global__ __launch_bounds__(256) void psgd_p_wide_kernel(const MatGeom* __restr
           }
           mv[i][sb] = mv[i][sb] + e4;  // send = g + e   (ddp_init.py:156-157)
           if constexpr (kLateE) late[i][sb] = mv[i][sb];
+          else if (tapped) store_c(i, cx, mv[i][sb]);
           else store_e(i, b, mv[i][sb]);
         }
       }
@@ -486,12 +568,17 @@ __global__ __launch_bounds__(256) void psgd_q_kernel(const MatGeom* __restrict__
   const int r = g.r;
   const int nrows = it.row1 - it.row0;
   const int nrows4 = (nrows + 3) & ~3;
+  // dead-tap compaction: the item's columns are compact columns of M (row stride mcols); the Q
+  // rows they produce keep their full index, the dead Q rows are never written (zeroed once)
+  const bool tapped = g.tap_T != 0;
+  const int mcols = tapped ? tap_cols(g) : g.m;
+  const bool mvec = tapped ? (g.vec & 2) != 0 : g.vec != 0;
   const int b0 = it.col0 + wave * 64;
-  const bool active = b0 < g.m;  // inactive waves still reach the finish's barriers
+  const bool active = b0 < mcols;  // inactive waves still reach the finish's barriers
   const int bl = b0 + 4 * (lane & 15);
   const int rsub = lane >> 4;
   const int cl = lane & 15;
-  const float NDP_GLOBAL* Mb = pt.mread + (int64_t)it.row0 * g.m;
+  const float NDP_GLOBAL* Mb = pt.mread + (int64_t)it.row0 * mcols;
 
   const float* P = p_hat + g.p_off + (int64_t)it.row0 * r;
   auto stage_p = [&]() {
@@ -513,14 +600,14 @@ __global__ __launch_bounds__(256) void psgd_q_kernel(const MatGeom* __restrict__
     const int al = s + rsub;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (al < nrows) {
-      const float NDP_GLOBAL* row = Mb + (int64_t)al * g.m;
-      if (g.vec) {
-        if (bl < g.m) v = kQNT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(row + bl))
+      const float NDP_GLOBAL* row = Mb + (int64_t)al * mcols;
+      if (mvec) {
+        if (bl < mcols) v = kQNT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(row + bl))
                                : ld4(row + bl);
       } else {
         float t[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) t[j] = (bl + j < g.m) ? row[bl + j] : 0.f;
+        for (int j = 0; j < 4; ++j) t[j] = (bl + j < mcols) ? row[bl + j] : 0.f;
         v = f32x4{t[0], t[1], t[2], t[3]};
       }
     }
@@ -573,7 +660,24 @@ __global__ __launch_bounds__(256) void psgd_q_kernel(const MatGeom* __restrict__
   const bool direct = fin.out != nullptr && chunks == 1;
   const bool sc1 = fin.out != nullptr && chunks > 1 && chunks <= fin.max_chunks;
   float* dst = direct ? fin.out + g.q_off : q_part + g.qp_off + (int64_t)it.chunk * g.m * r;
-  if (active) {
+  if (active && tapped) {
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int b = b0 + 4 * (4 * rsub + reg) + j;
+        if (b >= mcols) continue;
+        float* qrow = dst + (int64_t)tap_full(g, b) * r;
+#pragma unroll
+        for (int cg = 0; cg < NCG; ++cg) {
+          const int c = cg * 16 + cl;
+          if (c >= r) continue;
+          if (sc1) st_sc1(qrow + c, acc[cg][j][reg]);
+          else qrow[c] = acc[cg][j][reg];
+        }
+      }
+    }
+  } else if (active) {
 #pragma unroll
     for (int cg = 0; cg < NCG; ++cg) {
       const int c = cg * 16 + cl;
@@ -594,9 +698,10 @@ __global__ __launch_bounds__(256) void psgd_q_kernel(const MatGeom* __restrict__
   if (!sc1) return;
   __syncthreads();  // every wave is done reading the P-hat tile: smem[0] may carry the flag
   if (!last_arrival(fin.ctr + it.cb, chunks, reinterpret_cast<int*>(smem))) return;
-  const int cols = min(kQCols, g.m - it.col0);
+  const int cols = min(kQCols, mcols - it.col0);
   for (int t = threadIdx.x; t < cols * r; t += 256) {
-    const int64_t o = (int64_t)it.col0 * r + t;  // row-major m x r: the block's columns are contiguous
+    // row-major m x r: the block's columns are contiguous (compacted: each column's Q row is)
+    const int64_t o = tapped ? (int64_t)tap_full(g, it.col0 + t / r) * r + t % r : (int64_t)it.col0 * r + t;
     fin.out[g.q_off + o] = chunk_sum_sc1(q_part + g.qp_off, (int64_t)g.m * r, chunks, o,
                                          (int64_t)chunks * g.m * r * 4);
   }
@@ -718,11 +823,121 @@ __global__ __launch_bounds__(256) void psgd_update_kernel(
 // ----------------------------------------------------------------------------------
 constexpr int kURowsPerWave = kUWideRows / 4;
 
+// The tile of a dead-tap compacted matrix (MatGeom tap_*; engine modes 1 / 2 / 3): its columns are
+// compact columns.  Lane l owns compact columns col0 + l + 64 j (j < 4), not 4 consecutive ones:
+// the parameter (and the gradient with mode 2) and the Q rows are reached through the column map,
+// 4 bytes at a time, and a live tap comes only every tap_T / tap_L floats — with consecutive
+// columns per lane every wave load would touch 64 different cache lines of x, this way it
+// touches the 64 neighbouring live taps (18 lines for a centre-tap 3x3).  Momentum and e / M are
+// then coalesced 4-byte accesses in the compact slot.  The arithmetic per element is the full
+// tile's.
+template <int RQ, int NT>
+__device__ __forceinline__ void update_wide_tapped(const MatGeom& g, const GPtrs& pt, int col0, int arow0, int lane,
+                                                   const float* P, const float* Q, float q_div, int mode, float lr,
+                                                   float momentum, bool lazy) {
+  const int r = g.r, n = g.n, m = g.m;
+  const int mc = tap_cols(g);
+  const bool step = mode == 1 || mode == 2;
+  const int cb = col0 + lane;  // + 64 j
+  if (cb >= mc) return;
+  bool ok[4];
+  int fc[4];  // the full columns
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    ok[j] = cb + 64 * j < mc;
+    fc[j] = tap_full(g, ok[j] ? cb + 64 * j : cb);
+  }
+  auto ld_c = [&](const float NDP_GLOBAL* base, int a, bool nt) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (a >= n) return v;
+    const float NDP_GLOBAL* q = base + (int64_t)a * mc + cb;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (ok[j]) v[j] = nt ? __builtin_nontemporal_load(q + 64 * j) : q[64 * j];
+    return v;
+  };
+  auto st_c = [&](float NDP_GLOBAL* base, int a, f32x4 v, bool nt) {
+    float NDP_GLOBAL* q = base + (int64_t)a * mc + cb;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (ok[j]) {
+        if (nt) __builtin_nontemporal_store(v[j], q + 64 * j);
+        else q[64 * j] = v[j];
+      }
+  };
+  // the HBM stream first
+  f32x4 Mv[kURowsPerWave], Mm[kURowsPerWave], Xv[kURowsPerWave];
+#pragma unroll
+  for (int i = 0; i < kURowsPerWave; ++i) {
+    const int a = arow0 + i;
+    Mv[i] = lazy ? f32x4{0.f, 0.f, 0.f, 0.f} : ld_c(pt.mread, a, false);
+    Mm[i] = Xv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (step) {
+      Mm[i] = ld_c(pt.mom, a, NT >= 1);
+      if (a < n) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (ok[j]) Xv[i][j] = pt.x[(int64_t)a * m + fc[j]];
+      }
+    }
+  }
+  float qv[4][RQ];
+  const bool q4 = (r & 3) == 0 && (g.q_off & 3) == 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (q4) {
+#pragma unroll
+      for (int c = 0; c < RQ; c += 4) {
+        f32x4 t = (ok[j] && c < r) ? ld4(Q + (int64_t)fc[j] * r + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) qv[j][c + u] = t[u] / q_div;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < RQ; ++c) qv[j][c] = (ok[j] && c < r) ? Q[(int64_t)fc[j] * r + c] / q_div : 0.f;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kURowsPerWave; ++i) {
+    const int a = arow0 + i;
+    if (a >= n) break;  // wave-uniform
+    const float* prow = P + (int64_t)a * r;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < RQ; ++c) {
+      if (c >= r) break;
+      const float pv = prow[c];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = fmaf(pv, qv[j][c], o[j]);
+    }
+    if (!step) {  // mode 3
+      st_c(pt.e, a, Mv[i] - o, false);
+      continue;
+    }
+    f32x4 mm = Mm[i];
+    f32x4 xx = Xv[i];
+    if (!lazy) st_c(pt.e, a, Mv[i] - o, false);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mm[j] = __fadd_rn(__fmul_rn(mm[j], momentum), o[j]);
+    const f32x4 up = o + mm;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xx[j] = fmaf(-lr, up[j], xx[j]);
+    st_c(pt.mom, a, mm, NT >= 2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (ok[j]) {
+        pt.x[(int64_t)a * m + fc[j]] = xx[j];
+        if (mode == 2) pt.g[(int64_t)a * m + fc[j]] = up[j];
+      }
+  }
+}
+
 // p_prev != nullptr (lazy error feedback, modes 1 / 2): e is not written — M is not even read —
 // and the column-block-0 workgroup of each row block keeps its P-hat rows in p_prev for the
 // next P pass.  mode 3: e -= p_hat Qs^T only (the lazy state materialised: checkpoint, API).
 template <int RQ, int NT = 0>
-__global__ __launch_bounds__(256) void psgd_update_wide_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RQ <= 4 ? 5 : RQ <= 8 ? 4 : 5)))
+void psgd_update_wide_kernel(
     const MatGeom* __restrict__ geom, const MatPtrs* __restrict__ ptrs,
     const UItem* __restrict__ items, const float* __restrict__ p_hat,
     const float* __restrict__ q_sum, float q_div, float* __restrict__ q_warm, int mode,
@@ -748,7 +963,16 @@ __global__ __launch_bounds__(256) void psgd_update_wide_kernel(
   const float* P = p_hat + g.p_off;
   const float* Q = q_sum + g.q_off;
 
-  if (q_warm != nullptr && it.row0 == 0 && wave == 0) {
+  const bool tapped = g.tap_T != 0;
+  if (q_warm != nullptr && it.row0 == 0 && tapped) {
+    // the row-0 tiles tile the compact columns, but the warm start keeps EVERY Q row (the dead
+    // ones are zero): each takes an equal share of the matrix's m x r values
+    float* W = q_warm + g.q_off;
+    const int tiles = (tap_cols(g) + kUWideCols - 1) / kUWideCols;
+    const int per = (m * r + tiles - 1) / tiles;
+    const int lo = (it.col0 / kUWideCols) * per, hi = min(m * r, lo + per);
+    for (int idx = lo + tid; idx < hi; idx += 256) W[idx] = Q[idx] / q_div;
+  } else if (q_warm != nullptr && it.row0 == 0 && wave == 0) {
     float* W = q_warm + g.q_off;
     const int cnt = min(kUWideCols, m - it.col0) * r;
     const int64_t base = (int64_t)it.col0 * r;
@@ -762,6 +986,10 @@ __global__ __launch_bounds__(256) void psgd_update_wide_kernel(
 #pragma unroll
     for (int i = 0; i < kURowsPerWave; ++i)
       if (arow0 + i < n) p_prev[g.p_off + (int64_t)(arow0 + i) * r + lane] = P[(int64_t)(arow0 + i) * r + lane];
+  }
+  if (tapped) {
+    if (mode != 0) update_wide_tapped<RQ, NT>(g, pt, it.col0, arow0, lane, P, Q, q_div, mode, lr, momentum, lazy);
+    return;
   }
   const int b = it.col0 + 4 * lane;
   const int nb = max(0, min(4, m - b));  // valid columns of this lane (vec: 0 or 4)

@@ -34,7 +34,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops import gradfinish
+from ..ops import gradfinish, taps
 from ..ops._ext import ext
 from ..ops.conv import DirectConvFn, direct_plan, direct_plan_padded
 from ..ops.gradarena import grad_buffer
@@ -195,6 +195,19 @@ class GemmConv2d(nn.Conv2d):
         self._maps: Dict[Tuple, tuple] = {}
         self.bank: "ToeplitzBank | None" = None  # set by the owning model (one expand launch per pass)
         self.wbank = None  # ops/conv.WinoBank, set by the owning model (one Winograd transform launch per pass)
+        self._tap_sizes: set = set()  # input sizes whose live taps are already in the weight's support
+
+    def _record_taps(self, x):
+        """Widen the weight's live-tap support (ops/taps.py) by this input size: whatever path
+        runs the conv, a tap outside it only ever multiplies zero padding."""
+        if not (self.training and torch.is_grad_enabled() and self.weight.requires_grad):
+            return
+        if self.groups != 1 or self.dilation != (1, 1) or self.padding_mode != "zeros" or isinstance(self.padding, str):
+            return
+        hw = (int(x.shape[2]), int(x.shape[3]))
+        if hw not in self._tap_sizes:
+            taps.record(self.weight, hw[0], hw[1], self.stride, self.padding)
+            self._tap_sizes.add(hw)
 
     def _plan(self, x):
         C, H, W = x.shape[1:]
@@ -226,6 +239,7 @@ class GemmConv2d(nn.Conv2d):
         forward / grad-x split-K slabs go to the neighbouring fused BN instead of a sum
         launch (other paths leave the links empty).  ``branch`` (ops/gradlink.BranchLink):
         grad-x shared with a sibling conv of the same input."""
+        self._record_taps(x)
         if not (self.gemm and x.is_cuda and self.groups == 1 and self.dilation == (1, 1) and self.bias is None
                 and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1]
                 and self.padding_mode == "zeros" and x.dtype == torch.float32):

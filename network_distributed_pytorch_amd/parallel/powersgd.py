@@ -9,15 +9,18 @@ Two front-ends share one native execution plan:
 * :class:`PowerSGDOptimizer` — the reference training loop's whole "Algorithm 2" step
   (EF pack ``g + e``, compression, decompression, error memory, momentum, SGD update;
   ddp_powersgd_guide_cifar10/ddp_init.py:149-178) fused over flat parameter / gradient /
-  error / momentum arenas: 6 kernel launches + 2 collectives per step instead of the
-  reference's ~1.3k eager ops (SURVEY.md §2.6 launch-count evidence).
+  error / momentum arenas: 4 kernel launches + 2 collectives per step (6 launches with
+  ``NDP_FUSION_OFF=psgd_fin`` or above rank 16) instead of the reference's ~1.3k eager ops
+  (SURVEY.md §2.6 launch-count evidence).
 
 Per-step device pipeline (one launch each, all matrices at once):
-  psgd_p  (P = (g+e) Q, e <- g+e)  ->  seg_reduce (split-K sum of P | pack rank-1 grads)
+  psgd_p  (P = (g+e) Q, e <- g+e; split-K sum of P and the rank-1 pack in the same launch)
   -> all_reduce([P | rank-1])      ->  psgd_orth (/N + batched MGS)
-  -> psgd_q (Q = M^T P)            ->  seg_reduce (split-K sum of Q)
+  -> psgd_q (Q = M^T P; split-K sum of Q in the same launch)
   -> all_reduce(Q)                 ->  psgd_update (out = P Q^T/N, e = M - out, momentum,
-                                       x -= lr (out + m), warm-start Q)  + rank1_step
+                                       x -= lr (out + m), warm-start Q, the rank-1 step)
+Without the in-kernel finishes a seg_reduce launch follows psgd_p and psgd_q, and the rank-1
+step is its own launch.
 The P and rank-1 payloads share ONE collective (the reference issues them separately,
 reducer.py:126,132); the byte count per step is unchanged.
 
@@ -37,7 +40,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..ops import SegPlan, capturing, ext, gradfinish, upload, upload_epoch
+from ..ops import SegPlan, capturing, ext, gradfinish, taps, upload, upload_epoch
 from .comm import Communicator, n_bits
 from ..knobs import fusion_on
 
@@ -131,7 +134,7 @@ class _PlanBuffers:
     """Device/host buffers + native tables for one list of matrix shapes."""
 
     def __init__(self, shapes: List[Tuple[int, int]], rank: int, r1_numel: int, device: torch.device,
-                 native: bool = True):
+                 native: bool = True, supports: Optional[List[Tuple[int, int]]] = None):
         self.shapes = shapes
         self.rank = rank
         self.device = device
@@ -146,22 +149,15 @@ class _PlanBuffers:
         self.q_memory = torch.zeros(self.q_total, **f32)   # all-reduce payload for Q
         self.q_warm = torch.zeros(self.q_total, **f32)     # averaged Q = next step's query
         self.native = native and device.type == "cuda"
+        # dead-tap compaction (ops/taps.py): (T, mask) of every matrix whose error memory and
+        # momentum the plan keeps as [n, live columns], else None; compact_cols: their row length
+        self.layout: List[Optional[Tuple[int, int]]] = [None] * len(shapes)
+        self.compact_cols: List[int] = [m for _, m in shapes]
         if self.native:
             X = ext()
-            d = X.build_plan([(int(n), int(m)) for n, m in shapes], int(rank))
-            assert d["p_total"] == self.p_total and d["q_total"] == self.q_total
-            self._geom_host = d["geom"]
-            self.p_items = d["p_items"].to(device)
-            self.q_items = d["q_items"].to(device)
-            self.u_items = d["u_items"].to(device)
+            d = self._build_tables(supports)
             self.p_part = torch.zeros(max(1, d["pp_total"]), **f32)
             self.q_part = torch.zeros(max(1, d["qp_total"]), **f32)
-            self.pp_offs, self.qp_offs = d["pp_offs"], d["qp_offs"]
-            self.p_chunks, self.q_chunks = d["p_chunks"], d["q_chunks"]
-            self.counts = {k: d[k] for k in ("n_p_items", "n_q_items", "n_u_items", "n_orth_items", "pp_total",
-                                             "qp_total")}
-            self.item_start = {k: d[k + "_item_start"] for k in ("p", "q", "u", "orth")}
-            self.orth_items = d["orth_items"].to(device)
             self.orth_scratch = torch.zeros(max(1, 2 * d["n_orth_items"] * X.MAX_RANK), **f32)
             # 64-bit MGS barrier counters (never wrap) + the error word (low half of the last)
             self.orth_ctr = torch.zeros(len(shapes) + 1, dtype=torch.int64, device=device)
@@ -172,11 +168,50 @@ class _PlanBuffers:
             self.q_seg = SegPlan(self.q_seg_specs(0, len(shapes)), device)
             # in-kernel split-K finish of P / Q (csrc/powersgd.hip PFin / QFin): monotonic arrival
             # counters, one per P row block / Q column block (zeroed once, never reset)
-            self.p_cols = int(d["p_cols"])  # columns per P item
             self.p_ctr = torch.zeros(max(1, d["n_p_blocks"]), dtype=torch.int64, device=device)
-            self.q_ctr = torch.zeros(max(1, d["n_q_blocks"]), dtype=torch.int64, device=device)
             self._q_seg_fused = SegPlan(self.q_seg_specs(0, len(shapes), fused=True), device)
             self.fused = self.max_rank <= _LAZY_MAX_RANK and fusion_on("psgd_fin")
+
+    def _build_tables(self, supports: Optional[List[Tuple[int, int]]]):
+        """The native plan and its work-item tables for ``supports`` ((T, mask) per matrix, T = 0:
+        none).  Only the Q / update items, the Q arrival counters and the geometry depend on them."""
+        X = ext()
+        device = self.device
+        d = X.build_plan([(int(n), int(m)) for n, m in self.shapes], int(self.rank),
+                         [(int(t), int(k)) for t, k in supports] if supports else [])
+        assert d["p_total"] == self.p_total and d["q_total"] == self.q_total
+        self._geom_host = d["geom"]
+        self.p_items = d["p_items"].to(device)
+        self.q_items = d["q_items"].to(device)
+        self.u_items = d["u_items"].to(device)
+        self.pp_offs, self.qp_offs = d["pp_offs"], d["qp_offs"]
+        self.p_chunks, self.q_chunks = d["p_chunks"], d["q_chunks"]
+        self.counts = {k: d[k] for k in ("n_p_items", "n_q_items", "n_u_items", "n_orth_items", "pp_total",
+                                         "qp_total")}
+        self.item_start = {k: d[k + "_item_start"] for k in ("p", "q", "u", "orth")}
+        self.orth_items = d["orth_items"].to(device)
+        self.p_cols = int(d["p_cols"])  # columns per P item
+        self.q_ctr = torch.zeros(max(1, d["n_q_blocks"]), dtype=torch.int64, device=device)
+        self.layout = [tuple(supports[i]) if t else None for i, t in enumerate(d["tap_T"])]
+        self.compact_cols = [int(c) for c in d["compact_cols"]]
+        return d
+
+    def replan(self, supports: Optional[List[Tuple[int, int]]]):
+        """Rebuild the tables for new supports (never while capturing: the tables are new tensors).
+        The Q kernel never writes a dead Q row, so the Q sums and partials start from zero."""
+        assert self.native and not capturing()
+        self._build_tables(supports)
+        self.q_memory.zero_()
+        self.q_part.zero_()
+        self._bind_key = None
+
+    def vec_flag(self, i: int, row: Sequence[int]) -> int:
+        """MatGeom.vec of matrix ``i`` bound to the MatPtrs ``row``: float4 eligibility; for a
+        compacted matrix bit 0 covers the full-width arrays (grad, x) and bit 1 the compact ones."""
+        if self.layout[i] is None:
+            return _vec_ok(self.shapes[i][1], row)
+        return (_vec_ok(self.shapes[i][1], (row[0], row[6], row[7]))
+                | _vec_ok(self.compact_cols[i], (row[1], row[2], row[5])) << 1)
 
     # -- per-matrix-range views (a PowerSGD overlap group = matrices [lo, hi)) ----------------
     def p_seg_specs(self, lo: int = 0, hi: Optional[int] = None):
@@ -216,7 +251,7 @@ class _PlanBuffers:
         if not self.fused:
             if self.shapes:
                 X.psgd_p(self.geom, self.ptrs, items, self.q_warm, self.p_part, fuse_ef, self.max_rank, p_prev,
-                         p_cols=self.p_cols)
+                         p_cols=self.p_cols, err=self.orth_ctr)
             if p_seg is not None:
                 p_seg.run()
             return
@@ -225,7 +260,7 @@ class _PlanBuffers:
             return
         kw = dict(seg_entries=t[0], seg_prefix=t[1], seg_n=t[2], seg_blocks=t[3]) if t is not None else {}
         X.psgd_p(self.geom, self.ptrs, items, self.q_warm, self.p_part, fuse_ef, self.max_rank, p_prev,
-                 p_out=self.comm_buf, p_ctr=self.p_ctr, p_cols=self.p_cols, **kw)
+                 p_out=self.comm_buf, p_ctr=self.p_ctr, p_cols=self.p_cols, err=self.orth_ctr, **kw)
 
     def run_q(self, items: torch.Tensor, q_seg: SegPlan, q_seg_fused: Optional[SegPlan] = None):
         """Q = M^T P-hat into q_memory: split-K sums in-kernel when ``fused`` (+ ``q_seg_fused`` for
@@ -245,13 +280,19 @@ class _PlanBuffers:
                         self.max_rank, self.orth_scratch, self.orth_ctr, self.counts["n_orth_items"], max_spins)
 
     def orth_error(self) -> int:
-        """Non-zero if a cross-workgroup barrier of the MGS kernel ever timed out (host sync)."""
+        """The sticky device error word (host sync): bit 0 = a cross-workgroup barrier of the MGS
+        kernel timed out, bit 1 = a gradient was nonzero in a conv tap recorded as dead."""
         return int(self.orth_ctr[-1].item())
 
     def check_orth(self):
-        if self.native and self.orth_error():
+        err = self.orth_error() if self.native else 0
+        if err & 1:
             raise RuntimeError("PowerSGD orthogonalisation: a cross-workgroup barrier timed out; P-hat "
                                "was poisoned with NaN (co-residency violated)")
+        if err & 2:
+            raise RuntimeError("PowerSGD dead-tap compaction: a gradient was nonzero in a conv tap recorded as "
+                               "never seeing a real pixel; its error memory and momentum were dropped "
+                               "(NDP_FUSION_OFF=dead_taps keeps the full layout)")
 
     def bind(self, rows: List[List[int]], vec: List[int]) -> bool:
         """Point the grouped kernels at new tensors; returns True if the tables changed."""
@@ -344,7 +385,7 @@ class PowerSGDReducer(Reducer):
             self._reduce_torch(high, rank1, N)
         return n_bits(B.p_memory) + n_bits(B.rank1_buf) + n_bits(B.q_memory)
 
-    # -- device path: 6 launches + 2 collectives ------------------------------------------
+    # -- device path: 4 launches (6 without the in-kernel split-K finishes) + 2 collectives --
     def _bind(self, high, rank1):
         B = self._buf
         key = tuple(x.data_ptr() for trip in high + rank1 for x in trip)
@@ -519,7 +560,7 @@ class PowerSGDOptimizer:
         f32 = dict(dtype=torch.float32, device=self.device)
         self.x = torch.zeros(o, **f32)
         self._e = torch.zeros(o, **f32)
-        self.m = torch.zeros(o, **f32)
+        self._m = torch.zeros(o, **f32)
         self.offsets = offs
         with torch.no_grad():
             for p in self.params:
@@ -536,6 +577,10 @@ class PowerSGDOptimizer:
         self.r1_upd = torch.zeros(self.r1_numel if write_grad else 0, **f32)
         self.buf = _PlanBuffers(shapes, self.rank, self.r1_numel, self.device, native=native is not False)
         self.native = self.buf.native
+        # dead-tap compaction (ops/taps.py; NDP_FUSION_OFF=dead_taps): the support version the plan
+        # was last compared with (None: compare at the next step)
+        self.dead_taps = self.native and bool(shapes) and fusion_on("dead_taps")
+        self._taps_seen: Optional[int] = None
         # needs the warm-start Q of the next P pass to BE the update's Qs (reuse_query)
         self.lazy_ef = (self.native and bool(shapes) and self.buf.max_rank <= _LAZY_MAX_RANK and reuse_query
                         and fusion_on("lazy_ef"))
@@ -616,10 +661,10 @@ class PowerSGDOptimizer:
         for p, gr, (n, m) in zip(g.params, grads, B.shapes[g.lo:g.hi]):
             assert gr.is_contiguous() and gr.dtype == torch.float32, "PowerSGD needs dense fp32 grads"
             s = self.offsets[id(p)]
-            e, mo, x = (t[s:].data_ptr() for t in (self._e, self.m, self.x))
+            e, mo, x = (t[s:].data_ptr() for t in (self._e, self._m, self.x))
             row = [gr.data_ptr(), e, e, 0, 0, mo, x, gr.data_ptr()]
             rows.append(row)
-            vec.append(_vec_ok(m, row))
+            vec.append(B.vec_flag(g.lo + len(vec), row))
         B.bind_range(g.lo, rows, vec)
         g.p_seg.set(B.p_seg_specs(g.lo, g.hi))
         g.key = key
@@ -627,6 +672,8 @@ class PowerSGDOptimizer:
     @torch.no_grad()
     def _launch_group(self, g: _Group):
         gradfinish.flush()  # deferred conv grad-W sums / folds of the layers done so far
+        if g.idx == 0:  # the step's first reducer launch (groups launch in order)
+            self._sync_supports()
         B = self.buf
         X = ext()
         N = self.comm.world_size
@@ -684,7 +731,7 @@ class PowerSGDOptimizer:
             def rank1():
                 self._r1_pack.run()
                 self.comm.all_reduce(B.rank1_buf)                           # reducer.py:132
-                ext().rank1_step(B.rank1_buf, float(N), self.m[r1], self.x[r1],
+                ext().rank1_step(B.rank1_buf, float(N), self._m[r1], self.x[r1],
                                  self.r1_upd if self.write_grad else None, lr, mom)
                 if self.write_grad:
                     self._r1_out.run()
@@ -730,10 +777,10 @@ class PowerSGDOptimizer:
         for p, (n, m) in zip(self.high, B.shapes):
             s = self.offsets[id(p)]
             g = gmap[id(p)].data_ptr()
-            e, mo, x = (t[s:].data_ptr() for t in (self._e, self.m, self.x))
+            e, mo, x = (t[s:].data_ptr() for t in (self._e, self._m, self.x))
             row = [g, e, e, 0, 0, mo, x, g]
             rows.append(row)
-            vec.append(_vec_ok(m, row))
+            vec.append(B.vec_flag(len(vec), row))
         B.bind(rows, vec)
         pack, outs = [], []
         for p in self.rank1:
@@ -809,6 +856,7 @@ class PowerSGDOptimizer:
         self._grads()
         if not self.native:
             return
+        self._sync_supports()
         self._bind()
         B.run_p(B.p_items, True, self.p_prev if self.lazy_ef else None,   # P (+ split-K sum + rank-1 pack)
                 seg=self._r1_pack, p_seg=self._p_seg)
@@ -841,7 +889,7 @@ class PowerSGDOptimizer:
                 X.psgd_update(B.geom, B.ptrs, B.u_items, B.comm_buf, B.q_memory, float(N), B.q_warm,
                               2 if self.write_grad else 1, self.lr, self.momentum, B.max_rank,
                               self.p_prev if self.lazy_ef else None, r1_buf=B.rank1_buf, r1_div=float(N),
-                              r1_mom=self.m[r1], r1_x=self.x[r1], r1_g=self.r1_upd if self.write_grad else None)
+                              r1_mom=self._m[r1], r1_x=self.x[r1], r1_g=self.r1_upd if self.write_grad else None)
                 if self.write_grad:
                     self._r1_out.run()
             elif B.shapes:
@@ -849,7 +897,7 @@ class PowerSGDOptimizer:
                               2 if self.write_grad else 1, self.lr, self.momentum, B.max_rank,
                               self.p_prev if self.lazy_ef else None)
             if self.r1_numel and not (B.shapes and B.fused):
-                X.rank1_step(B.rank1_buf, float(N), self.m[r1], self.x[r1],
+                X.rank1_step(B.rank1_buf, float(N), self._m[r1], self.x[r1],
                              self.r1_upd if self.write_grad else None, self.lr, self.momentum)
                 if self.write_grad:
                     self._r1_out.run()
@@ -921,7 +969,7 @@ class PowerSGDOptimizer:
         for i, (p, M) in enumerate(zip(self.high, Ms)):
             out = torch.matmul(B.p_view(i), B.q_view(i).t()).view(-1)
             self._view(self._e, p).copy_(M.reshape(-1) - out)
-            mom = self._view(self.m, p)
+            mom = self._view(self._m, p)
             mom.mul_(lam).add_(out)
             upd = out + mom
             self._view(self.x, p).add_(upd, alpha=-lr)
@@ -930,22 +978,119 @@ class PowerSGDOptimizer:
         if self.r1_numel:
             r1 = slice(self.r1_start, self.arena_numel)
             out = B.rank1_buf / N
-            self.m[r1].mul_(lam).add_(out)
-            upd = out + self.m[r1]
+            self._m[r1].mul_(lam).add_(out)
+            upd = out + self._m[r1]
             self.x[r1].add_(upd, alpha=-lr)
             if self.write_grad:
                 for p in self.rank1:
                     s = self.offsets[id(p)] - self.r1_start
                     gmap[id(p)].copy_(upd[s: s + p.numel()].view_as(p))
 
+    # -- dead-tap compaction -----------------------------------------------------------------------
+    def _wanted_supports(self) -> List[Tuple[int, int]]:
+        """(T, mask) of every high-rank parameter whose recorded support has dead taps, else (0, 0)."""
+        out = []
+        for p in self.high:
+            s = taps.support_of(p) if p.dim() == 4 else None
+            T = p.shape[2] * p.shape[3] if p.dim() == 4 else 0
+            ok = (s is not None and s[0] == T and 2 <= T <= taps.MAX_PERIOD
+                  and 0 < len(taps.tap_list(T, s[1])) < T)
+            out.append((int(s[0]), int(s[1])) if ok else (0, 0))
+        return out
+
+    def _slot(self, arena: torch.Tensor, i: int, layout) -> torch.Tensor:
+        """Matrix ``i``'s slot of an arena as [n, columns] in ``layout`` (None: full)."""
+        n, m = self.buf.shapes[i]
+        cols = m if layout is None else taps.compact_cols(m, *layout)
+        s = self.offsets[id(self.high[i])]
+        return arena[s: s + n * cols].view(n, cols)
+
+    def _sync_supports(self):
+        """Before a step's first reducer launch: re-plan if some conv's live-tap support changed."""
+        if not self.dead_taps or self._taps_seen == taps.version():
+            return
+        seen = taps.version()
+        want = self._wanted_supports()
+        if [w if w[0] else None for w in want] != self.buf.layout:
+            if capturing():
+                raise RuntimeError("PowerSGD: a conv's live-tap support changed while capturing a graph; run one "
+                                   "eager step on every input size first")
+            self._replan(want)
+        self._taps_seen = seen
+
+    @torch.no_grad()
+    def _replan(self, want: List[Tuple[int, int]]):
+        """Convert the error-memory and momentum slots to the layout of ``want`` and rebuild the
+        plan.  A matrix with a nonzero dead entry (a checkpoint trained at another resolution)
+        stays full."""
+        B = self.buf
+        self.materialize_error()
+        old = list(B.layout)
+        want = list(want)
+        for i, w in enumerate(want):
+            if w[0] and old[i] != w:
+                for arena in (self._e, self._m):
+                    full = self._slot(arena, i, old[i])
+                    if old[i] is not None:
+                        full = taps.expand(full, B.shapes[i][1], *old[i])
+                    if not taps.dead_all_zero(full, *w):
+                        want[i] = (0, 0)
+                        break
+        new = [w if w[0] else None for w in want]
+        for i in range(len(old)):  # compact -> full, in place
+            if old[i] is not None and old[i] != new[i]:
+                for arena in (self._e, self._m):
+                    self._slot(arena, i, None).copy_(taps.expand(self._slot(arena, i, old[i]), B.shapes[i][1], *old[i]))
+        B.replan(want)
+        for i, lay in enumerate(B.layout):  # full -> compact (what the plan accepted), in place
+            if lay is not None and lay != old[i]:
+                for arena in (self._e, self._m):
+                    full = self._slot(arena, i, None)
+                    c = taps.compress(full, *lay).contiguous()
+                    full.zero_()
+                    self._slot(arena, i, lay).copy_(c)
+        self._grad_key = None
+        for g in self.groups:
+            g.key = None
+
+    def _full_arena(self, arena: torch.Tensor) -> torch.Tensor:
+        """``arena`` in the full reference layout (the arena itself when nothing is compacted)."""
+        B = self.buf
+        if all(lay is None for lay in B.layout):
+            return arena
+        out = arena.clone()
+        for i, lay in enumerate(B.layout):
+            if lay is not None:
+                s = self.offsets[id(self.high[i])]
+                n, m = B.shapes[i]
+                out[s: s + n * m].view(n, m).copy_(taps.expand(self._slot(arena, i, lay), m, *lay))
+        return out
+
+    def _load_arena(self, arena: torch.Tensor, full: torch.Tensor):
+        """Copy a full-layout arena image into ``arena`` in the plan's layout."""
+        B = self.buf
+        arena.copy_(full)
+        for i, lay in enumerate(B.layout):
+            if lay is not None:
+                slot = self._slot(arena, i, None)
+                c = taps.compress(slot, *lay).contiguous()
+                slot.zero_()
+                self._slot(arena, i, lay).copy_(c)
+
+    @property
+    def m(self) -> torch.Tensor:
+        """The momentum arena in the full reference layout (a copy when a matrix is compacted)."""
+        return self._full_arena(self._m)
+
     # -- lazy error feedback -------------------------------------------------------------------
     @property
     def e(self) -> torch.Tensor:
         """The error-feedback memory (reducer.py ``memories``), materialised: with lazy error
         feedback the arena holds ``M`` and the correction ``- P_prev Qs^T`` is applied here by
-        the update kernel's own arithmetic (mode 3), exactly as the next P pass would."""
+        the update kernel's own arithmetic (mode 3), exactly as the next P pass would.  Full
+        reference layout (a copy when a matrix is dead-tap compacted)."""
         self.materialize_error()
-        return self._e
+        return self._full_arena(self._e)
 
     @torch.no_grad()
     def materialize_error(self):
@@ -963,17 +1108,18 @@ class PowerSGDOptimizer:
             self._ensure_queries()
 
     def snapshot(self):
-        return {"x": self.x.clone(), "e": self._e.clone(), "p_prev": self.p_prev.clone(),
+        # e / m in the full layout: the warm-up steps between snapshot and restore may re-plan
+        return {"x": self.x.clone(), "e": self._full_arena(self._e).clone(), "p_prev": self.p_prev.clone(),
                 "lazy_pending": self._lazy_pending, "m": self.m.clone(), "q": self.buf.q_warm.clone(),
                 "step_count": self.step_count, "bits": self.bits_communicated, "q_ready": self._q_ready,
                 "rng": self.rng.get_state()}
 
     def restore(self, snap):
         self.x.copy_(snap["x"])
-        self._e.copy_(snap["e"])
+        self._load_arena(self._e, snap["e"])
         self.p_prev.copy_(snap["p_prev"])
         self._lazy_pending = snap["lazy_pending"]
-        self.m.copy_(snap["m"])
+        self._load_arena(self._m, snap["m"])
         self.buf.q_warm.copy_(snap["q"])
         self.step_count = snap["step_count"]
         self.bits_communicated = snap["bits"]
@@ -999,10 +1145,14 @@ class PowerSGDOptimizer:
         assert sd["rank"] == self.rank, "checkpoint compression rank differs"
         self.step_count = int(sd["step_count"])
         self.bits_communicated = int(sd["bits_communicated"])
+        if any(lay is not None for lay in self.buf.layout):
+            # back to the full layout; the next step compacts again what the loaded state allows
+            self._replan([(0, 0)] * len(self.high))
+        self._taps_seen = None
         self._e.copy_(sd["error"])
         self.p_prev.zero_()  # e is the true error memory: no pending correction
         self._lazy_pending = False
-        self.m.copy_(sd["momentum"])
+        self._m.copy_(sd["momentum"])
         self.buf.q_warm.copy_(sd["q_warm"])
         self._q_ready = bool(sd.get("q_ready", self.step_count > 0)) and self.reuse_query
         self.rng.set_state(_rng_state_from_dict(sd["rng_state"]))
