@@ -833,24 +833,18 @@ void toeplitz_fold(torch::Tensor dwb, torch::Tensor dw, const std::vector<int64_
   check_launch("launch_toeplitz_fold");
 }
 
-// (class, fwd images per workgroup, grad-W images per slice, grad-x direct) or class -1
+// the plan the Python side asks about (conv_plan, conv_stats_slices, conv_dgrad_stats_slices,
+// conv_wino): the defaults (class -1) where the forward / grad-x kernels cannot tile the batch
+ndp::ConvPlan conv_query(const std::vector<int64_t>& geom, int64_t B) {
+  const ndp::ConvPlan p = ndp::conv_make_plan(conv_geom(geom), (int)B);
+  return (p.cls < 0 || B <= 0 || B % p.fwd_imgs) ? ndp::ConvPlan{} : p;
+}
+
 // (class, fwd images per workgroup, grad-W images per slice, grad-x direct, fwd split-K,
 // grad-x split-K) for batch B, or class -1
 py::tuple conv_plan(const std::vector<int64_t>& geom, int64_t B) {
-  const ndp::ConvGeom g = conv_geom(geom);
-  const int cls = ndp::conv_direct_class(g);
-  if (cls < 0 || B <= 0 || B % ndp::conv_fwd_imgs(cls)) return py::make_tuple(-1, 0, 0, false, 1, 1);
-  return py::make_tuple(cls, ndp::conv_fwd_imgs(cls), ndp::conv_wgrad_imgs(cls, g, (int)B),
-                        ndp::conv_dgrad_direct(cls), ndp::conv_ksplit(cls, g, (int)B, false),
-                        ndp::conv_ksplit(cls, g, (int)B, true));
-}
-
-// batch-tile partials of the BatchNorm statistics the forward epilogue can emit (0 = none)
-int64_t conv_stats_slices(const std::vector<int64_t>& geom, int64_t B) {
-  const ndp::ConvGeom g = conv_geom(geom);
-  const int cls = ndp::conv_direct_class(g);
-  if (cls < 0 || B <= 0 || B % ndp::conv_fwd_imgs(cls)) return 0;
-  return ndp::conv_fwd_stats_slices(cls, g, (int)B);
+  const ndp::ConvPlan p = conv_query(geom, B);
+  return py::make_tuple(p.cls, p.fwd_imgs, p.wgrad_imgs, p.dgrad_direct, p.fwd_ksplit, p.dgrad_ksplit);
 }
 
 float* conv_part(const c10::optional<torch::Tensor>& part, int ks, int64_t slab, const char* who) {
@@ -867,9 +861,10 @@ void conv_check(const torch::Tensor& t, const char* n, int64_t b, int64_t c, int
               ": shape mismatch with the conv geometry");
 }
 
-int conv_batch(const torch::Tensor& t, const ndp::ConvGeom& g, int imgs) {
+// the batch of a launch: whole tiles / slices of `imgs` images (the plan's fwd_imgs / wgrad_imgs)
+int conv_batch(const torch::Tensor& t, const ndp::ConvPlan& p, int imgs) {
   const int B = (int)t.size(0);
-  TORCH_CHECK(ndp::conv_direct_class(g) >= 0, "conv: no direct kernel for this geometry");
+  TORCH_CHECK(p.cls >= 0, "conv: no direct kernel for this geometry");
   TORCH_CHECK(imgs > 0 && B % imgs == 0, "conv: batch must be a multiple of ", imgs);
   return B;
 }
@@ -928,16 +923,15 @@ int64_t conv_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor y, const std::v
                  c10::optional<torch::Tensor> part, bool defer, c10::optional<torch::Tensor> stats,
                  c10::optional<torch::Tensor> wino_u, bool pair) {
   const ndp::ConvGeom g = conv_geom(geom);
-  const int cls = ndp::conv_direct_class(g);
-  const int B = conv_batch(x, g, ndp::conv_fwd_imgs(cls));
+  const ndp::ConvPlan p = ndp::conv_make_plan(g, (int)x.size(0));
+  const int B = conv_batch(x, p, p.fwd_imgs);
   conv_check(x, "x", B, g.C, g.H, g.W);
   conv_check(w, "w", g.Co, g.C, g.KH, g.KW);
   conv_check(y, "y", B, g.Co, g.OH, g.OW);
-  const int ks = ndp::conv_ksplit(cls, g, B, false);
-  float* pp = conv_part(part, ks, y.numel(), "conv_fwd");
+  float* pp = conv_part(part, p.fwd_ksplit, y.numel(), "conv_fwd");
   double* st = nullptr;
   if (stats.has_value()) {  // BatchNorm partial sums from the epilogue: [Co][S][2]
-    const int S = ndp::conv_fwd_stats_slices(cls, g, B);
+    const int S = p.fwd_stats_slices;
     check_dev(*stats, "stats");
     TORCH_CHECK(S > 0, "conv_fwd: no statistics epilogue for this geometry / batch (conv_stats_slices)");
     TORCH_CHECK(stats->scalar_type() == torch::kFloat64 && stats->is_contiguous() &&
@@ -945,8 +939,8 @@ int64_t conv_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor y, const std::v
                 "conv_fwd: stats must hold Co * S * 2 doubles");
     st = stats->data_ptr<double>();
   }
-  torch::Tensor wu = wino_u_for(wino_u, w, g, ndp::conv_wino(cls, g, B, false));
-  const int left = ndp::launch_conv_fwd(x.data_ptr<float>(), w.data_ptr<float>(), y.data_ptr<float>(), B, g, pp,
+  torch::Tensor wu = wino_u_for(wino_u, w, g, p.fwd_wino);
+  const int left = ndp::launch_conv_fwd(x.data_ptr<float>(), w.data_ptr<float>(), y.data_ptr<float>(), B, g, p, pp,
                                         cur_stream(), defer, st, wu.defined() ? wu.data_ptr<float>() : nullptr,
                                         pair && x.is_contiguous());
   check_launch("launch_conv_fwd");
@@ -959,17 +953,13 @@ int64_t conv_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, const st
                    c10::optional<torch::Tensor> bn_y, c10::optional<torch::Tensor> bn_mean,
                    c10::optional<torch::Tensor> bn_invstd, c10::optional<torch::Tensor> wino_u) {
   const ndp::ConvGeom g = conv_geom(geom);
-  const int cls = ndp::conv_direct_class(g);
-  TORCH_CHECK(cls >= 0 && ndp::conv_dgrad_direct(cls), "conv_dgrad: no direct grad-x kernel for this geometry");
-  const int B = conv_batch(dy, g, ndp::conv_fwd_imgs(cls));
+  const ndp::ConvPlan p = ndp::conv_make_plan(g, (int)dy.size(0));
+  TORCH_CHECK(p.dgrad_direct, "conv_dgrad: no direct grad-x kernel for this geometry");
+  const int B = conv_batch(dy, p, p.fwd_imgs);
   conv_check(dy, "dy", B, g.Co, g.OH, g.OW);
   conv_check(w, "w", g.Co, g.C, g.KH, g.KW);
   conv_check(dx, "dx", B, g.C, g.H, g.W);
-  const int ks = ndp::conv_ksplit(cls, g, B, true);
-  // partial slabs are compact [B][C][OH*OW]-pixel tiles of the transposed product (for the
-  // stride-2 1x1 class the 4x4 map, before the even-pixel scatter)
-  const int64_t slab = (int64_t)B * g.C * ((cls == 4 || cls == 5) ? g.OH * g.OW : g.H * g.W);
-  float* pp = conv_part(part, ks, slab, "conv_dgrad");
+  float* pp = conv_part(part, p.dgrad_ksplit, p.dgrad_slab, "conv_dgrad");
   const float* ap = nullptr;
   if (addend.has_value()) {
     conv_check(*addend, "addend", B, g.C, g.H, g.W);
@@ -978,7 +968,7 @@ int64_t conv_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, const st
   }
   ndp::ConvBnStats bst{nullptr, nullptr, nullptr, nullptr, nullptr};
   if (stats.has_value()) {  // backward-mode BN partial sums of dx: [C][S][2]
-    const int S = ndp::conv_dgrad_stats_slices(cls, g, B);
+    const int S = p.dgrad_stats_slices;
     TORCH_CHECK(S > 0, "conv_dgrad: no statistics epilogue for this geometry / batch (conv_dgrad_stats_slices)");
     check_dev(*stats, "stats");
     TORCH_CHECK(stats->scalar_type() == torch::kFloat64 && stats->is_contiguous() &&
@@ -992,9 +982,9 @@ int64_t conv_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, const st
     bst = ndp::ConvBnStats{stats->data_ptr<double>(), bn_x->data_ptr<float>(), bn_y->data_ptr<float>(),
                            bn_mean->data_ptr<float>(), bn_invstd->data_ptr<float>()};
   }
-  torch::Tensor wu = wino_u_for(wino_u, w, g, ndp::conv_wino(cls, g, B, true));
-  const int left = ndp::launch_conv_dgrad(dy.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), B, g, pp,
-                                          cur_stream(), ap, defer && cls != 4 && cls != 5, bst.out ? &bst : nullptr,
+  torch::Tensor wu = wino_u_for(wino_u, w, g, p.dgrad_wino);
+  const int left = ndp::launch_conv_dgrad(dy.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), B, g, p, pp,
+                                          cur_stream(), ap, defer && p.dgrad_defer_ok, bst.out ? &bst : nullptr,
                                           wu.defined() ? wu.data_ptr<float>() : nullptr);
   check_launch("launch_conv_dgrad");
   return left;
@@ -1004,10 +994,9 @@ int64_t conv_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, const st
 void conv_wgrad(torch::Tensor x, torch::Tensor dy, torch::Tensor part, c10::optional<torch::Tensor> dw_opt,
                 const std::vector<int64_t>& geom, bool pair) {
   const ndp::ConvGeom g = conv_geom(geom);
-  const int cls = ndp::conv_direct_class(g);
-  TORCH_CHECK(cls >= 0, "conv_wgrad: no direct kernel for this geometry");
-  const int imgs = ndp::conv_wgrad_imgs(cls, g, (int)x.size(0));
-  const int B = conv_batch(x, g, imgs);
+  const ndp::ConvPlan p = ndp::conv_make_plan(g, (int)x.size(0));
+  TORCH_CHECK(p.cls >= 0, "conv_wgrad: no direct kernel for this geometry");
+  const int B = conv_batch(x, p, p.wgrad_imgs);
   conv_check(x, "x", B, g.C, g.H, g.W);
   conv_check(dy, "dy", B, g.Co, g.OH, g.OW);
   float* dwp = nullptr;
@@ -1016,8 +1005,8 @@ void conv_wgrad(torch::Tensor x, torch::Tensor dy, torch::Tensor part, c10::opti
     dwp = dw_opt->data_ptr<float>();
   }
   check_f32(part, "part");
-  TORCH_CHECK(part.numel() >= (int64_t)(B / imgs) * g.Co * g.C * g.KH * g.KW, "conv_wgrad: partial scratch too small");
-  ndp::launch_conv_wgrad(x.data_ptr<float>(), dy.data_ptr<float>(), part.data_ptr<float>(), dwp, B, g, cur_stream(),
+  TORCH_CHECK(part.numel() >= (int64_t)(B / p.wgrad_imgs) * g.Co * g.C * g.KH * g.KW, "conv_wgrad: partial scratch too small");
+  ndp::launch_conv_wgrad(x.data_ptr<float>(), dy.data_ptr<float>(), part.data_ptr<float>(), dwp, B, g, p, cur_stream(),
                          pair && dy.is_contiguous() && x.is_contiguous());
   check_launch("launch_conv_wgrad");
 }
@@ -1537,20 +1526,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wino_weights", &wino_weights);
   m.def("wino_weights_many", &wino_weights_many);
   m.def("conv_wino", [](const std::vector<int64_t>& geom, int64_t B, bool dgrad) {
-    const ndp::ConvGeom g = conv_geom(geom);
-    const int cls = ndp::conv_direct_class(g);
-    return cls >= 0 && B > 0 && B % ndp::conv_fwd_imgs(cls) == 0 && ndp::conv_wino(cls, g, (int)B, dgrad);
+    const ndp::ConvPlan p = conv_query(geom, B);
+    return dgrad ? p.dgrad_wino : p.fwd_wino;
   });
-  m.def("conv_stats_slices", &conv_stats_slices, py::arg("geom"), py::arg("batch"));
+  // batch-tile partials of the BatchNorm statistics the forward / grad-x epilogue can emit (0 = none)
+  m.def("conv_stats_slices", [](const std::vector<int64_t>& geom, int64_t B) -> int64_t {
+    return conv_query(geom, B).fwd_stats_slices;
+  }, py::arg("geom"), py::arg("batch"));
   m.def("conv_dgrad", &conv_dgrad, py::arg("dy"), py::arg("w"), py::arg("dx"), py::arg("geom"),
         py::arg("part") = py::none(), py::arg("addend") = py::none(), py::arg("defer") = false,
         py::arg("stats") = py::none(), py::arg("bn_x") = py::none(), py::arg("bn_y") = py::none(),
         py::arg("bn_mean") = py::none(), py::arg("bn_invstd") = py::none(), py::arg("wino_u") = py::none());
   m.def("conv_dgrad_stats_slices", [](const std::vector<int64_t>& geom, int64_t B) -> int64_t {
-    const ndp::ConvGeom g = conv_geom(geom);
-    const int cls = ndp::conv_direct_class(g);
-    if (cls < 0 || B <= 0 || B % ndp::conv_fwd_imgs(cls)) return 0;
-    return ndp::conv_dgrad_stats_slices(cls, g, (int)B);
+    return conv_query(geom, B).dgrad_stats_slices;
   }, py::arg("geom"), py::arg("batch"));
   m.def("conv_wgrad", &conv_wgrad, py::arg("x"), py::arg("dy"), py::arg("part"), py::arg("dw"), py::arg("geom"),
         py::arg("pair") = false);

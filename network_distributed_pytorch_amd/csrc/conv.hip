@@ -11,7 +11,10 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "ndp_kernels.h"
 #include "wino_dpp.h"
@@ -312,7 +315,6 @@ void launch_toeplitz_fold(const float* dwb, float* dw, const ConvGeom& g, hipStr
   launch_toeplitz_fold_many(b, s);
 }
 
-
 // =====================================================================================
 // Direct (implicit-GEMM) convolutions on v_mfma_f32_32x32x2_f32 — exact f32, NCHW.
 //
@@ -356,9 +358,21 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
 // PSPLIT (one image per tile only): the tile covers P / PSPLIT output rows of its image
 // (blockIdx.x = image * PSPLIT + row block); the whole image is still staged in LDS.  The stem at
 // small per-GPU batches: one 16x16-output image per workgroup left 3/4 of the CUs idle at batch 64.
-template <int R, int S, int ST, int PD, int H, int W, int CK, int BM, int IMGS, int WM, int NBUF, int KB, bool TRANSW,
-          int PSPLIT = 1>
-struct ConvFwdCfg {
+// One forward / grad-x kernel configuration as a type: the parameters of conv_fwd_body (described below) and
+// the LDS geometry they imply.  The shape classes (further down) name each one once; all else reads it here.
+template <int R_, int S_, int ST_, int PD_, int H_, int W_, int CK_, int BM_, int IMGS_, int WM_, int NBUF_, int KB_,
+          bool TRANSW_, bool VEC_, int UPS_ = 1, int SCH_ = 0, int IUPS_ = 1, int PSPLIT_ = 1>
+struct FwdTile {
+  static constexpr int R = R_, S = S_, ST = ST_, PD = PD_, H = H_, W = W_, CK = CK_, BM = BM_, IMGS = IMGS_, WM = WM_,
+                       NBUF = NBUF_, KB = KB_, UPS = UPS_, SCH = SCH_, IUPS = IUPS_, PSPLIT = PSPLIT_;
+  static constexpr bool TRANSW = TRANSW_, VEC = VEC_;
+  // the same tile on the transposed, flipped weights (grad-x of a stride-1 conv), on a zero-inserted
+  // half-size input (IUPS), in row blocks of one image (PSPLIT)
+  using transposed = FwdTile<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, !TRANSW, VEC, UPS, SCH, IUPS, PSPLIT>;
+  template <int N>
+  using iups = FwdTile<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, TRANSW, VEC, UPS, SCH, N, PSPLIT>;
+  template <int N>
+  using psplit = FwdTile<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, TRANSW, VEC, UPS, SCH, IUPS, N>;
   static constexpr int P = (H + 2 * PD - R) / ST + 1, Q = (W + 2 * PD - S) / ST + 1, PQ = P * Q;
   static_assert(PSPLIT == 1 || (IMGS == 1 && P % PSPLIT == 0), "row blocks of one image");
   // Bank-conflict-free LDS image (ds_read_b32: bank = dword % 32, one 32-lane half-wave per
@@ -478,14 +492,15 @@ struct ConvFwdCfg {
 
 // (a device function of the workgroup's grid coordinates: the downsample-conv backward pairs run it
 // on one part of a combined grid, launch_conv_dgrad)
-template <int R, int S, int ST, int PD, int H, int W, int CK, int BM, int IMGS, int WM, int NBUF, int KB, bool TRANSW,
-          bool VEC, int UPS = 1, int SCH = 0, int IUPS = 1, int PSPLIT = 1>
+template <typename G>  // G: a FwdTile
 __device__ __forceinline__ void conv_fwd_body(const float* __restrict__ x, const float* __restrict__ w,
                                               float* __restrict__ y, float* __restrict__ part, int Cin, int Kout,
                                               int cps, int64_t slab, const float* __restrict__ addend,
                                               const ConvBnStats& st, const uint3 bid, const uint3 gdim,
                                               float* __restrict__ smem) {
-  using G = ConvFwdCfg<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, TRANSW, PSPLIT>;
+  constexpr int S = G::S, ST = G::ST, PD = G::PD, H = G::H, W = G::W, CK = G::CK, BM = G::BM, IMGS = G::IMGS,
+                WM = G::WM, NBUF = G::NBUF, KB = G::KB, UPS = G::UPS, SCH = G::SCH, IUPS = G::IUPS, PSPLIT = G::PSPLIT;
+  constexpr bool TRANSW = G::TRANSW, VEC = G::VEC;
   constexpr int AE = (BM * G::KK + 3) / 4;  // float4 slots (scalar path: 4 scalars per slot)
   constexpr int A_PER_T = (AE + 255) / 256;
   float* As = smem;
@@ -881,14 +896,19 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(const float* __restrict__
                                                        int Kout, int cps, int64_t slab,
                                                        const float* __restrict__ addend, ConvBnStats st) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  conv_fwd_body<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, TRANSW, VEC, UPS, SCH, IUPS, PSPLIT>(
+  conv_fwd_body<FwdTile<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, TRANSW, VEC, UPS, SCH, IUPS, PSPLIT>>(
       x, w, y, part, Cin, Kout, cps, slab, addend, st, make_uint3(blockIdx.x, blockIdx.y, blockIdx.z),
       make_uint3(gridDim.x, gridDim.y, gridDim.z), smem);
 }
 
 // ---- grad-W -----------------------------------------------------------------------------
-template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB>
-struct ConvWgCfg {
+// One grad-W kernel configuration as a type: the parameters of conv_wgrad_body (IPS: images per stage)
+template <int R_, int S_, int ST_, int PD_, int H_, int W_, int CB_, int BM_, int NW_, int NBPW_, int KB_, int IPS_ = 1>
+struct WgTile {
+  static constexpr int R = R_, S = S_, ST = ST_, PD = PD_, H = H_, W = W_, CB = CB_, BM = BM_, NW = NW_, NBPW = NBPW_,
+                       KB = KB_, IPS = IPS_;
+  template <int N>
+  using staged = WgTile<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, N>;  // N images per stage
   static constexpr int P = (H + 2 * PD - R) / ST + 1, Q = (W + 2 * PD - S) / ST + 1, PQ = P * Q;
   // odd channel stride + tap-major columns (TAPMAJ: column j = rs * CB + c, so the 32 lanes of
   // a B read are 32 channels at one tap): conflict-free B reads.  Channel-major (c * RS + rs)
@@ -922,9 +942,8 @@ struct ConvWgCfg {
   static constexpr int LDJ = J + 4;
   static constexpr size_t MAIN_BYTES = 2 * (size_t)(A_SZ + B_SZ) * sizeof(float);
   static constexpr size_t EPI_BYTES = TAPMAJ ? (size_t)BM * LDJ * sizeof(float) : 0;
-  static constexpr size_t LDS_BYTES = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
   // IPS images per stage (conv_wgrad_body): both stage buffers hold IPS images' tiles
-  static constexpr size_t lds_bytes(int ips) { return ips * MAIN_BYTES > EPI_BYTES ? ips * MAIN_BYTES : EPI_BYTES; }
+  static constexpr size_t LDS_BYTES = IPS * MAIN_BYTES > EPI_BYTES ? IPS * MAIN_BYTES : EPI_BYTES;
   static_assert(MB * JB == NW * NBPW, "every wave owns NBPW 32x32 blocks");
   static_assert(P % 2 == 0 && PQ % 4 == 0 && HW % 4 == 0 && NSTEP % KB == 0, "pixel pairing / float4 loads");
 };
@@ -940,11 +959,12 @@ struct ConvWgCfg {
 // per load round trip, the same MFMAs in the same order on every accumulator (bitwise the one-image
 // loop's result).  The slice's image count must be a multiple of IPS: the dispatch (wgrad_staged)
 // never gives a slice another IPS, there is no predicated last stage.
-template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB, int IPS = 1>
+template <typename G>  // G: a WgTile
 __device__ __forceinline__ void conv_wgrad_body(const float* __restrict__ x, const float* __restrict__ dy,
                                                 float* __restrict__ part, int Cin, int Kout, int imgs_per_slice,
                                                 const uint3 bid, float* __restrict__ smem) {
-  using G = ConvWgCfg<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
+  constexpr int S = G::S, ST = G::ST, PD = G::PD, W = G::W, CB = G::CB, BM = G::BM, NBPW = G::NBPW, KB = G::KB,
+                IPS = G::IPS;
   float* As = smem;                       // [2][IPS][A_SZ]
   float* Bs = smem + 2 * IPS * G::A_SZ;   // [2][IPS][B_SZ]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1132,8 +1152,8 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_kernel(const float* __rest
                                                              float* __restrict__ part, int Cin, int Kout,
                                                              int imgs_per_slice) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  conv_wgrad_body<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>(x, dy, part, Cin, Kout, imgs_per_slice,
-                                                                make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), smem);
+  conv_wgrad_body<WgTile<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>>(
+      x, dy, part, Cin, Kout, imgs_per_slice, make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), smem);
 }
 
 // A layer2 backward pair in ONE launch: workgroups [0, n_dgrad) run the Winograd grad-x
@@ -1154,7 +1174,7 @@ __global__ __launch_bounds__(256, 2) void wino_direct_pair_kernel(WinoConvArgs A
   } else {
     if (threadIdx.x >= 64 * NW) return;
     b -= na;
-    conv_wgrad_body<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>(
+    conv_wgrad_body<WgTile<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>>(
         x, dy, part, Cin, Kout, imgs, make_uint3(b % gw.x, (b / gw.x) % gw.y, b / (gw.x * gw.y)), smem);
   }
 }
@@ -1276,20 +1296,58 @@ __global__ __launch_bounds__(256) void conv_slab_sum_ups_kernel(const float* __r
   *reinterpret_cast<f32x4c*>(dx + i4 * 4) = v;
 }
 
-// ---- dispatch -----------------------------------------------------------------------------
-template <typename KernelT>
-static void set_lds(KernelT k, size_t bytes) {
-  hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
+// ---- shape classes --------------------------------------------------------------------------
+// Images per stage of the direct grad-W (conv_wgrad_body IPS): kWgIps for the layer2 3x3 class
+// (kConv3x3Map4: 4 images = 57 KB of tiles, two workgroups per CU as before, 8 float4 of staging
+// registers) when the slice holds at least two such stages, else the one-image loop — so per-GPU
+// batch 64 (4-image slices) runs what it ran.  NDP_FUSION_OFF=wgrad_pipe (A/B arm) and
+// conv_set_wgrad_stage(1) give the one-image loop everywhere; conv_set_wgrad_stage(0) = auto.
+// Measured and not built (profiles/r7/README.md): 2 images per stage, and stages for the 3x3/2 and
+// 1x1/2 classes.  conv_set_wgrad_stage accepts 0, 1 and kWgIps only (the binding rejects the rest).
+constexpr int kWgIps = 4;
+
+// Shape classes with a direct kernel (ConvClass, ndp_kernels.h, lists the shapes; everything else stays
+// on MIOpen / the Toeplitz path).  Each class names its forward, grad-x and grad-W tiles once, here;
+// conv_direct_class detects it, class_info reads the tiles for the host-side plan.
+// MFMA-block schedule of the layer1 / layer2 fwd + grad-x kernels: SCH = 2 (pinned MFMA /
+// LDS-read interleave): ResNet-18 step on 1x MI355X 2.0175 / 2.0154 -> 1.9981 / 1.9994 ms at
+// batch 512, 1.0582 / 1.0627 -> 1.0546 / 1.0569 at batch 64 against the compiler's schedule
+// (iglp_opt(0): 2.0043 / 1.0602; the pinned interleave on the stem / 3x3-2 / 1x1-2 forwards
+// and 16-channel chunks or two-image layer1 tiles were slower — round 3 A/Bs)
+using Fwd3x3Map8 = FwdTile<3, 3, 1, 1, 8, 8, 8, 64, 1, 2, 2, 4, false, true, 1, 2>;
+using Dgrad3x3Map8 = Fwd3x3Map8::transposed;
+using Wgrad3x3Map8 = WgTile<3, 3, 1, 1, 8, 8, 32, 32, 3, 3, 4>;
+using Fwd3x3Map4 = FwdTile<3, 3, 1, 1, 4, 4, 8, 64, 4, 2, 2, 4, false, true, 1, 2>;
+using Dgrad3x3Map4 = Fwd3x3Map4::transposed;
+using Wgrad3x3Map4 = WgTile<3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4>;
+using Wgrad3x3Map4Staged = Wgrad3x3Map4::staged<kWgIps>;
+using Fwd3x3S2 = FwdTile<3, 3, 2, 1, 8, 8, 8, 64, 4, 2, 2, 4, false, true>;
+using Dgrad3x3S2 = Dgrad3x3Map8::iups<2>;  // the layer1 grad-x kernel on the zero-inserted dY (staged, not stored)
+using Wgrad3x3S2 = WgTile<3, 3, 2, 1, 8, 8, 32, 32, 3, 3, 4>;
+using FwdStem = FwdTile<7, 7, 2, 3, 32, 32, 4, 64, 1, 2, 1, 7, false, false>;
+using FwdStem2 = FwdStem::psplit<2>;
+using FwdStem4 = FwdStem::psplit<4>;
+struct NoTile { static constexpr int IMGS = 0, UPS = 1, IUPS = 1, PQ = 0; };  // the stem has no grad-x kernel
+using WgradStem = WgTile<7, 7, 2, 3, 32, 32, 3, 32, 5, 1, 4>;
+// grad-x of a 1x1 stride-2 conv: the transposed 1x1 product on the DH x DW output map, written to the
+// even pixels of the (2 DH) x (2 DW) plane (UPS = 2 epilogue, odd pixels zero)
+template <int DH, int DW, int DBM, int DIMGS>
+using DsDgradTile = FwdTile<1, 1, 1, 0, DH, DW, 8, DBM, DIMGS, 2, 2, 4, true, true, 2>;
+using Fwd1x1S2Map8 = FwdTile<1, 1, 2, 0, 8, 8, 8, 64, 4, 2, 2, 4, false, true>;
+using Dgrad1x1S2Map8 = DsDgradTile<4, 4, 64, 4>;
+using Wgrad1x1S2Map8 = WgTile<1, 1, 2, 0, 8, 8, 32, 32, 1, 1, 4>;
+// the kConv1x1S2Map8 scheme one map size down, 16 images per tile; the Toeplitz GEMM it replaces multiplied 15
+// zero rows of W_big per useful one (profiles/r5/toeplitz_layers_b512.md: 72.8 us fwd + bwd at batch 512)
+using Fwd1x1S2Map4 = FwdTile<1, 1, 2, 0, 4, 4, 8, 64, 16, 2, 2, 4, false, true>;
+using Dgrad1x1S2Map4 = DsDgradTile<2, 2, 64, 16>;
+using Wgrad1x1S2Map4 = WgTile<1, 1, 2, 0, 4, 4, 32, 32, 1, 1, 2>;
 
 // A downsample conv's backward pair (the 1x1 stride-2 classes) in ONE launch: workgroups
 // [0, n_dgrad) run the direct grad-x (conv_fwd_body on the transposed weights, UPS = 2 epilogue),
 // the rest the direct grad-W (64 NW threads; the surplus waves leave before any barrier).
 struct DirectDgradArgs {
-  const float* dy;
-  const float* w;
-  float* dx;
-  float* part;
+  const float *dy, *w;
+  float *dx, *part;
   int Cin, Kout, cps;
   int64_t slab;
   const float* addend;
@@ -1304,63 +1362,24 @@ __global__ __launch_bounds__(256) void direct_pair_kernel(DirectDgradArgs A, uin
   const unsigned na = ga.x * ga.y * ga.z;
   unsigned b = blockIdx.x;
   if (b < na) {
-    conv_fwd_body<1, 1, 1, 0, DH, DW, 8, DBM, DIMGS, 2, 2, 4, true, true, 2>(
-        A.dy, A.w, A.dx, A.part, A.Cin, A.Kout, A.cps, A.slab, A.addend, ConvBnStats{},
-        make_uint3(b % ga.x, (b / ga.x) % ga.y, b / (ga.x * ga.y)), ga, smem);
+    conv_fwd_body<DsDgradTile<DH, DW, DBM, DIMGS>>(A.dy, A.w, A.dx, A.part, A.Cin, A.Kout, A.cps, A.slab, A.addend,
+                                                   ConvBnStats{},
+                                                   make_uint3(b % ga.x, (b / ga.x) % ga.y, b / (ga.x * ga.y)), ga, smem);
   } else {
     if (threadIdx.x >= 64 * NW) return;
     b -= na;
-    conv_wgrad_body<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>(
+    conv_wgrad_body<WgTile<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>>(
         x, dy, part, Cin, Kout, imgs, make_uint3(b % gw.x, (b / gw.x) % gw.y, b / (gw.x * gw.y)), smem);
   }
 }
 
-// ksplit > 1: the ksplit workgroups of an output tile each reduce 1/ksplit of the input
-// channels into their own slab of `part`; conv_slab_sum(_ups) adds the slabs in split order
-// (deterministic).  Used where B / IMGS * Kout / BM alone cannot fill the 256 CUs
-// (small per-GPU batches: the strong-scaling shapes 512 / N).
-template <int R, int S, int ST, int PD, int H, int W, int CK, int BM, int IMGS, int WM, int NBUF, int KB, bool TRANSW,
-          bool VEC, int UPS = 1, int SCH = 0, int IUPS = 1, int PSPLIT = 1>
-static int run_fwd(const float* x, const float* w, float* y, int B, int Cin, int Kout, int ksplit, float* part,
-                   hipStream_t s, const float* addend = nullptr, bool defer = false,
-                   ConvBnStats stats = ConvBnStats{nullptr, nullptr, nullptr, nullptr, nullptr}) {
-  using G = ConvFwdCfg<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, TRANSW, PSPLIT>;
-  auto k = conv_fwd_kernel<R, S, ST, PD, H, W, CK, BM, IMGS, WM, NBUF, KB, TRANSW, VEC, UPS, SCH, IUPS, PSPLIT>;
-  static bool attr = false;  // once per instantiation (> 64 KiB of LDS needs the opt-in)
-  if (!attr) { set_lds(k, G::LDS_BYTES); attr = true; }
-  const int nchunks = (Cin + CK - 1) / CK;
-  if (ksplit < 1 || part == nullptr) ksplit = 1;
-  const int cps = (nchunks + ksplit - 1) / ksplit;
-  ksplit = (nchunks + cps - 1) / cps;
-  const int64_t slab = (int64_t)B * Kout * G::PQ;  // compact partial tile layout
-  // stats: only unsplit launches of statistics-capable tiles (conv_fwd_stats_slices says which)
-  if (!(G::STATS_OK && UPS == 1) || ksplit > 1 || (stats.bx != nullptr && !G::STATS2_OK)) stats.out = nullptr;
-  hipLaunchKernelGGL(k, dim3(B / IMGS * PSPLIT, Kout / BM, ksplit), dim3(256), G::LDS_BYTES, s, x, w, y, part, Cin, Kout, cps,
-                     slab, ksplit > 1 ? nullptr : addend, stats);
-  // defer: leave the ksplit slabs for the consumer (the fused BN kernel sums them while it
-  // reads its input, ops/slablink.py) — one launch fewer per conv
-  // (an addend then goes to the consumer too: it adds it after the slabs, launch_bn_bwd dyadd)
-  if (ksplit > 1 && defer && UPS == 1) return ksplit;
-  if (ksplit > 1) {
-    if constexpr (UPS == 1)
-      hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((slab / 4 + 15) / 16)), dim3(256), 0, s, part, y, slab,
-                         ksplit, addend);
-    else
-      hipLaunchKernelGGL((conv_slab_sum_ups_kernel<G::P, G::Q>), dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, s,
-                         part, y, slab, ksplit, addend);
-  }
-  return 1;
-}
-
 // ---- the downsample block's two forward convs in ONE launch --------------------------------
-// conv1 (3x3 stride 2, class 2) and the 1x1 stride-2 downsample (class 4) read the same block
-// input; the downsample's launch is held back (launch_conv_fwd pair = true) and conv1's launch
+// conv1 (3x3 stride 2, kConv3x3S2) and the 1x1 stride-2 downsample (kConv1x1S2Map8) read the same
+// block input; the downsample's launch is held back (launch_conv_fwd pair = true) and conv1's launch
 // runs both bodies on one grid: conv1's workgroups first (its output feeds bn1 right after).
 struct FwdPart {
-  const float* x;
-  const float* w;
-  float* y;
-  float* part;
+  const float *x, *w;
+  float *y, *part;
   int Cin, Kout, cps;
   int64_t slab;
 };
@@ -1369,40 +1388,87 @@ __global__ __launch_bounds__(256) void ds_fwd_pair_kernel(FwdPart a, uint3 ga, F
   const unsigned na = ga.x * ga.y * ga.z;
   unsigned k = blockIdx.x;
   if (k < na) {
-    conv_fwd_body<3, 3, 2, 1, 8, 8, 8, 64, 4, 2, 2, 4, false, true>(
-        a.x, a.w, a.y, a.part, a.Cin, a.Kout, a.cps, a.slab, nullptr, ConvBnStats{},
-        make_uint3(k % ga.x, (k / ga.x) % ga.y, k / (ga.x * ga.y)), ga, smem);
+    conv_fwd_body<Fwd3x3S2>(a.x, a.w, a.y, a.part, a.Cin, a.Kout, a.cps, a.slab, nullptr, ConvBnStats{},
+                                   make_uint3(k % ga.x, (k / ga.x) % ga.y, k / (ga.x * ga.y)), ga, smem);
   } else {
     k -= na;
-    conv_fwd_body<1, 1, 2, 0, 8, 8, 8, 64, 4, 2, 2, 4, false, true>(
-        b.x, b.w, b.y, b.part, b.Cin, b.Kout, b.cps, b.slab, nullptr, ConvBnStats{},
-        make_uint3(k % gb.x, (k / gb.x) % gb.y, k / (gb.x * gb.y)), gb, smem);
+    conv_fwd_body<Fwd1x1S2Map8>(b.x, b.w, b.y, b.part, b.Cin, b.Kout, b.cps, b.slab, nullptr, ConvBnStats{},
+                                       make_uint3(k % gb.x, (k / gb.x) % gb.y, k / (gb.x * gb.y)), gb, smem);
   }
 }
 
-// the split of a class-2 / class-4 forward as run_fwd normalises it
-template <typename G>
-static FwdPart fwd_part(const float* x, const float* w, float* y, float* part, int B, int Cin, int Kout, int& ksplit) {
-  const int nchunks = (Cin + 8 - 1) / 8;
-  if (ksplit < 1 || part == nullptr) ksplit = 1;
-  const int cps = (nchunks + ksplit - 1) / ksplit;
-  ksplit = (nchunks + cps - 1) / cps;
-  return FwdPart{x, w, y, part, Cin, Kout, cps, (int64_t)B * Kout * G::PQ};
+// ---- launch helpers -------------------------------------------------------------------------
+template <typename KernelT>
+static void set_lds(KernelT k, size_t bytes) {
+  // (result discarded: without the opt-in the launch that follows fails, the error every caller reads)
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 void launch_slab_sum(const float* part, float* out, int64_t n, int nslab, hipStream_t s, const float* addend) {
   hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((n / 4 + 15) / 16)), dim3(256), 0, s, part, out, n, nslab,
                      addend);
 }
+// the split-K sum of a UPS = 2 grad-x tile T (slab: compact floats per partial; dx holds 4x as many)
+template <typename T>
+static void launch_slab_sum_ups(const float* part, float* dx, int64_t slab, int nslab, hipStream_t s,
+                                const float* addend) {
+  hipLaunchKernelGGL((conv_slab_sum_ups_kernel<T::P, T::Q>), dim3((unsigned)((slab + 255) / 256)), dim3(256),
+                     0, s, part, dx, slab, nslab, addend);
+}
 
-// Images per stage of the direct grad-W (conv_wgrad_body IPS): kWgIps for the layer2 3x3 class
-// (class 1: 4 images = 57 KB of tiles, two workgroups per CU as before, 8 float4 of staging
-// registers) when the slice holds at least two such stages, else the one-image loop — so per-GPU
-// batch 64 (4-image slices) runs what it ran.  NDP_FUSION_OFF=wgrad_pipe (A/B arm) and
-// conv_set_wgrad_stage(1) give the one-image loop everywhere; conv_set_wgrad_stage(0) = auto.
-// Measured and not built (profiles/r7/README.md): 2 images per stage, and stages for the 3x3/2 and
-// 1x1/2 classes.  conv_set_wgrad_stage accepts 0, 1 and kWgIps only (the binding rejects the rest).
-constexpr int kWgIps = 4;
+// One forward / grad-x launch: y[B, Kout, ...] from x[B, Cin, ...] (grad-x: x = dY, y = dX)
+struct FwdArgs {
+  const float *x, *w;
+  float* y;
+  int B, Cin, Kout, ksplit;
+  float* part;
+  hipStream_t s;
+  const float* addend;
+  bool defer;
+  ConvBnStats stats;
+};
+// Tile T's kernel arguments and grid for `a`; grid.z = the split-K factor as every launch normalises it (no
+// split without scratch, no empty split).  ksplit > 1: the ksplit workgroups of an output tile each reduce
+// 1/ksplit of the input channels (cps chunks of CK) into their own slab of `part`; conv_slab_sum(_ups) adds
+// the slabs in split order (deterministic).  Used where B / IMGS * Kout / BM alone cannot fill the 256 CUs
+// (small per-GPU batches: the strong-scaling shapes 512 / N).
+template <typename T>
+static FwdPart fwd_part(const FwdArgs& a, uint3& grid) {
+  const int nchunks = (a.Cin + T::CK - 1) / T::CK;
+  const int ksplit = (a.ksplit < 1 || a.part == nullptr) ? 1 : a.ksplit;
+  const int cps = (nchunks + ksplit - 1) / ksplit;
+  grid = make_uint3((unsigned)(a.B / T::IMGS * T::PSPLIT), (unsigned)(a.Kout / T::BM), (unsigned)((nchunks + cps - 1) / cps));
+  return FwdPart{a.x, a.w, a.y, a.part, a.Cin, a.Kout, cps, (int64_t)a.B * a.Kout * T::PQ};  // compact partial tiles
+}
+// take a held-back launch out of its slot
+template <typename P>
+static P take(P& slot) { return std::exchange(slot, P{}); }
+
+template <typename T>
+static int run_fwd(const FwdArgs& a) {
+  auto k = conv_fwd_kernel<T::R, T::S, T::ST, T::PD, T::H, T::W, T::CK, T::BM, T::IMGS, T::WM, T::NBUF, T::KB,
+                           T::TRANSW, T::VEC, T::UPS, T::SCH, T::IUPS, T::PSPLIT>;
+  static bool attr = false;  // once per instantiation (> 64 KiB of LDS needs the opt-in)
+  if (!attr) { set_lds(k, T::LDS_BYTES); attr = true; }
+  uint3 grid;
+  const FwdPart f = fwd_part<T>(a, grid);
+  const int ksplit = (int)grid.z;
+  // stats: only unsplit launches of statistics-capable tiles (ConvPlan::fwd_stats_slices says which)
+  ConvBnStats stats = a.stats;
+  if (!(T::STATS_OK && T::UPS == 1) || ksplit > 1 || (stats.bx != nullptr && !T::STATS2_OK)) stats.out = nullptr;
+  hipLaunchKernelGGL(k, dim3(grid.x, grid.y, grid.z), dim3(256), T::LDS_BYTES, a.s, f.x, f.w, f.y, f.part, f.Cin, f.Kout,
+                     f.cps, f.slab, ksplit > 1 ? nullptr : a.addend, stats);
+  // defer: leave the ksplit slabs for the consumer (the fused BN kernel sums them while it
+  // reads its input, ops/slablink.py) — one launch fewer per conv
+  // (an addend then goes to the consumer too: it adds it after the slabs, launch_bn_bwd dyadd)
+  if (ksplit > 1 && a.defer && T::UPS == 1) return ksplit;
+  if (ksplit > 1) {
+    if constexpr (T::UPS == 1) launch_slab_sum(a.part, a.y, f.slab, ksplit, a.s, a.addend);
+    else launch_slab_sum_ups<T>(a.part, a.y, f.slab, ksplit, a.s, a.addend);
+  }
+  return 1;
+}
+
 static int g_wgrad_stage = 0;
 bool conv_set_wgrad_stage(int n) {
   if (n != 0 && n != 1 && n != kWgIps) return false;
@@ -1418,66 +1484,72 @@ static bool wgrad_staged(int imgs) {
   return on && imgs % kWgIps == 0 && imgs >= 2 * kWgIps;
 }
 
-template <int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB, int IPS = 1>
-static void run_wgrad(const float* x, const float* dy, float* part, float* dw, int B, int Cin, int Kout,
-                      int imgs, hipStream_t s) {
-  using G = ConvWgCfg<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  auto k = conv_wgrad_kernel<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>;
-  constexpr size_t lds = G::lds_bytes(IPS);
+// One direct grad-W launch: slices of `imgs` images into `part`, summed into dw unless dw == nullptr
+// (partials only: the caller sums the slabs, batched, ops/gradfinish.py)
+struct WgArgs {
+  const float *x, *dy;
+  float *part, *dw;
+  int B, Cin, Kout, imgs;
+  hipStream_t s;
+};
+// its grid for tile T: (batch slices, output-channel tiles, input-channel blocks)
+template <typename T>
+static uint3 wgrad_grid(const WgArgs& a) {
+  return make_uint3((unsigned)(a.B / a.imgs), (unsigned)(a.Kout / T::BM), (unsigned)((a.Cin + T::CB - 1) / T::CB));
+}
+template <typename T>
+static void run_wgrad(const WgArgs& a) {
+  auto k = conv_wgrad_kernel<T::R, T::S, T::ST, T::PD, T::H, T::W, T::CB, T::BM, T::NW, T::NBPW, T::KB, T::IPS>;
   static bool attr = false;
-  if (!attr) { set_lds(k, lds); attr = true; }
-  const int slices = B / imgs;
-  hipLaunchKernelGGL(k, dim3(slices, Kout / BM, (Cin + CB - 1) / CB), dim3(G::NT), lds, s, x, dy, part, Cin,
-                     Kout, imgs);
-  if (dw == nullptr) return;  // partials only: the caller sums the slabs (batched, ops/gradfinish.py)
-  const int64_t n = (int64_t)Kout * Cin * G::RS;  // multiple of 4 for every class
-  hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((n / 4 + 15) / 16)), dim3(256), 0, s, part, dw, n, slices);
+  if (!attr) { set_lds(k, T::LDS_BYTES); attr = true; }
+  const uint3 gw = wgrad_grid<T>(a);
+  hipLaunchKernelGGL(k, dim3(gw.x, gw.y, gw.z), dim3(T::NT), T::LDS_BYTES, a.s, a.x, a.dy, a.part, a.Cin, a.Kout,
+                     a.imgs);
+  // (Kout * Cin * RS: a multiple of 4 for every class)
+  if (a.dw != nullptr) launch_slab_sum(a.part, a.dw, (int64_t)a.Kout * a.Cin * T::RS, (int)gw.x, a.s);
 }
 // the layer2 3x3 class: staged where the slice allows (wgrad_staged)
-static void run_wgrad_c1(const float* x, const float* dy, float* part, float* dw, int B, int Cin, int Kout, int imgs,
-                         hipStream_t s) {
-  if (wgrad_staged(imgs)) run_wgrad<3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4, kWgIps>(x, dy, part, dw, B, Cin, Kout, imgs, s);
-  else run_wgrad<3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4>(x, dy, part, dw, B, Cin, Kout, imgs, s);
+static void run_wgrad_c1(const WgArgs& a) {
+  return wgrad_staged(a.imgs) ? run_wgrad<Wgrad3x3Map4Staged>(a) : run_wgrad<Wgrad3x3Map4>(a);
 }
 
-// Shape classes with a direct kernel (everything else stays on MIOpen / the Toeplitz path)
-//   id 0: 3x3 s1 p1 on 8x8   (ResNet layer1)           C, K % 64 == 0
-//   id 1: 3x3 s1 p1 on 4x4   (ResNet layer2)           C, K % 64 == 0
-//   id 2: 3x3 s2 p1 8x8->4x4 (layer2 first conv)       C, K % 64 == 0; grad-x = the id-0 kernel on
-//         the zero-inserted dY (IUPS = 2 staging)
-//   id 3: 7x7 s2 p3 32x32->16x16, C = 3 (stem)         K % 64 == 0
-//   id 4: 1x1 s2 p0 8x8->4x4 (layer2 downsample)        C % 32 == 0, K % 64 == 0;
-//         grad-x = the 1x1 transposed product on the 4x4 map, written to the even pixels
-//         of the 8x8 plane (UPS = 2 epilogue, odd pixels zero)
-//   id 5: 1x1 s2 p0 4x4->2x2 (layer3 downsample)        the id-4 scheme one map size down: 16
-//         images per tile; the Toeplitz GEMM it replaces multiplied 15 zero rows of W_big per
-//         useful one (profiles/r5/toeplitz_layers_b512.md: 72.8 us fwd + bwd at batch 512)
-int conv_direct_class(const ConvGeom& g) {
-  if (g.KH == 3 && g.KW == 3 && g.pad == 1 && g.stride == 1 && g.H == 8 && g.W == 8 && g.C % 64 == 0 && g.Co % 64 == 0)
-    return 0;
-  if (g.KH == 3 && g.KW == 3 && g.pad == 1 && g.stride == 1 && g.H == 4 && g.W == 4 && g.C % 64 == 0 && g.Co % 64 == 0)
-    return 1;
-  if (g.KH == 3 && g.KW == 3 && g.pad == 1 && g.stride == 2 && g.H == 8 && g.W == 8 && g.C % 64 == 0 && g.Co % 64 == 0)
-    return 2;
+// ---- plan -----------------------------------------------------------------------------------
+static int conv_direct_class(const ConvGeom& g) {
+  const bool k3 = g.KH == 3 && g.KW == 3 && g.pad == 1, k1s2 = g.KH == 1 && g.KW == 1 && g.pad == 0 && g.stride == 2;
+  const bool ch64 = g.C % 64 == 0 && g.Co % 64 == 0, map8 = g.H == 8 && g.W == 8, map4 = g.H == 4 && g.W == 4;
+  if (k3 && g.stride == 1 && map8 && ch64) return kConv3x3Map8;
+  if (k3 && g.stride == 1 && map4 && ch64) return kConv3x3Map4;
+  if (k3 && g.stride == 2 && map8 && ch64) return kConv3x3S2;
   if (g.KH == 7 && g.KW == 7 && g.pad == 3 && g.stride == 2 && g.H == 32 && g.W == 32 && g.C == 3 && g.Co % 64 == 0)
-    return 3;
-  if (g.KH == 1 && g.KW == 1 && g.pad == 0 && g.stride == 2 && g.H == 8 && g.W == 8 && g.C % 64 == 0 && g.Co % 64 == 0)
-    return 4;
-  if (g.KH == 1 && g.KW == 1 && g.pad == 0 && g.stride == 2 && g.H == 4 && g.W == 4 && g.C % 64 == 0 && g.Co % 64 == 0)
-    return 5;
-  return -1;
+    return kConvStem;
+  if (k1s2 && map8 && ch64) return kConv1x1S2Map8;
+  if (k1s2 && map4 && ch64) return kConv1x1S2Map4;
+  return kConvNone;
 }
 
-// images per workgroup of the forward / grad-x kernels, images per grad-W slice
-int conv_fwd_imgs(int cls) { return (cls == 0 || cls == 3) ? 1 : cls == 5 ? 16 : 4; }
+// what the host-side plan reads off a class's tiles, and its default images per grad-W slice
+struct ClassInfo {
+  int fwd_imgs, dgrad_imgs;  // images per workgroup (dgrad_imgs 0: no grad-x kernel)
+  int dgrad_pq, dgrad_ups, dgrad_iups;  // grad-x: pixels per image of a compact partial tile; UPS; IUPS
+  int wg_cb, wg_bm, wg_slice;
+};
+template <typename F, typename D, typename Wg>
+static constexpr ClassInfo info_of(int wg_slice) {
+  return {F::IMGS, D::IMGS, D::PQ, D::UPS, D::IUPS, Wg::CB, Wg::BM, wg_slice};
+}
+static ClassInfo class_info(int cls) {
+  switch (cls) {
+    case kConv3x3Map8: return info_of<Fwd3x3Map8, Dgrad3x3Map8, Wgrad3x3Map8>(8);
+    case kConv3x3Map4: return info_of<Fwd3x3Map4, Dgrad3x3Map4, Wgrad3x3Map4>(16);  // 32 from batch 512
+    case kConv3x3S2: return info_of<Fwd3x3S2, Dgrad3x3S2, Wgrad3x3S2>(16);
+    case kConvStem: return info_of<FwdStem, NoTile, WgradStem>(4);
+    case kConv1x1S2Map8: return info_of<Fwd1x1S2Map8, Dgrad1x1S2Map8, Wgrad1x1S2Map8>(8);
+    case kConv1x1S2Map4: return info_of<Fwd1x1S2Map4, Dgrad1x1S2Map4, Wgrad1x1S2Map4>(16);
+    default: return ClassInfo{};
+  }
+}
 
 static constexpr int kFillWgs = 256;  // one workgroup per CU: below this, split the reduction
-
-static int pow2_floor(int v) {
-  int p = 1;
-  while (p * 2 <= v) p *= 2;
-  return p;
-}
 
 // images per grad-W slice: the class default, lowered (power of two dividing B) until the
 // grid has >= kFillWgs workgroups.  Workgroups per slice = (Kout / 32) * ceil(Cin / CB).
@@ -1485,16 +1557,17 @@ static int pow2_floor(int v) {
 // 1.9969 vs 1.9904 / 1.9927 ms; batch 256 1.4473 / 1.4444 vs 1.441.)
 // Round 5 (Winograd grad-W, deferred batched slab sums): doubling the layer1 (Winograd), 3x3/2 and
 // stem slices halves their slabs — ResNet-18 r=4 batch 512 1.5118 / 1.5129 -> 1.4977 / 1.4957 ms;
-// doubling layer2's (class 1) was slower, 1.5043 -> 1.5165 (profiles/r5/bench_wgrad_slices.jsonl).
+// doubling layer2's (kConv3x3Map4) was slower, 1.5043 -> 1.5165 (profiles/r5/bench_wgrad_slices.jsonl).
 // Round 7 (pipelined operand feeding: LDS prefetch in the layer1 Winograd grad-W, 4-image stages in
 // layer2's): the slice sizes re-measured at batch 512 and left as they were — layer1 32-image
 // 1.3774 / 1.3784 vs 1.3574 / 1.3605 ms (16), layer2 16-image 1.3745 / 1.3724 and 64-image 1.4457 /
 // 1.4447 (32), 3x3/2 32-image 1.3779 / 1.3748 (16) (profiles/r7/bench_wgrad_slices.jsonl; the
 // slice overrides of those arms were removed after the runs).
-int conv_wgrad_imgs(int cls, const ConvGeom& g, int B) {
+static int conv_wgrad_imgs(int cls, const ClassInfo& ci, const ConvGeom& g, int B) {
   // (the geometry test only, not the runtime Winograd switch: the slicing stays fixed for a shape,
   // so scratch sized from a cached plan fits whichever grad-W kernel runs)
-  if (cls == 0 && g.H == 8 && g.C % 16 == 0 && g.Co % 16 == 0 && B <= 128 && B % 4 == 0) {
+  const bool l1 = cls == kConv3x3Map8 && g.H == 8 && g.C % 16 == 0 && g.Co % 16 == 0;
+  if (l1 && B <= 128 && B % 4 == 0) {
     // Winograd grad-W with the 4-wave reduction (winograd.hip wino_wgrad_kernel RED = 4) at the
     // small per-GPU batches: a workgroup per 16 x 16 block and slice, >= one image per wave.
     // ResNet-18 r=4 batch 64 0.843 -> 0.830 ms (4x fewer slabs: grad-W 31.7 -> 29.9 µs, slab sum
@@ -1505,7 +1578,7 @@ int conv_wgrad_imgs(int cls, const ConvGeom& g, int B) {
     while (d > 4 && (B % d != 0 || (B / d) * per_slice < kFillWgs)) d /= 2;
     if (B % d == 0 && wino_wgrad_red(B, d)) return d;
   }
-  if (cls == 0 && g.H == 8 && g.C % 16 == 0 && g.Co % 16 == 0 && B >= 256 && B % 16 == 0 && wino_wgrad_red(B, 16)) {
+  if (l1 && B >= 256 && B % 16 == 0 && wino_wgrad_red(B, 16)) {
     // from batch 256: 16-image slices over the 4-wave reduction (4 images per wave) — half the
     // slabs of 8-image slices, two workgroups per CU at 512.  ResNet-18 r=4, ms/step: batch 512
     // 1.3866 / 1.3908 vs 1.4043 / 1.4021 (8-image, 2-wave), batch 256 0.9942 / 0.9993 vs 1.0035 /
@@ -1513,13 +1586,12 @@ int conv_wgrad_imgs(int cls, const ConvGeom& g, int B) {
     // (32-image slices lose with the prefetched feeding too: the round-7 note above)
     return 16;
   }
-  // layer2 (class 1) from batch 512: 32-image slices, half the slabs.  Its grad-W now runs in one
+  // layer2 (kConv3x3Map4) from batch 512: 32-image slices, half the slabs.  Its grad-W now runs in one
   // launch with its grad-x (wino_direct_pair_kernel), which fills the CUs: ResNet-18 r=4 batch 512
   // 1.3711 / 1.3692 vs 1.3775 / 1.3804 ms (16-image), and 1.3806 / 1.3819 vs 1.3877 / 1.3886 on a
   // second box; batch 256 unchanged (0.9927 vs 0.9920 / 0.9914) (profiles/r6/bench_l2_wgrad_slices.jsonl)
-  int def = cls == 0 ? 8 : cls == 1 ? (B >= 512 ? 32 : 16) : cls == 2 ? 16 : cls == 4 ? 8 : cls == 5 ? 16 : 4;
-  const int cb = cls == 3 ? 3 : 32;
-  const int per_slice = (g.Co / 32) * ((g.C + cb - 1) / cb);
+  int def = (cls == kConv3x3Map4 && B >= 512) ? 32 : ci.wg_slice;
+  const int per_slice = (g.Co / ci.wg_bm) * ((g.C + ci.wg_cb - 1) / ci.wg_cb);
   while (def > 1 && B % def != 0) def /= 2;  // a batch that is not a multiple of the default
   while (def > 1 && (B / def) * per_slice < kFillWgs && B % (def / 2) == 0) def /= 2;
   return def;
@@ -1533,44 +1605,32 @@ static constexpr int kConvMaxSplit = 4;
 
 // split-K factor of the forward (dgrad = false) / grad-x (dgrad = true) kernels: a power of
 // two <= the channel chunks, so that (B / IMGS) * (outC / 64) * ksplit >= kFillWgs
-int conv_ksplit(int cls, const ConvGeom& g, int B, bool dgrad) {
-  if (cls < 0 || cls == 3) return 1;
+static int conv_ksplit(int cls, const ClassInfo& ci, const ConvGeom& g, int B, bool dgrad) {
+  if (cls == kConvStem) return 1;
   // the 1x1/2 grad-x runs in one launch with its grad-W (direct_pair_kernel), whose workgroups fill
   // the CUs: unsplit from batch 512 (no slab-sum launch; 1.4306 / 1.4308 -> 1.4192 / 1.4229 ms, at
   // 256 even: 1.0053 vs 1.0076)
-  if (dgrad && (cls == 4 || cls == 5) && B >= 512) return 1;
+  if (dgrad && ci.dgrad_ups == 2 && B >= 512) return 1;
   const int inC = dgrad ? g.Co : g.C, outC = dgrad ? g.C : g.Co;
-  const int imgs = (dgrad && cls == 2) ? 1 : conv_fwd_imgs(cls);  // class-2 grad-x: 8x8 tiles, 1 image
+  const int imgs = dgrad ? ci.dgrad_imgs : ci.fwd_imgs;  // (kConv3x3S2's grad-x: 8x8 tiles, 1 image)
   const int base = (B / imgs) * (outC / 64);
   const int nchunks = inC / 8;
   int ks = 1;
   while (ks * 2 <= nchunks && base * ks < kFillWgs && ks * 2 <= kConvMaxSplit) ks *= 2;
-  return pow2_floor(ks);
-}
-// BatchNorm statistics from the forward epilogue: the layer1 3x3 and stem 7x7 classes (their
-// BatchNorms take the two-kernel large-map path; layer2's single-launch BN computes its own),
-// unsplit launches only.  Returns the partial count S (= workgroups along the batch), 0 = none.
-// split-K Winograd slabs: left to the consumer (defer: it sums them, and an addend after them) or
-// summed here in slab order (+ addend), like run_fwd
-static int wino_slabs(const float* part, float* out, int64_t n, int ks, bool defer, const float* addend,
-                      hipStream_t s) {
-  if (defer) return ks;
-  hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((n / 4 + 15) / 16)), dim3(256), 0, s, part, out, n, ks,
-                     addend);
-  return 1;
+  return ks;
 }
 
-// Winograd F(2x2, 3x3) (winograd.hip) for the 8x8 3x3 classes: forward of class 0, grad-x of
-// class 0 and of class 2 (its zero-inserted dY), unsplit launches that tile exactly
-bool conv_wino(int cls, const ConvGeom& g, int B, bool dgrad) {
-  // the direct kernel's split-K factor (small batches) is kept: the Winograd slabs then go to the
-  // same consumers (slab sum / the fused BN kernel)
-  if (dgrad)  // class 2's grad-x is an 8x8 map (its zero-inserted dY)
-    return (cls == 0 || cls == 1 || cls == 2) && wino_ok(g.Co, g.C, B, g.H, g.W, conv_ksplit(cls, g, B, true));
-  return (cls == 0 || cls == 1) && wino_ok(g.C, g.Co, B, g.H, g.W, conv_ksplit(cls, g, B, false));
+// Winograd F(2x2, 3x3) (winograd.hip) for the 3x3 classes: forward of the stride-1 classes, grad-x of
+// those and of kConv3x3S2 (its zero-inserted dY is an 8x8 map), launches that tile exactly.  The
+// direct kernel's split-K factor ks (small batches) is kept: the Winograd slabs then go to the same
+// consumers (slab sum / the fused BN kernel)
+static bool conv_wino(int cls, const ConvGeom& g, int B, bool dgrad, int ks) {
+  const bool s1 = cls == kConv3x3Map8 || cls == kConv3x3Map4;
+  if (dgrad) return (s1 || cls == kConv3x3S2) && wino_ok(g.Co, g.C, B, g.H, g.W, ks);
+  return s1 && wino_ok(g.C, g.Co, B, g.H, g.W, ks);
 }
 
-// Output-row blocks per image of the stem forward (ConvFwdCfg PSPLIT): enough workgroups for
+// Output-row blocks per image of the stem forward (FwdTile PSPLIT): enough workgroups for
 // the 256 CUs at the small per-GPU batches of the strong-scaling runs.  Every split re-stages
 // the image and the 64 x 196 weight image, so more blocks only pay below one workgroup per CU.
 // Stem forward + statistics epilogue on 1x MI355X (tools/diag/stem_psplit.py, µs, split 1/2/4;
@@ -1579,147 +1639,113 @@ bool conv_wino(int cls, const ConvGeom& g, int B, bool dgrad) {
 // before it, 512: 51.5 / 72.3 / 110 — 1 wave per SIMD from 400+ registers of staging state).
 static int g_stem_psplit = 0;  // 0 = by batch (A/B override: conv_set_stem_psplit)
 void conv_set_stem_psplit(int p) { g_stem_psplit = (p == 1 || p == 2 || p == 4) ? p : 0; }
-int stem_psplit(int B) {
+static int stem_psplit(int B) {
   if (g_stem_psplit) return g_stem_psplit;
   return B >= 256 ? 1 : B >= 128 ? 2 : 4;
 }
 
-int conv_fwd_stats_slices(int cls, const ConvGeom& g, int B) {
-  static_assert(ConvFwdCfg<3, 3, 1, 1, 8, 8, 8, 64, 1, 2, 2, 4, false>::STATS_OK &&
-                    ConvFwdCfg<7, 7, 2, 3, 32, 32, 4, 64, 1, 2, 1, 7, false>::STATS_OK &&
-                    ConvFwdCfg<7, 7, 2, 3, 32, 32, 4, 64, 1, 2, 1, 7, false, 2>::STATS_OK &&
-                    ConvFwdCfg<7, 7, 2, 3, 32, 32, 4, 64, 1, 2, 1, 7, false, 4>::STATS_OK,
+ConvPlan conv_make_plan(const ConvGeom& g, int B) {
+  ConvPlan p;
+  const int cls = conv_direct_class(g);
+  if (cls < 0) return p;
+  const ClassInfo ci = class_info(cls);
+  p.cls = cls;
+  p.fwd_imgs = ci.fwd_imgs;
+  p.wgrad_imgs = conv_wgrad_imgs(cls, ci, g, B);
+  // Every class but the stem runs its grad-x natively.  The 3x3 stride-2 grad-x runs on the
+  // zero-inserted dY (exact, 4x the MFMA work of the sub-pixel form; round 2: 2.006 / 2.005 vs MIOpen
+  // 1.991 ms at batch 512): MIOpen's algorithm choice depends on its on-disk find database and,
+  // captured in a hipGraph, was found non-deterministic and NaN-producing (round 3 bisection).
+  p.dgrad_direct = ci.dgrad_imgs > 0;
+  p.fwd_ksplit = conv_ksplit(cls, ci, g, B, false);
+  p.dgrad_ksplit = conv_ksplit(cls, ci, g, B, true);
+  p.fwd_wino = conv_wino(cls, g, B, false, p.fwd_ksplit);
+  p.dgrad_wino = conv_wino(cls, g, B, true, p.dgrad_ksplit);
+  p.fwd_psplit = cls == kConvStem ? stem_psplit(B) : 1;
+  // BatchNorm statistics from the forward epilogue: the layer1 3x3 and stem 7x7 classes (their
+  // BatchNorms take the two-kernel large-map path; layer2's single-launch BN computes its own), unsplit
+  // launches only.  Partials = workgroups along the batch (the stem: one per image and row block).
+  static_assert(Fwd3x3Map8::STATS_OK && FwdStem::STATS_OK && FwdStem2::STATS_OK && FwdStem4::STATS_OK,
                 "statistics epilogue fits every layer1 / stem tile");
-  if (cls != 0 && cls != 3) return 0;
-  if (conv_ksplit(cls, g, B, false) != 1) return 0;
-  if (cls == 3) return B * stem_psplit(B);  // one partial per (image, row block)
-  return conv_wino(cls, g, B, false) ? B / wino_imgs(g.H) : B / conv_fwd_imgs(cls);
+  if (cls == kConvStem) p.fwd_stats_slices = B * p.fwd_psplit;
+  else if (cls == kConv3x3Map8 && p.fwd_ksplit == 1) p.fwd_stats_slices = B / (p.fwd_wino ? wino_imgs(g.H) : ci.fwd_imgs);
+  // backward-mode BN partial sums from the grad-x epilogue: the layer1 3x3 class (its BN takes the
+  // two-kernel large-map path) and kConv3x3S2, which runs the layer1 grad-x kernel (one image per
+  // tile); unsplit grad-x launches only
+  static_assert(Dgrad3x3Map8::STATS2_OK && Dgrad3x3S2::STATS2_OK, "backward statistics epilogue fits the layer1 grad-x tiles");
+  if ((cls == kConv3x3Map8 || cls == kConv3x3S2) && p.dgrad_ksplit == 1)
+    p.dgrad_stats_slices = B / (p.dgrad_wino ? wino_imgs(g.H) : ci.dgrad_imgs);
+  p.dgrad_slab = (int64_t)B * g.C * ci.dgrad_pq;
+  p.dgrad_defer_ok = ci.dgrad_ups == 1;  // (the UPS = 2 sum scatters: conv_slab_sum_ups_kernel)
+  return p;
 }
-// backward-mode BN partial sums from the grad-x epilogue: the layer1 3x3 class (its BN takes the
-// two-kernel large-map path), unsplit grad-x launches only; 0 = none
-int conv_dgrad_stats_slices(int cls, const ConvGeom& g, int B) {
-  static_assert(ConvFwdCfg<3, 3, 1, 1, 8, 8, 8, 64, 1, 2, 2, 4, true>::STATS2_OK,
-                "backward statistics epilogue fits the layer1 grad-x tiles");
-  // class 2 (3x3 stride 2) runs the layer1 grad-x kernel on the zero-inserted dY: one image per tile
-  if ((cls != 0 && cls != 2) || conv_ksplit(cls, g, B, true) != 1) return 0;
-  if (conv_wino(cls, g, B, true)) return B / wino_imgs(g.H);
-  return cls == 2 ? B : B / conv_fwd_imgs(cls);
-}
-// Every class runs its grad-x natively.  The 3x3 stride-2 grad-x runs on the zero-inserted dY
-// (exact, 4x the MFMA work of the sub-pixel form; round 2: 2.006 / 2.005 vs MIOpen 1.991 ms at
-// batch 512): MIOpen's algorithm choice depends on its on-disk find database and, captured in a
-// hipGraph, was found non-deterministic and NaN-producing (round 3 bisection).
-bool conv_dgrad_direct(int cls) { return cls >= 0 && cls <= 5 && cls != 3; }
 
-// MFMA-block schedule of the layer1 / layer2 fwd + grad-x kernels: SCH = 2 (pinned MFMA /
-// LDS-read interleave): ResNet-18 step on 1x MI355X 2.0175 / 2.0154 -> 1.9981 / 1.9994 ms at
-// batch 512, 1.0582 / 1.0627 -> 1.0546 / 1.0569 at batch 64 against the compiler's schedule
-// (iglp_opt(0): 2.0043 / 1.0602; the pinned interleave on the stem / 3x3-2 / 1x1-2 forwards
-// and 16-channel chunks or two-image layer1 tiles were slower — round 3 A/Bs)
-namespace {
-struct PendingFwd {  // the downsample conv's forward, held for its block's conv1 (class 2)
-  const float* x = nullptr;
-  const float* w = nullptr;
-  float* y = nullptr;
-  float* part = nullptr;
-  int B = 0, ks = 1;
-  bool defer = false;
-  ConvGeom g{};
-  hipStream_t s = nullptr;
-};
-PendingFwd g_pending_fwd;
-using CfgC2 = ConvFwdCfg<3, 3, 2, 1, 8, 8, 8, 64, 4, 2, 2, 4, false, 1>;
-using CfgC4 = ConvFwdCfg<1, 1, 2, 0, 8, 8, 8, 64, 4, 2, 2, 4, false, 1>;
-}  // namespace
+// ---- launchers ------------------------------------------------------------------------------
+// split-K Winograd slabs: left to the consumer (defer: it sums them, and an addend after them) or
+// summed here in slab order (+ addend), like run_fwd
+static int wino_slabs(const float* part, float* out, int64_t n, int ks, bool defer, const float* addend, hipStream_t s) {
+  if (!defer) launch_slab_sum(part, out, n, ks, s, addend);
+  return defer ? ks : 1;
+}
+
+// the downsample conv's forward, held for its block's conv1 (kConv3x3S2); x == nullptr: none
+static FwdArgs g_pending_fwd{};
 
 void conv_flush_pending_fwd() {
-  if (g_pending_fwd.x == nullptr) return;
-  const PendingFwd p = g_pending_fwd;
-  g_pending_fwd = PendingFwd{};
-  run_fwd<1, 1, 2, 0, 8, 8, 8, 64, 4, 2, 2, 4, false, true>(p.x, p.w, p.y, p.B, p.g.C, p.g.Co, p.ks, p.part, p.s,
-                                                           nullptr, p.defer);
+  if (g_pending_fwd.x != nullptr) run_fwd<Fwd1x1S2Map8>(take(g_pending_fwd));
 }
 
-int launch_conv_fwd(const float* x, const float* w, float* y, int B, const ConvGeom& g, float* part, hipStream_t s,
-                    bool defer, double* stats_out, float* wino_u, bool pair) {
+int launch_conv_fwd(const float* x, const float* w, float* y, int B, const ConvGeom& g, const ConvPlan& p, float* part,
+                    hipStream_t s, bool defer, double* stats_out, float* wino_u, bool pair) {
   const ConvBnStats stats{stats_out, nullptr, nullptr, nullptr, nullptr};
-  const int cls = conv_direct_class(g);
-  const int ks = conv_ksplit(cls, g, B, false);
-  if (cls == 4 && pair && stats_out == nullptr) {  // held for conv1 (ds_fwd_pair_kernel); same return as run_fwd
+  const int cls = p.cls, ks = p.fwd_ksplit;
+  FwdArgs a{x, w, y, B, g.C, g.Co, ks, part, s, nullptr, defer, ConvBnStats{}};
+  if (cls == kConv1x1S2Map8 && pair && stats_out == nullptr) {  // held for conv1 (ds_fwd_pair_kernel); same return as run_fwd
     conv_flush_pending_fwd();
-    int k = ks;
-    fwd_part<CfgC4>(x, w, y, part, B, g.C, g.Co, k);
-    g_pending_fwd = PendingFwd{x, w, y, part, B, ks, defer, g, s};
-    return (k > 1 && defer) ? k : 1;
+    uint3 grid;
+    fwd_part<Fwd1x1S2Map8>(a, grid);
+    g_pending_fwd = a;
+    return (grid.z > 1 && defer) ? (int)grid.z : 1;
   }
-  if (cls == 2 && g_pending_fwd.x == x && g_pending_fwd.s == s && g_pending_fwd.B == B && stats_out == nullptr) {
-    const PendingFwd p = g_pending_fwd;
-    g_pending_fwd = PendingFwd{};
-    int ka = ks, kb = p.ks;
-    const FwdPart a = fwd_part<CfgC2>(x, w, y, part, B, g.C, g.Co, ka);
-    const FwdPart b = fwd_part<CfgC4>(p.x, p.w, p.y, p.part, B, p.g.C, p.g.Co, kb);
-    const uint3 ga = make_uint3((unsigned)(B / 4), (unsigned)(g.Co / 64), (unsigned)ka);
-    const uint3 gb = make_uint3((unsigned)(B / 4), (unsigned)(p.g.Co / 64), (unsigned)kb);
-    constexpr size_t lds = CfgC2::LDS_BYTES > CfgC4::LDS_BYTES ? CfgC2::LDS_BYTES : CfgC4::LDS_BYTES;
+  if (cls == kConv3x3S2 && g_pending_fwd.x == x && g_pending_fwd.s == s && g_pending_fwd.B == B && stats_out == nullptr) {
+    const FwdArgs b = take(g_pending_fwd);
+    uint3 ga, gb;
+    const FwdPart fa = fwd_part<Fwd3x3S2>(a, ga), fb = fwd_part<Fwd1x1S2Map8>(b, gb);
+    constexpr size_t lds = std::max(Fwd3x3S2::LDS_BYTES, Fwd1x1S2Map8::LDS_BYTES);
     static bool attr = false;
     if (!attr) { set_lds(ds_fwd_pair_kernel, lds); attr = true; }
-    hipLaunchKernelGGL(ds_fwd_pair_kernel, dim3(ga.x * ga.y * ga.z + gb.x * gb.y * gb.z), dim3(256), lds, s, a, ga, b, gb);
-    if (kb > 1 && !p.defer)
-      hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((b.slab / 4 + 15) / 16)), dim3(256), 0, s, p.part, p.y,
-                         b.slab, kb, nullptr);
-    if (ka > 1 && defer) return ka;
-    if (ka > 1)
-      hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((a.slab / 4 + 15) / 16)), dim3(256), 0, s, part, y,
-                         a.slab, ka, nullptr);
+    hipLaunchKernelGGL(ds_fwd_pair_kernel, dim3(ga.x * ga.y * ga.z + gb.x * gb.y * gb.z), dim3(256), lds, s, fa, ga, fb, gb);
+    if (gb.z > 1 && !b.defer) launch_slab_sum(b.part, b.y, fb.slab, (int)gb.z, s, nullptr);
+    if (ga.z > 1 && defer) return (int)ga.z;
+    if (ga.z > 1) launch_slab_sum(part, y, fa.slab, (int)ga.z, s, nullptr);
     return 1;
   }
   conv_flush_pending_fwd();
-  if (wino_u != nullptr && conv_wino(cls, g, B, false)) {
+  if (wino_u != nullptr && p.fwd_wino) {
     launch_wino_conv(x, wino_u, y, B, g.C, g.Co, g.H, false, 1, nullptr, ks > 1 ? ConvBnStats{} : stats, ks, part, s);
     return ks > 1 ? wino_slabs(part, y, (int64_t)B * g.Co * g.H * g.W, ks, defer, nullptr, s) : 1;
   }
+  if (cls == kConv3x3Map8 || cls == kConvStem) a.stats = stats;  // the classes with a statistics epilogue
   switch (cls) {
-    case 0:
-      return run_fwd<3, 3, 1, 1, 8, 8, 8, 64, 1, 2, 2, 4, false, true, 1, 2>(x, w, y, B, g.C, g.Co, ks, part, s,
-                                                                             nullptr, defer, stats);
-    case 1:
-      return run_fwd<3, 3, 1, 1, 4, 4, 8, 64, 4, 2, 2, 4, false, true, 1, 2>(x, w, y, B, g.C, g.Co, ks, part, s,
-                                                                             nullptr, defer);
-    case 2:
-      return run_fwd<3, 3, 2, 1, 8, 8, 8, 64, 4, 2, 2, 4, false, true>(x, w, y, B, g.C, g.Co, ks, part, s, nullptr,
-                                                                       defer);
-    case 3:
-      switch (stem_psplit(B)) {
-        case 4:
-          return run_fwd<7, 7, 2, 3, 32, 32, 4, 64, 1, 2, 1, 7, false, false, 1, 0, 1, 4>(x, w, y, B, g.C, g.Co, 1, nullptr,
-                                                                                        s, nullptr, false, stats);
-        case 2:
-          return run_fwd<7, 7, 2, 3, 32, 32, 4, 64, 1, 2, 1, 7, false, false, 1, 0, 1, 2>(x, w, y, B, g.C, g.Co, 1, nullptr,
-                                                                                        s, nullptr, false, stats);
-        default:
-          return run_fwd<7, 7, 2, 3, 32, 32, 4, 64, 1, 2, 1, 7, false, false>(x, w, y, B, g.C, g.Co, 1, nullptr, s,
-                                                                              nullptr, false, stats);
-      }
-    case 4:
-      return run_fwd<1, 1, 2, 0, 8, 8, 8, 64, 4, 2, 2, 4, false, true>(x, w, y, B, g.C, g.Co, ks, part, s, nullptr,
-                                                                       defer);
-    case 5:
-      return run_fwd<1, 1, 2, 0, 4, 4, 8, 64, 16, 2, 2, 4, false, true>(x, w, y, B, g.C, g.Co, ks, part, s, nullptr,
-                                                                        defer);
+    case kConv3x3Map8: return run_fwd<Fwd3x3Map8>(a);
+    case kConv3x3Map4: return run_fwd<Fwd3x3Map4>(a);
+    case kConv3x3S2: return run_fwd<Fwd3x3S2>(a);
+    case kConvStem:  // (never split: fwd_ksplit == 1)
+      return p.fwd_psplit == 4   ? run_fwd<FwdStem4>(a)
+             : p.fwd_psplit == 2 ? run_fwd<FwdStem2>(a)
+                                 : run_fwd<FwdStem>(a);
+    case kConv1x1S2Map8: return run_fwd<Fwd1x1S2Map8>(a);
+    case kConv1x1S2Map4: return run_fwd<Fwd1x1S2Map4>(a);
     default: return 1;
   }
 }
 
-// A layer1 Winograd grad-W held back by launch_conv_wgrad(pair = true) for the grad-x of the same
-// conv (host state only: set and consumed within one conv backward, capture-safe)
+// A grad-W held back by launch_conv_wgrad(pair = true) for the grad-x of the same conv (host state
+// only: set and consumed within one conv backward, capture-safe)
 namespace {
 struct PendingWgrad {
-  const float* x = nullptr;
-  const float* dy = nullptr;
-  float* part = nullptr;
-  int B = 0, imgs = 0, cls = -1;
-  ConvGeom g{};
-  hipStream_t s = nullptr;
+  WgArgs a;    // partials only (a.dw == nullptr); a.dy == nullptr: an empty slot
+  int cls, H;  // the conv's class and map size
 };
 // two slots: a downsample block's two sibling convs (3x3/2 and 1x1/2) each hold one while the
 // BranchLink defers one of their grad-x launches into the other's backward
@@ -1728,91 +1754,82 @@ PendingWgrad g_pending[kPendingSlots];
 unsigned g_pending_seq[kPendingSlots];
 unsigned g_seq = 0;
 
-void launch_pending(const PendingWgrad& p);
+// a held-back grad-W on its own (partials only; the classes launch_conv_wgrad holds)
+void launch_pending(const PendingWgrad& p) {
+  const WgArgs& a = p.a;
+  switch (p.cls) {
+    case kConv3x3Map8: return launch_wino_wgrad(a.x, a.dy, a.part, a.B, a.Cin, a.Kout, p.H, a.imgs, a.s);
+    case kConv3x3Map4: return run_wgrad_c1(a);
+    case kConv3x3S2: return run_wgrad<Wgrad3x3S2>(a);
+    case kConv1x1S2Map8: return run_wgrad<Wgrad1x1S2Map8>(a);
+    case kConv1x1S2Map4: return run_wgrad<Wgrad1x1S2Map4>(a);
+    default: return;
+  }
+}
 // the held-back grad-W of THIS grad-x's conv (same dY, same geometry and stream), or nullptr
 PendingWgrad* find_pending(const float* dy, int cls, int B, const ConvGeom& g, hipStream_t s) {
   for (auto& p : g_pending)
-    if (p.dy == dy && p.cls == cls && p.s == s && p.B == B && p.g.C == g.C && p.g.Co == g.Co && p.g.H == g.H) return &p;
+    if (p.a.dy == dy && p.cls == cls && p.a.s == s && p.a.B == B && p.a.Cin == g.C && p.a.Kout == g.Co && p.H == g.H)
+      return &p;
   return nullptr;
 }
 // launch (alone) whatever is held for this dY
 void flush_pending_dy(const float* dy) {
   for (auto& p : g_pending)
-    if (p.dy == dy) {
-      const PendingWgrad q = p;
-      p = PendingWgrad{};
-      launch_pending(q);
-    }
+    if (p.a.dy == dy) launch_pending(take(p));
 }
 // hold a grad-W: a free slot, else the oldest one is launched alone first
 void hold_pending(const PendingWgrad& q) {
   int k = -1;
   for (int i = 0; i < kPendingSlots; ++i)
-    if (g_pending[i].dy == nullptr) { k = i; break; }
+    if (g_pending[i].a.dy == nullptr) { k = i; break; }
   if (k < 0) {
     k = g_pending_seq[0] <= g_pending_seq[1] ? 0 : 1;
-    const PendingWgrad old = g_pending[k];
-    g_pending[k] = PendingWgrad{};
-    launch_pending(old);
+    launch_pending(take(g_pending[k]));
   }
   g_pending[k] = q;
   g_pending_seq[k] = ++g_seq;
 }
 
-// grad-x of a layer2 class on the Winograd kernel + the held-back direct grad-W, one launch
-template <int WH, int IUPS, int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW, int KB,
-          int IPS = 1>
+// grad-x of a layer2 class on the Winograd kernel (its map size and zero insertion are those of the
+// class's direct grad-x tile D) + the held-back direct grad-W (tile Wg), one launch
+template <typename D, typename Wg>
 void run_pair(const float* dy, const float* u, float* dx, int B, int inC, int outC, const float* addend,
-              const ConvBnStats& st, int ks, float* part_x, const PendingWgrad& p, hipStream_t s) {
-  using G = ConvWgCfg<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  auto k = wino_direct_pair_kernel<WH, IUPS, R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB, IPS>;
-  constexpr size_t lds = kWLds > G::lds_bytes(IPS) ? kWLds : G::lds_bytes(IPS);
+              const ConvBnStats& st, int ks, float* part_x, const WgArgs& p, hipStream_t s) {
+  constexpr int WH = D::H, IUPS = D::IUPS;
+  auto k = wino_direct_pair_kernel<WH, IUPS, Wg::R, Wg::S, Wg::ST, Wg::PD, Wg::H, Wg::W, Wg::CB, Wg::BM, Wg::NW,
+                                   Wg::NBPW, Wg::KB, Wg::IPS>;
+  constexpr size_t lds = std::max<size_t>(kWLds, Wg::LDS_BYTES);
   static bool attr = false;
   if (!attr) { set_lds(k, lds); attr = true; }
   const WinoConvArgs a{dy, u + 16 * (int64_t)inC * outC,  // the grad-x half of the transforms
                        dx, inC, outC, ks > 1 ? nullptr : addend, ks > 1 ? ConvBnStats{} : st, (inC / kWCK) / ks,
                        part_x, (int64_t)B * outC * WH * WH};
   const uint3 ga = make_uint3((unsigned)(B / wino_imgs(WH)), (unsigned)(outC / kWBM), (unsigned)ks);
-  const uint3 gw = make_uint3((unsigned)(p.B / p.imgs), (unsigned)(p.g.Co / BM), (unsigned)((p.g.C + CB - 1) / CB));
+  const uint3 gw = wgrad_grid<Wg>(p);
   const unsigned n = ga.x * ga.y * ga.z + gw.x * gw.y * gw.z;
-  hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, s, a, ga, p.x, p.dy, p.part, p.g.C, p.g.Co, p.imgs, gw);
+  hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, s, a, ga, p.x, p.dy, p.part, p.Cin, p.Kout, p.imgs, gw);
   ++g_pair_launches;
 }
-// the 1x1 stride-2 grad-x (run_fwd's UPS = 2 path, incl. its split-K slab sum) + the held-back direct
-// grad-W of the same conv, one launch
-template <int DH, int DW, int DIMGS, int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW, int NBPW,
-          int KB>
-int run_direct_pair(const float* dy, const float* w, float* dx, int B, int Cin, int Kout, int ksplit, float* part,
-                    const float* addend, const PendingWgrad& p, hipStream_t s) {
-  using GF = ConvFwdCfg<1, 1, 1, 0, DH, DW, 8, 64, DIMGS, 2, 2, 4, true, 1>;
-  using GW = ConvWgCfg<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  auto k = direct_pair_kernel<DH, DW, 64, DIMGS, R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>;
-  constexpr size_t lds = GF::LDS_BYTES > GW::LDS_BYTES ? GF::LDS_BYTES : GW::LDS_BYTES;
+// the 1x1 stride-2 grad-x (tile F: run_fwd's UPS = 2 path, incl. its split-K slab sum) + the held-back
+// direct grad-W of the same conv (tile Wg), one launch
+template <typename F, typename Wg>
+int run_direct_pair(const FwdArgs& a, const WgArgs& p) {
+  static_assert(std::is_same<F, DsDgradTile<F::H, F::W, F::BM, F::IMGS>>::value, "the tile direct_pair_kernel runs");
+  auto k = direct_pair_kernel<F::H, F::W, F::BM, F::IMGS, Wg::R, Wg::S, Wg::ST, Wg::PD, Wg::H, Wg::W, Wg::CB, Wg::BM,
+                              Wg::NW, Wg::NBPW, Wg::KB>;
+  constexpr size_t lds = std::max(F::LDS_BYTES, Wg::LDS_BYTES);
   static bool attr = false;
   if (!attr) { set_lds(k, lds); attr = true; }
-  const int nchunks = (Cin + 7) / 8;
-  if (ksplit < 1 || part == nullptr) ksplit = 1;
-  const int cps = (nchunks + ksplit - 1) / ksplit;
-  ksplit = (nchunks + cps - 1) / cps;
-  const int64_t slab = (int64_t)B * Kout * GF::PQ;
-  const DirectDgradArgs a{dy, w, dx, part, Cin, Kout, cps, slab, ksplit > 1 ? nullptr : addend};
-  const uint3 ga = make_uint3((unsigned)(B / DIMGS), (unsigned)(Kout / 64), (unsigned)ksplit);
-  const uint3 gw = make_uint3((unsigned)(p.B / p.imgs), (unsigned)(p.g.Co / BM), (unsigned)((p.g.C + CB - 1) / CB));
+  uint3 ga;
+  const FwdPart f = fwd_part<F>(a, ga);
+  const DirectDgradArgs d{f.x, f.w, f.y, f.part, f.Cin, f.Kout, f.cps, f.slab, ga.z > 1 ? nullptr : a.addend};
+  const uint3 gw = wgrad_grid<Wg>(p);
   const unsigned n = ga.x * ga.y * ga.z + gw.x * gw.y * gw.z;
-  hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, s, a, ga, p.x, p.dy, p.part, p.g.C, p.g.Co, p.imgs, gw);
+  hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, a.s, d, ga, p.x, p.dy, p.part, p.Cin, p.Kout, p.imgs, gw);
   ++g_pair_launches;
-  if (ksplit > 1)
-    hipLaunchKernelGGL((conv_slab_sum_ups_kernel<GF::P, GF::Q>), dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, s,
-                       part, dx, slab, ksplit, addend);
+  if (ga.z > 1) launch_slab_sum_ups<F>(a.part, a.y, f.slab, (int)ga.z, a.s, a.addend);
   return 1;
-}
-
-void launch_pending(const PendingWgrad& p) {
-  if (p.cls == 0) launch_wino_wgrad(p.x, p.dy, p.part, p.B, p.g.C, p.g.Co, p.g.H, p.imgs, p.s);
-  else if (p.cls == 1) run_wgrad_c1(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
-  else if (p.cls == 2) run_wgrad<3, 3, 2, 1, 8, 8, 32, 32, 3, 3, 4>(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
-  else if (p.cls == 4) run_wgrad<1, 1, 2, 0, 8, 8, 32, 32, 1, 1, 4>(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
-  else run_wgrad<1, 1, 2, 0, 4, 4, 32, 32, 1, 1, 2>(p.x, p.dy, p.part, nullptr, p.B, p.g.C, p.g.Co, p.imgs, p.s);
 }
 }  // namespace
 
@@ -1821,96 +1838,78 @@ void conv_flush_pending() {
   while (true) {
     int k = -1;
     for (int i = 0; i < kPendingSlots; ++i)
-      if (g_pending[i].dy != nullptr && (k < 0 || g_pending_seq[i] < g_pending_seq[k])) k = i;
+      if (g_pending[i].a.dy != nullptr && (k < 0 || g_pending_seq[i] < g_pending_seq[k])) k = i;
     if (k < 0) return;
-    const PendingWgrad p = g_pending[k];
-    g_pending[k] = PendingWgrad{};
-    launch_pending(p);
+    launch_pending(take(g_pending[k]));
   }
 }
 
 // dx[B, C, H, W] from dy[B, Co, OH, OW]
-int launch_conv_dgrad(const float* dy, const float* w, float* dx, int B, const ConvGeom& g, float* part,
-                      hipStream_t s, const float* addend, bool defer, const ConvBnStats* bst, float* wino_u) {
+int launch_conv_dgrad(const float* dy, const float* w, float* dx, int B, const ConvGeom& g, const ConvPlan& p,
+                      float* part, hipStream_t s, const float* addend, bool defer, const ConvBnStats* bst,
+                      float* wino_u) {
   const ConvBnStats stats = bst != nullptr ? *bst : ConvBnStats{nullptr, nullptr, nullptr, nullptr, nullptr};
-  const int cls = conv_direct_class(g);
-  const int ks = conv_ksplit(cls, g, B, true);
-  if (wino_u != nullptr && conv_wino(cls, g, B, true)) {
+  const int cls = p.cls, ks = p.dgrad_ksplit;
+  const ClassInfo ci = class_info(cls);
+  if (wino_u != nullptr && p.dgrad_wino) {
     if (PendingWgrad* pp = find_pending(dy, cls, B, g, s)) {
       // this conv's grad-W is waiting: both in one launch
-      const PendingWgrad p = *pp;
-      *pp = PendingWgrad{};
-      if (cls == 0) {
-        launch_wino_bwd_pair(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, p.x, p.part, p.imgs, s);
+      const WgArgs q = take(*pp).a;
+      if (cls == kConv3x3Map8) {
+        launch_wino_bwd_pair(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, q.x, q.part, q.imgs, s);
         ++g_pair_launches;
-      } else if (cls == 1 && wgrad_staged(p.imgs))
-        run_pair<4, 1, 3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4, kWgIps>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, p,
-                                                                  s);
-      else if (cls == 1)
-        run_pair<4, 1, 3, 3, 1, 1, 4, 4, 32, 32, 3, 3, 4>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, p, s);
+      } else if (cls == kConv3x3Map4 && wgrad_staged(q.imgs))
+        run_pair<Dgrad3x3Map4, Wgrad3x3Map4Staged>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, q, s);
+      else if (cls == kConv3x3Map4)
+        run_pair<Dgrad3x3Map4, Wgrad3x3Map4>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, q, s);
       else
-        run_pair<8, 2, 3, 3, 2, 1, 8, 8, 32, 32, 3, 3, 4>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, p, s);
+        run_pair<Dgrad3x3S2, Wgrad3x3S2>(dy, wino_u, dx, B, g.Co, g.C, addend, stats, ks, part, q, s);
     } else {
       flush_pending_dy(dy);  // this conv's own grad-W, not pairable after all
-      launch_wino_conv(dy, wino_u, dx, B, g.Co, g.C, g.H, true, cls == 2 ? 2 : 1, addend,
-                       ks > 1 ? ConvBnStats{} : stats, ks, part, s);
+      launch_wino_conv(dy, wino_u, dx, B, g.Co, g.C, g.H, true, ci.dgrad_iups, addend, ks > 1 ? ConvBnStats{} : stats, ks,
+                       part, s);
     }
     return ks > 1 ? wino_slabs(part, dx, (int64_t)B * g.C * g.H * g.W, ks, defer, addend, s) : 1;
   }
-  if (PendingWgrad* pp = (cls == 4 || cls == 5) ? find_pending(dy, cls, B, g, s) : nullptr) {
+  FwdArgs a{dy, w, dx, B, g.Co, g.C, ks, part, s, addend, defer, ConvBnStats{}};
+  if (PendingWgrad* pp = ci.dgrad_ups == 2 ? find_pending(dy, cls, B, g, s) : nullptr) {
     // the downsample conv's grad-W is waiting: both in one launch
-    const PendingWgrad p = *pp;
-    *pp = PendingWgrad{};
-    return cls == 4
-        ? run_direct_pair<4, 4, 4, 1, 1, 2, 0, 8, 8, 32, 32, 1, 1, 4>(dy, w, dx, B, g.Co, g.C, ks, part, addend, p, s)
-        : run_direct_pair<2, 2, 16, 1, 1, 2, 0, 4, 4, 32, 32, 1, 1, 2>(dy, w, dx, B, g.Co, g.C, ks, part, addend, p, s);
+    const WgArgs q = take(*pp).a;
+    return cls == kConv1x1S2Map8 ? run_direct_pair<Dgrad1x1S2Map8, Wgrad1x1S2Map8>(a, q)
+                                 : run_direct_pair<Dgrad1x1S2Map4, Wgrad1x1S2Map4>(a, q);
   }
   flush_pending_dy(dy);
+  if (cls == kConv3x3Map8 || cls == kConv3x3S2) a.stats = stats;  // the layer1 grad-x kernel's statistics epilogue
   switch (cls) {
-    case 0:
-      return run_fwd<3, 3, 1, 1, 8, 8, 8, 64, 1, 2, 2, 4, true, true, 1, 2>(dy, w, dx, B, g.Co, g.C, ks, part, s,
-                                                                            addend, defer, stats);
-    case 1:
-      return run_fwd<3, 3, 1, 1, 4, 4, 8, 64, 4, 2, 2, 4, true, true, 1, 2>(dy, w, dx, B, g.Co, g.C, ks, part, s,
-                                                                            addend, defer);
-    case 2:  // 3x3 stride 2: the layer1 grad-x kernel on the zero-inserted dY (staged, not stored)
-      return run_fwd<3, 3, 1, 1, 8, 8, 8, 64, 1, 2, 2, 4, true, true, 1, 2, 2>(dy, w, dx, B, g.Co, g.C, ks, part, s,
-                                                                              addend, defer, stats);
-    case 4:
-      return run_fwd<1, 1, 1, 0, 4, 4, 8, 64, 4, 2, 2, 4, true, true, 2>(dy, w, dx, B, g.Co, g.C, ks, part, s, addend);
-    case 5:
-      return run_fwd<1, 1, 1, 0, 2, 2, 8, 64, 16, 2, 2, 4, true, true, 2>(dy, w, dx, B, g.Co, g.C, ks, part, s, addend);
+    case kConv3x3Map8: return run_fwd<Dgrad3x3Map8>(a);
+    case kConv3x3Map4: return run_fwd<Dgrad3x3Map4>(a);
+    case kConv3x3S2: return run_fwd<Dgrad3x3S2>(a);
+    case kConv1x1S2Map8: return run_fwd<Dgrad1x1S2Map8>(a);
+    case kConv1x1S2Map4: return run_fwd<Dgrad1x1S2Map4>(a);
     default: return 1;
   }
 }
 
-// part: (B / conv_wgrad_imgs) * Co * C * KH * KW floats of scratch
+// part: (B / p.wgrad_imgs) * Co * C * KH * KW floats of scratch
 void launch_conv_wgrad(const float* x, const float* dy, float* part, float* dw, int B, const ConvGeom& g,
-                       hipStream_t s, bool pair) {
+                       const ConvPlan& p, hipStream_t s, bool pair) {
   // a grad-W held back earlier stays held (its grad-x may come later, e.g. from the BranchLink
   // sibling's backward) unless this one needs its slot
-  const int cls = conv_direct_class(g);
-  const int imgs = conv_wgrad_imgs(cls, g, B);
-  if (cls == 0 && wino_wgrad_ok(g.C, g.Co, g.H)) {
+  const int cls = p.cls, imgs = p.wgrad_imgs;
+  const WgArgs a{x, dy, part, dw, B, g.C, g.Co, imgs, s};
+  if (cls == kConv3x3Map8 && wino_wgrad_ok(g.C, g.Co, g.H)) {
     // held back for this conv's grad-x (launch_conv_dgrad).  ResNet-18 r=4, ms/step
     // (profiles/r6/bench_wino_pair.jsonl): batch 64 0.7758 / 0.7656 -> 0.7498 / 0.7517, 128
     // 0.8676 -> 0.8434, 256 (with the layer2 pairs) 1.0539 / 1.0572 -> 1.0303 / 1.0343; at 512 the
     // pair was slower with the one-wave-per-block grad-W (1.4640 -> 1.4818), faster with the
     // two-wave one (winograd.hip wgrad_red: 1.4143 / 1.4147 -> 1.3934 / 1.3966)
-    if (pair && dw == nullptr) {
-      hold_pending(PendingWgrad{x, dy, part, B, imgs, cls, g, s});
-      return;
-    }
+    if (pair && dw == nullptr) return hold_pending(PendingWgrad{a, cls, g.H});
     // Winograd-domain grad-W (winograd.hip): same slab layout and slicing as the direct kernel.
     // Layer1 only: ResNet-18 at batch 512 90.7 vs 130.2 µs per step (4 launches), batch 64 31.1 vs
     // 38.5; the 4x4 maps (one tile per lane group and image: a load per 16 MFMAs) measured slower,
     // 142.8 vs 99.0 µs at batch 512 and 64.0 vs 29.5 at batch 64 (profiles/r5)
     launch_wino_wgrad(x, dy, part, B, g.C, g.Co, g.H, imgs, s);
-    if (dw != nullptr) {
-      const int64_t n = (int64_t)g.Co * g.C * 9;
-      hipLaunchKernelGGL(conv_slab_sum_kernel, dim3((unsigned)((n / 4 + 15) / 16)), dim3(256), 0, s, part, dw, n,
-                         B / imgs);
-    }
+    if (dw != nullptr) launch_slab_sum(part, dw, (int64_t)g.Co * g.C * 9, B / imgs, s);
     return;
   }
   // the layer2 3x3 classes likewise when their grad-x takes the Winograd kernel: the 3x3 class at
@@ -1921,19 +1920,17 @@ void launch_conv_wgrad(const float* x, const float* dy, float* part, float* dw, 
   // The 1x1 stride-2 downsample classes (direct grad-x + direct grad-W, direct_pair_kernel) at every
   // batch: 64 0.7218 / 0.7264 vs 0.7301 / 0.7311, 256 1.0125 vs 1.0256, 512 1.4396 / 1.4355 vs
   // 1.4469 / 1.4360.
-  if (pair && dw == nullptr &&
-      (((cls == 1 || (cls == 2 && B <= 256)) && conv_wino(cls, g, B, true)) || cls == 4 || cls == 5)) {
-    hold_pending(PendingWgrad{x, dy, part, B, imgs, cls, g, s});
-    return;
-  }
+  const bool wino_pair = (cls == kConv3x3Map4 || (cls == kConv3x3S2 && B <= 256)) && p.dgrad_wino;
+  if (pair && dw == nullptr && (wino_pair || cls == kConv1x1S2Map8 || cls == kConv1x1S2Map4))
+    return hold_pending(PendingWgrad{a, cls, g.H});
   switch (cls) {
-    case 0: run_wgrad<3, 3, 1, 1, 8, 8, 32, 32, 3, 3, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
-    case 1: run_wgrad_c1(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
-    case 2: run_wgrad<3, 3, 2, 1, 8, 8, 32, 32, 3, 3, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
-    case 3: run_wgrad<7, 7, 2, 3, 32, 32, 3, 32, 5, 1, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
-    case 4: run_wgrad<1, 1, 2, 0, 8, 8, 32, 32, 1, 1, 4>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
-    case 5: run_wgrad<1, 1, 2, 0, 4, 4, 32, 32, 1, 1, 2>(x, dy, part, dw, B, g.C, g.Co, imgs, s); break;
-    default: break;
+    case kConv3x3Map8: return run_wgrad<Wgrad3x3Map8>(a);
+    case kConv3x3Map4: return run_wgrad_c1(a);
+    case kConv3x3S2: return run_wgrad<Wgrad3x3S2>(a);
+    case kConvStem: return run_wgrad<WgradStem>(a);
+    case kConv1x1S2Map8: return run_wgrad<Wgrad1x1S2Map8>(a);
+    case kConv1x1S2Map4: return run_wgrad<Wgrad1x1S2Map4>(a);
+    default: return;
   }
 }
 

@@ -184,7 +184,7 @@ void launch_bn_fwd(const float* x, const float* res, float* y, const float* gamm
                    int training, int single, hipStream_t s, const float* xpart = nullptr, int nslab = 0,
                    const double* xstats = nullptr, int xS = 0);
 // xstats (nullable, training): [C][xS][2] fp64 partial sums of x from the producing conv's
-// epilogue (conv_fwd_stats_slices); the large-map path then skips its statistics pass
+// epilogue (ConvPlan::fwd_stats_slices); the large-map path then skips its statistics pass
 // xpart / dypart (nullable): the input x (forward) / dy (backward) is the sum of `nslab`
 // split-K slabs of numel(x) floats (a deferred conv sum); the forward also writes the sum to x
 void launch_bn_bwd(const float* dy, const float* y, const float* x, const float* gamma, const float* save_mean,
@@ -316,18 +316,35 @@ void launch_slab_sum_many(const SlabBatch& b, hipStream_t s);
 void launch_gradw_finish(const SlabBatch& sb, const FoldBatch& fb, hipStream_t s);
 // dW [Co, C, KH, KW] <- fold of dWt_big [Co*OH*OW, C*H*W]  (fixed-order sum, deterministic)
 void launch_toeplitz_fold(const float* dwb, float* dw, const ConvGeom& g, hipStream_t s);
-// direct fp32-MFMA convolutions: shape class (-1 = none), images per workgroup / slice
-int conv_direct_class(const ConvGeom& g);
-int conv_fwd_imgs(int cls);
-int conv_wgrad_imgs(int cls, const ConvGeom& g, int B);
-bool conv_dgrad_direct(int cls);
-// split-K factor (1 = none) of the forward / grad-x kernel for batch B; with ksplit > 1 the
-// launchers need `part` scratch of ksplit * (compact output) floats: B * outC * OH * OW
-// (the stride-2 1x1 grad-x: B * C * 4 * 4 before its even-pixel scatter)
-int conv_ksplit(int cls, const ConvGeom& g, int B, bool dgrad);
+// direct fp32-MFMA convolutions: the shape classes with a kernel (C, Co % 64 == 0, the stem C = 3; conv_plan
+// returns the values to Python).  ResNet layer1 / layer2 3x3 s1 p1 on 8x8 / 4x4 maps, layer2's first conv 3x3 s2
+// p1 8x8 -> 4x4, the 7x7 s2 p3 stem 32x32 -> 16x16, the layer2 / layer3 downsamples 1x1 s2 p0 on 8x8 / 4x4
+enum ConvClass : int {
+  kConvNone = -1, kConv3x3Map8 = 0, kConv3x3Map4 = 1, kConv3x3S2 = 2, kConvStem = 3, kConv1x1S2Map8 = 4, kConv1x1S2Map4 = 5
+};
+// What the three launchers below do for (geometry, batch): computed once per call by conv_make_plan
+// (the Winograd and stem-split switches are mutable at run time), checked against the tensors by
+// the caller and handed to the launcher.  cls == kConvNone (no direct kernel) leaves the defaults.
+// The forward / grad-x kernels need B % fwd_imgs == 0, the grad-W B % wgrad_imgs == 0.
+struct ConvPlan {
+  int cls = kConvNone;
+  int fwd_imgs = 0, wgrad_imgs = 0;  // images per forward / grad-x workgroup, per grad-W slice
+  bool dgrad_direct = false;         // the class has a grad-x kernel
+  // split-K factor (1 = none) of the forward / grad-x kernel; with ksplit > 1 the launchers need
+  // `part` scratch of ksplit slabs: B * Co * OH * OW floats forward, dgrad_slab floats grad-x
+  // (B * C * H * W; the stride-2 1x1 classes B * C * OH * OW, their product before the even-pixel
+  // scatter, which only the launcher can sum: dgrad_defer_ok false)
+  int fwd_ksplit = 1, dgrad_ksplit = 1;
+  int64_t dgrad_slab = 0;
+  bool dgrad_defer_ok = false;
+  bool fwd_wino = false, dgrad_wino = false;  // the launch takes the Winograd kernel (given wino_u)
+  int fwd_psplit = 1;                         // output-row blocks per image (the stem forward)
+  int fwd_stats_slices = 0, dgrad_stats_slices = 0;  // BatchNorm statistics partials of the epilogue (0 = none)
+};
+ConvPlan conv_make_plan(const ConvGeom& g, int B);
 // defer: with split-K, skip the slab sum and return the number of slabs left in `part`
 // (compact output layout, slab = numel(out)); returns 1 when `y` / `dx` holds the result
-// stats (nullable; only where conv_fwd_stats_slices > 0): BatchNorm partial sums of y from the
+// stats (nullable; only where the plan has fwd_stats_slices > 0): BatchNorm partial sums of y from the
 // epilogue, [Co][S][2] fp64 (sum, sum of squares per channel and batch tile)
 // BatchNorm partial sums from the epilogue (out != nullptr): forward mode (bx == nullptr) sums
 // the output v and v^2 for the BN that consumes it; backward mode sums dz = v * (by > 0) and
@@ -341,27 +358,24 @@ struct ConvBnStats {
   const float* invstd;
 };
 // wino_u (nullable): the conv's Winograd weight transforms (launch_wino_weights: forward + grad-x
-// layouts, 32 * Co * C floats) when conv_wino(cls, g, B, dgrad) — the launch then runs the Winograd kernel
-// pair: a downsample conv (class 4) forward may be held back and launched together with the next
-// class-2 forward of the same input (ds_fwd_pair_kernel); conv_flush_pending_fwd() launches it alone
-int launch_conv_fwd(const float* x, const float* w, float* y, int B, const ConvGeom& g, float* part, hipStream_t s,
-                    bool defer = false, double* stats = nullptr, float* wino_u = nullptr, bool pair = false);
+// layouts, 32 * Co * C floats) when the plan says fwd_wino / dgrad_wino — the launch then runs the Winograd kernel
+// pair: a downsample conv (kConv1x1S2Map8) forward may be held back and launched together with the next
+// kConv3x3S2 forward of the same input (ds_fwd_pair_kernel); conv_flush_pending_fwd() launches it alone
+int launch_conv_fwd(const float* x, const float* w, float* y, int B, const ConvGeom& g, const ConvPlan& p, float* part,
+                    hipStream_t s, bool defer = false, double* stats = nullptr, float* wino_u = nullptr,
+                    bool pair = false);
 void conv_flush_pending_fwd();
-// stem forward output-row blocks per image (by batch; A/B override 1 / 2 / 4, 0 = auto)
-int stem_psplit(int B);
+// stem forward output-row blocks per image (A/B override 1 / 2 / 4, 0 = by batch)
 void conv_set_stem_psplit(int p);
-int conv_fwd_stats_slices(int cls, const ConvGeom& g, int B);
 // addend (nullable, 3x3 classes): dx += addend in the epilogue / split-K sum; with defer the
 // slabs are left unsummed and the consumer adds the addend after them (launch_bn_bwd dyadd)
-// bst (nullable; the layer1 3x3 class, unsplit: conv_dgrad_stats_slices): backward-mode BN partial
+// bst (nullable; the layer1 3x3 class, unsplit: dgrad_stats_slices > 0): backward-mode BN partial
 // sums of dx for the BN whose output gradient dx is
-int launch_conv_dgrad(const float* dy, const float* w, float* dx, int B, const ConvGeom& g, float* part,
-                      hipStream_t s, const float* addend = nullptr, bool defer = false,
+int launch_conv_dgrad(const float* dy, const float* w, float* dx, int B, const ConvGeom& g, const ConvPlan& p,
+                      float* part, hipStream_t s, const float* addend = nullptr, bool defer = false,
                       const ConvBnStats* bst = nullptr, float* wino_u = nullptr);
-int conv_dgrad_stats_slices(int cls, const ConvGeom& g, int B);
-// Winograd F(2x2, 3x3) path of the 8x8 3x3 classes (winograd.hip): whether a launch takes it,
+// Winograd F(2x2, 3x3) path of the 8x8 3x3 classes (winograd.hip): whether a launch can take it,
 // and the U scratch it needs (16 * inC * outC floats)
-bool conv_wino(int cls, const ConvGeom& g, int B, bool dgrad);
 bool wino_ok(int inC, int outC, int B, int H, int W, int ks);
 bool wino_disabled();
 void wino_set_enabled(bool on);
@@ -396,12 +410,12 @@ void launch_wino_conv(const float* x, const float* u, float* y, int B, int inC, 
 // the split-K sums; out may alias addend
 void launch_slab_sum(const float* part, float* out, int64_t n, int nslab, hipStream_t s,
                      const float* addend = nullptr);
-// part: (B / conv_wgrad_imgs(cls, g, B)) * Co*C*KH*KW floats of scratch.  pair: a layer1 Winograd
+// part: (B / p.wgrad_imgs) * Co*C*KH*KW floats of scratch.  pair: a layer1 Winograd
 // grad-W into `part` (dw == nullptr) may be held back and launched together with the next
 // launch_conv_dgrad of the same dY (one wino_bwd_pair_kernel launch); conv_flush_pending() launches
 // a held-back grad-W on its own (the caller's end of the conv backward)
 void launch_conv_wgrad(const float* x, const float* dy, float* part, float* dw, int B, const ConvGeom& g,
-                       hipStream_t s, bool pair = false);
+                       const ConvPlan& p, hipStream_t s, bool pair = false);
 void conv_flush_pending();
 void launch_wino_bwd_pair(const float* dy, const float* u, float* dx, int B, int inC, int outC, const float* addend,
                           const ConvBnStats& st, int ks, float* part_x, const float* x, float* part_w, int imgs,
