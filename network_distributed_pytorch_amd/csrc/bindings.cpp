@@ -1228,6 +1228,49 @@ void cls_metrics(torch::Tensor x, torch::Tensor tgt, torch::Tensor state, torch:
   check_launch("launch_cls_metrics");
 }
 
+// batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
+// [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
+// shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
+void image_batch(torch::Tensor src, torch::Tensor labels, torch::Tensor idx, torch::Tensor out,
+                 torch::Tensor out_target, int64_t m, int64_t B, std::vector<double> scale, std::vector<double> shift,
+                 int64_t pad, bool flip_on, int64_t seed, int64_t epoch, int64_t pad_target, torch::Tensor err) {
+  TORCH_CHECK(src.scalar_type() == torch::kUInt8 && src.dim() == 4 && src.is_contiguous(),
+              "image_batch: src must be contiguous uint8 [N, C, 32, 32]");
+  TORCH_CHECK(src.size(2) == 32 && src.size(3) == 32, "image_batch: H == W == 32 required, got ", src.size(2), " x ",
+              src.size(3));
+  const int64_t N = src.size(0), C = src.size(1);
+  TORCH_CHECK(N >= 1 && N < (1LL << 31), "image_batch: 1 <= N < 2^31 required");
+  TORCH_CHECK(C >= 1 && C <= ndp::kImageMaxC, "image_batch: 1 <= C <= ", ndp::kImageMaxC, " required");
+  TORCH_CHECK((int64_t)scale.size() == C && (int64_t)shift.size() == C, "image_batch: scale / shift need C entries");
+  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.dim() == 1 && labels.is_contiguous() &&
+                  labels.numel() == N, "image_batch: labels must be contiguous int64 [N]");
+  TORCH_CHECK(B >= 1 && B * C < (1LL << 31), "image_batch: 1 <= B, B * C < 2^31 required");
+  TORCH_CHECK(m >= 1 && m <= B, "image_batch: 1 <= m <= B required (m = ", m, ", B = ", B, ")");
+  TORCH_CHECK(idx.scalar_type() == torch::kInt64 && idx.dim() == 1 && idx.is_contiguous() && idx.numel() >= m,
+              "image_batch: idx must be contiguous int64 with >= m elements");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat32 && out.dim() == 4 && out.is_contiguous() && out.size(0) >= B &&
+                  out.size(1) == C && out.size(2) == 32 && out.size(3) == 32,
+              "image_batch: out must be contiguous float32 [>= B, C, 32, 32]");
+  TORCH_CHECK(out_target.scalar_type() == torch::kInt64 && out_target.dim() == 1 && out_target.is_contiguous() &&
+                  out_target.numel() >= B, "image_batch: out_target must be contiguous int64 [>= B]");
+  TORCH_CHECK(pad >= 0 && pad <= 8, "image_batch: 0 <= pad <= 8 required");
+  TORCH_CHECK(err.scalar_type() == torch::kInt32 && err.numel() >= 1, "image_batch: err must be int32");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, "image_batch: out must be 16-byte aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 4 == 0, "image_batch: src must be 4-byte aligned");
+  check_dev(src, "src"); check_dev(labels, "labels"); check_dev(idx, "idx"); check_dev(out, "out");
+  check_dev(out_target, "out_target"); check_dev(err, "err");
+  ndp::ImageNorm norm{};
+  for (int64_t c = 0; c < C; ++c) {
+    norm.scale[c] = (float)scale[c];
+    norm.shift[c] = (float)shift[c];
+  }
+  ndp::launch_image_batch(src.data_ptr<uint8_t>(), labels.data_ptr<int64_t>(), idx.data_ptr<int64_t>(),
+                          out.data_ptr<float>(), out_target.data_ptr<int64_t>(), (int)m, (int)B, N, (int)C, norm,
+                          (int)pad, flip_on ? 1 : 0, (uint32_t)(uint64_t)seed, (uint32_t)(uint64_t)epoch, pad_target,
+                          err.data_ptr<int32_t>(), cur_stream());
+  check_launch("launch_image_batch");
+}
+
 // fused residual add + LayerNorm (last dim D): y, s (= a + b), mean, rstd are outputs
 // LayerNorm hash dropout: mode 0 none / 1 on the input a / 2 on the output (layernorm.hip)
 static ndp::LnDrop ln_drop(int64_t mode, double p, const c10::optional<torch::Tensor>& seed,
@@ -1572,6 +1615,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("cls_metrics", &cls_metrics, py::arg("x"), py::arg("tgt"), py::arg("state"), py::arg("rowbuf"),
         py::arg("ctr"), py::arg("ignore_index"), py::arg("k"), py::arg("pred") = py::none());
+  m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
+        py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
+        py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   register_comm(m);

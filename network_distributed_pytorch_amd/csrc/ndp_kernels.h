@@ -251,6 +251,22 @@ void launch_cls_metrics(const float* x, const int64_t* tgt, int B, int K, int64_
                         float* rowbuf, unsigned* ctr, int64_t* pred, hipStream_t s);
 }  // namespace ndp
 
+// ---- batch assembly from byte images (image_batch.hip) ------------------------------------
+// src [N, C, 32, 32] bytes, labels [N], idx [m]; out [B, C, 32, 32] fp32 and out_target [B] are
+// written in full: rows < m gathered, normalised (fmaf(byte, scale[c], shift[c])) and optionally
+// cropped / flipped by a hash of (seed, epoch, index); rows >= m and rows whose index is outside
+// [0, N) are zero with target = pad_target, and the latter store 1 into *err.
+namespace ndp {
+constexpr int kImageMaxC = 8;
+struct ImageNorm {
+  float scale[kImageMaxC];
+  float shift[kImageMaxC];
+};
+void launch_image_batch(const uint8_t* src, const int64_t* labels, const int64_t* idx, float* out,
+                        int64_t* out_target, int m, int B, int64_t N, int C, const ImageNorm& norm, int pad,
+                        int flip_on, uint32_t seed, uint32_t epoch, int64_t pad_target, int* err, hipStream_t s);
+}  // namespace ndp
+
 // ---- fused residual add + LayerNorm over the last dim (layernorm.hip) --------------------
 namespace ndp {
 bool ln_supported(int D);  // D in {256, 512, 768, 1024}

@@ -14,8 +14,10 @@ print; the PowerSGD Algorithm-2 update and the dense SGD(momentum) update.
 Fixed / added: rank-0 parameter broadcast (Q3/Q4), a rank-identical
 IMDb split (Q2), a private PowerSGD RNG (Q1), configurable ``n_workers`` / batch
 (Q11/Q12), synthetic device-resident data, JSONL metrics, checkpoint/resume,
-replica-divergence checks, link emulation, hipGraph step capture, and held-out evaluation
-(``eval_every``: :func:`evaluate`, the fused loss / top-1 / top-k pass of ops/metrics.py).
+replica-divergence checks, link emulation, hipGraph step capture, held-out evaluation
+(``eval_every``: :func:`evaluate`, the fused loss / top-1 / top-k pass of ops/metrics.py), and
+training / evaluating on the CIFAR-10 files of ``data_root`` (utils/cifar.py), held as bytes and
+turned into batches by one launch each (ops/image_batch.py); ``data_root=None`` = synthetic data.
 """
 from __future__ import annotations
 
@@ -37,8 +39,9 @@ from .parallel.comm import LINK_PRESETS, Communicator
 from .parallel.trainer import build_grad_sync
 from .utils.checkpoint import load_checkpoint, save_checkpoint
 from .utils.config import validate_config
-from .utils.data import (DeviceLoader, SyntheticCIFAR10, SyntheticIMDb, SyntheticMLPData, TensorDictDataset,
-                         train_val_split)
+from .utils.cifar import load_cifar10
+from .utils.data import (NORMALIZE, DeviceLoader, SyntheticCIFAR10, SyntheticIMDb, SyntheticMLPData,
+                         TensorDictDataset, Uint8ImageDataset, train_val_split)
 from .utils.divergence import ReplicaChecker
 from .utils.metrics import JsonlLogger, PhaseTimer, print_epoch, print_eval
 from .utils.partition_helper import DataPartitioner
@@ -62,6 +65,8 @@ def default_config(**over) -> Dict[str, Any]:
         deterministic=True,
         # held-out evaluation every N epochs (0 = off), held-out size, k of the top-k accuracy
         eval_every=0, eval_size=None, eval_topk=5,
+        # CIFAR-10 from files (None = synthetic data), training augmentation, normalisation
+        data_root=None, augment="none", normalize="half",
     )
     cfg.update(over)
     return cfg
@@ -152,6 +157,21 @@ def _build_data(config, device, world, rank):
     seed = config["data_seed"]
     want_val = bool(config.get("eval_every"))
     eval_size = config.get("eval_size")
+    if task == "cifar" and config.get("data_root"):
+        # the CIFAR-10 files, resident as bytes; batches come from ops.image_batch (one launch)
+        mean, std = NORMALIZE[config.get("normalize", "half")]
+        crop = config.get("augment", "none") == "crop_flip"
+        images, labels = load_cifar10(config["data_root"], train=True)
+        n = min(config["dataset_size"] or len(images), len(images))
+        ds = Uint8ImageDataset(images[:n], labels[:n], mean, std, pad=4 if crop else 0, flip=crop).to(device)
+        val = None
+        if want_val:  # the test split, never augmented
+            vi, vl = load_cifar10(config["data_root"], train=False)
+            nv = min(eval_size or len(vi), len(vi))
+            val = Uint8ImageDataset(vi[:nv], vl[:nv], mean, std).to(device)
+        bsz = int(config["global_batch"] / float(world))
+        part = DataPartitioner(ds, [1.0 / world for _ in range(world)]).use(rank)
+        return part, bsz, val
     if task == "cifar":
         n = config["dataset_size"] or 50000
         val = None
@@ -216,7 +236,10 @@ class Evaluator:
       on the evaluator and reused by later calls (the model's weights are read by the graph at
       replay time, weight transforms included, so it always sees the current parameters);
     * DistilBERT-style datasets (``input_ids`` / ``attention_mask`` / ``labels`` columns) call the
-      model without ``labels``; its logits feed the kernel.
+      model without ``labels``; its logits feed the kernel;
+    * a dataset with ``gather_into`` (``Uint8ImageDataset``) loads batch, targets and tail padding
+      into fp32 static inputs in one launch, unaugmented; every other dataset takes the
+      gather + copy path.
     """
 
     def __init__(self, model, dataset, *, batch: int, comm=None, device=None, topk: int = 5,
@@ -238,7 +261,10 @@ class Evaluator:
         else:
             self.inputs, self.target_key = ["input_ids", "attention_mask"], "labels"
         cols = self.ds.columns
-        self.static = {k: torch.zeros((self.batch,) + tuple(cols[k].shape[1:]), dtype=cols[k].dtype,
+        # a dataset that assembles its own batches (Uint8ImageDataset) delivers fp32 whatever it stores
+        self.fused_load = hasattr(self.ds, "gather_into")
+        self.static = {k: torch.zeros((self.batch,) + tuple(cols[k].shape[1:]),
+                                      dtype=torch.float32 if self.fused_load else cols[k].dtype,
                                       device=self.device) for k in self.inputs}
         self.static_target = torch.full((self.batch,), self.ignore_index, dtype=torch.int64, device=self.device)
         self.metrics = ClassificationMetrics(k=topk, ignore_index=self.ignore_index, device=self.device)
@@ -254,6 +280,9 @@ class Evaluator:
         self.metrics.update(logits, self.static_target)
 
     def _load(self, idx: torch.Tensor):
+        if self.fused_load:  # batch, targets and tail padding in one launch
+            self.ds.gather_into(idx, self.static[self.inputs[0]], self.static_target, pad_target=self.ignore_index)
+            return
         m = int(idx.numel())
         for k in self.inputs:
             self.static[k][:m].copy_(self.ds.columns[k].index_select(0, idx))
@@ -298,6 +327,8 @@ class Evaluator:
                             self._capture()  # a capture enqueues nothing: the state is untouched,
                             self.metrics.state.copy_(state)  # restored all the same
                 rec = self.metrics.compute(self.comm)
+                if hasattr(self.ds, "check_errors"):
+                    self.ds.check_errors()  # after compute(): the pass's one host sync is behind us
         finally:
             self.model.train(was_training)
         rec["comm_bytes"] = self.metrics.comm_bytes
@@ -427,7 +458,9 @@ def run_task(config) -> Dict[str, Any]:
             elif runner is not None:
                 if "batch" not in static:
                     static["batch"] = _clone_batch(batch)
-                else:
+                    if not isinstance(batch, dict):  # later full batches: written in place, one launch
+                        loader.deliver_into(*static["batch"])
+                elif not _delivered(static["batch"], batch):
                     _copy_batch(static["batch"], batch)
                 runner()
                 epoch_loss += loss_static
@@ -462,6 +495,8 @@ def run_task(config) -> Dict[str, Any]:
                 if runner is not None:
                     runner.join()
                 sync.check_errors()  # flag-wait timeouts / MGS barrier / RCCL async errors: fatal
+            if health_every and step % health_every == 0 and hasattr(loader.ds, "check_errors"):
+                loader.ds.check_errors()  # image-batch error word: an index outside the dataset
             if log_every and step % log_every == 0:  # per-step record (host sync at this cadence)
                 loss_now = float((loss_static if runner is not None else loss.detach()).item())
                 now = time.perf_counter()
@@ -484,6 +519,8 @@ def run_task(config) -> Dict[str, Any]:
         mean = float(epoch_loss.item()) / max(1, num_batches if i == num_batches else i)
         if hasattr(sync, "check_errors"):
             sync.check_errors()  # MGS barrier timeouts / RCCL async errors (epoch cadence)
+        if hasattr(loader.ds, "check_errors"):
+            loader.ds.check_errors()
         losses.append(mean)
         if config.get("verbose", True):
             print_epoch(rank, epoch, mean)
@@ -539,6 +576,11 @@ def _same_shape(a, b) -> bool:
     if isinstance(a, dict):
         return all(a[k].shape == b[k].shape for k in a)
     return all(x.shape == y.shape for x, y in zip(a, b))
+
+
+def _delivered(static_batch, batch) -> bool:
+    """True when the loader wrote ``batch`` straight into the static tensors (DeviceLoader.deliver_into)."""
+    return not isinstance(batch, dict) and batch[0] is static_batch[0]
 
 
 def _clone_batch(b):

@@ -29,6 +29,10 @@ __all__ = [
     "upload_epoch",
     "classification_metrics",
     "ClassificationMetrics",
+    "image_batch",
+    "hash4",
+    "crop_flip_draw",
+    "image_norm_constants",
 ]
 
 
@@ -268,3 +272,4 @@ def checksum(x: torch.Tensor) -> float:
 
 
 from .metrics import ClassificationMetrics, classification_metrics  # noqa: E402  (fused eval metrics, csrc/loss.hip)
+from .image_batch import crop_flip_draw, hash4, image_batch, image_norm_constants  # noqa: E402  (csrc/image_batch.hip)

@@ -26,6 +26,8 @@ TASKS = ("cifar", "imdb", "mlp")
 GRAPH_MODES = ("auto", "full", "piecewise", "none")
 LINKS = ("none", "1g", "10g", "100g")
 BACKENDS = ("nccl", "gloo")
+AUGMENTS = ("none", "crop_flip")
+NORMALIZES = ("half", "cifar")
 
 
 @dataclasses.dataclass
@@ -78,6 +80,10 @@ class TrainConfig:
     eval_every: int = 0  # evaluate every N epochs; 0 = off (no held-out data is built)
     eval_size: Optional[int] = None  # held-out size (cifar 10,000, mlp 256; imdb: cap on its validation split)
     eval_topk: int = 5  # k of the top-k accuracy
+    # real CIFAR-10 from files (utils/cifar.py), held as bytes; batches by ops/image_batch.py
+    data_root: Optional[str] = None  # directory with the CIFAR-10 files; None = synthetic data
+    augment: str = "none"  # "crop_flip": random crop (pad 4) + horizontal flip, training only
+    normalize: str = "half"  # "half" = 0.5 / 0.5 per channel (the reference), "cifar" = dataset statistics
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -124,7 +130,7 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
             config[name] = _check_type(name, config[name])
     c = config
     for key, allowed in (("grad_sync", GRAD_SYNCS), ("task", TASKS), ("graph_mode", GRAPH_MODES), ("link", LINKS),
-                         ("distributed_backend", BACKENDS)):
+                         ("distributed_backend", BACKENDS), ("augment", AUGMENTS), ("normalize", NORMALIZES)):
         if c[key] not in allowed:
             raise ConfigError(f"config[{key!r}] = {c[key]!r}; allowed: {list(allowed)}")
     if c["n_workers"] < 1 or not 0 <= c["rank"] < c["n_workers"]:
@@ -147,6 +153,10 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError("log_every >= 1, training_epochs >= 0, timeout_s > 0 required")
     if c["eval_every"] < 0 or c["eval_topk"] < 1 or (c["eval_size"] is not None and c["eval_size"] < 1):
         raise ConfigError("eval_every >= 0, eval_topk >= 1 and eval_size >= 1 (or None) required")
+    if c["data_root"] is not None and c["task"] != "cifar":
+        raise ConfigError(f"data_root is for task='cifar' only (task = {c['task']!r})")
+    if c["augment"] != "none" and c["data_root"] is None:
+        raise ConfigError(f"augment = {c['augment']!r} needs data_root (the synthetic data is never augmented)")
     if unknown:
         config["_unknown_keys"] = unknown
     return config

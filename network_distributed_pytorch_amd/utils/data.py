@@ -18,6 +18,12 @@ Both generate identically on every rank from a seed (so ``DataPartitioner`` shar
 disjoint), and live in HBM: 614 MB for CIFAR is nothing next to 288 GB.
 :class:`DeviceLoader` replaces ``DataLoader(partition, batch_size, shuffle=True)``:
 per-epoch shuffles and batch gathers happen on the GPU (no host->device copy per step).
+
+Real data: :class:`Uint8ImageDataset` keeps the CIFAR-10 files' images (utils/cifar.py) in HBM as
+bytes, 154 MB instead of 614 MB, and assembles every batch with one launch of
+``ops.image_batch`` (gather, normalise, random crop + flip, tail padding, targets);
+:meth:`DeviceLoader.deliver_into` has the loader write full batches straight into a captured
+step's static inputs.
 """
 from __future__ import annotations
 
@@ -29,7 +35,11 @@ import torch
 from .partition_helper import Partition
 
 __all__ = ["SyntheticCIFAR10", "SyntheticMLPData", "SyntheticIMDb", "train_val_split", "DeviceLoader",
-           "TensorDictDataset"]
+           "TensorDictDataset", "Uint8ImageDataset", "NORMALIZE"]
+
+# per-channel (mean, std) of config["normalize"]: "half" is the reference's Normalize(0.5, 0.5)
+NORMALIZE = {"half": ((0.5, 0.5, 0.5), (0.5, 0.5, 0.5)),
+             "cifar": ((0.4914, 0.4822, 0.4465), (0.2470, 0.2435, 0.2616))}
 
 
 class TensorDictDataset:
@@ -56,6 +66,74 @@ class TensorDictDataset:
 
     def to(self, device):
         return TensorDictDataset({k: v.to(device) for k, v in self.columns.items()}, self.as_tuple)
+
+
+class Uint8ImageDataset:
+    """Byte images ``[N, C, 32, 32]`` + int64 labels, resident as bytes; batches are assembled by
+    :func:`ops.image_batch` (gather, normalise, crop + flip, tail padding: one launch on device).
+
+    Presents the ``columns`` / ``as_tuple`` / ``__len__`` / ``to()`` surface of
+    :class:`TensorDictDataset`, so ``DataPartitioner``, :class:`DeviceLoader` and the engine's
+    ``Evaluator`` take it as they take any dataset.  ``pad`` / ``flip`` are the augmentation
+    ``gather`` applies (and ``gather_into`` with ``augment=True``); which crop and flip a sample
+    gets depends on ``(seed, epoch, dataset index)`` only.  ``err`` is the int32 error word an
+    out-of-range index sets; :meth:`check_errors` reads it (one host sync)."""
+
+    def __init__(self, images_u8: torch.Tensor, labels: torch.Tensor, mean, std, pad: int = 0, flip: bool = False):
+        if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or tuple(images_u8.shape[2:]) != (32, 32):
+            raise ValueError(f"Uint8ImageDataset: uint8 [N, C, 32, 32] images expected, got {images_u8.dtype} "
+                             f"{tuple(images_u8.shape)}")
+        if labels.dim() != 1 or labels.shape[0] != images_u8.shape[0]:
+            raise ValueError("Uint8ImageDataset: one label per image expected")
+        C = int(images_u8.shape[1])
+        self.mean = tuple(float(v) for v in (mean if hasattr(mean, "__len__") else (mean,) * C))
+        self.std = tuple(float(v) for v in (std if hasattr(std, "__len__") else (std,) * C))
+        if len(self.mean) != C or len(self.std) != C:
+            raise ValueError(f"Uint8ImageDataset: mean / std need {C} entries")
+        if not 0 <= int(pad) <= 8:
+            raise ValueError("Uint8ImageDataset: 0 <= pad <= 8 required")
+        self.pad, self.flip = int(pad), bool(flip)
+        self.columns = {"data": images_u8.contiguous(), "target": labels.long().contiguous()}
+        self.as_tuple = ["data", "target"]
+        self.err = torch.zeros(1, dtype=torch.int32, device=images_u8.device)
+
+    def __len__(self):
+        return int(self.columns["data"].shape[0])
+
+    def __getitem__(self, i):
+        """Row ``i`` unaugmented: (normalised fp32 image, label)."""
+        data, target = self.gather_rows(torch.as_tensor([int(i)], device=self.columns["data"].device))
+        return data[0], target[0]
+
+    def to(self, device):
+        return Uint8ImageDataset(self.columns["data"].to(device), self.columns["target"].to(device), self.mean,
+                                 self.std, self.pad, self.flip)
+
+    def _run(self, idx, out, out_target, rows, pad_target, epoch, seed, augment):
+        from ..ops.image_batch import image_batch
+
+        return image_batch(self.columns["data"], self.columns["target"], idx, out=out, out_target=out_target,
+                           rows=rows, mean=self.mean, std=self.std, pad=self.pad if augment else 0,
+                           flip=self.flip and augment, seed=seed, epoch=epoch, pad_target=pad_target, err=self.err)
+
+    def gather_rows(self, idx: torch.Tensor):
+        """Fresh unaugmented ``(fp32 batch, targets)``."""
+        return self._run(idx, None, None, None, -100, 0, 0, False)
+
+    def gather(self, idx: torch.Tensor, epoch: int = 0, seed: int = 0):
+        """Fresh ``(fp32 batch, targets)`` of ``idx``, augmented as the dataset was built."""
+        return self._run(idx, None, None, None, -100, epoch, seed, True)
+
+    def gather_into(self, idx: torch.Tensor, data_out: torch.Tensor, target_out: torch.Tensor, *, pad_target: int,
+                    epoch: int = 0, seed: int = 0, augment: bool = False) -> None:
+        """Write the batch of ``idx`` into ``data_out`` / ``target_out`` in place; the rows past
+        ``len(idx)`` become zero images with ``target = pad_target``."""
+        self._run(idx, data_out, target_out, int(data_out.shape[0]), pad_target, epoch, seed, augment)
+
+    def check_errors(self) -> None:
+        if int(self.err.item()):
+            raise RuntimeError(f"image batch: a sample index was outside [0, {len(self)}) (dataset size "
+                               f"{len(self)}); that row was delivered as padding")
 
 
 def _cifar_images(labels: torch.Tensor, base: torch.Tensor, noise: float, g: torch.Generator) -> torch.Tensor:
@@ -168,6 +246,20 @@ class DeviceLoader:
         self.drop_last = drop_last
         self.epoch = 0
         self.dataset = source  # DataLoader-compatible attribute (len(loader.dataset))
+        self._static = None
+
+    def deliver_into(self, data: Optional[torch.Tensor], target: Optional[torch.Tensor] = None,
+                     pad_target: int = -100) -> bool:
+        """Have every batch of ``data``'s row count written straight into the caller's
+        ``(data, target)`` tensors (e.g. a captured step's static inputs): the loader then yields
+        those two tensors themselves instead of fresh ones.  Batches of another size (the ragged
+        last one) are still yielded fresh.  Only datasets with ``gather_into`` can do this;
+        returns whether delivery is on.  ``deliver_into(None)`` turns it off."""
+        if data is None or not hasattr(self.ds, "gather_into"):
+            self._static = None
+            return False
+        self._static = (data, target, int(pad_target))
+        return True
 
     def __len__(self):
         n = len(self.index)
@@ -183,9 +275,20 @@ class DeviceLoader:
             order = self.index[torch.randperm(n, generator=g).to(self.device)]
         else:
             order = self.index
+        epoch = self.epoch
         self.epoch += 1
+        keyed = hasattr(self.ds, "gather_into")  # augmentation keyed by (seed, epoch, dataset index)
         for s in range(0, n, self.batch_size):
             e = s + self.batch_size
             if e > n and self.drop_last:
                 break
-            yield self.ds.gather(order[s:e])
+            idx = order[s:e]
+            if not keyed:
+                yield self.ds.gather(idx)
+            elif self._static is not None and len(idx) == self._static[0].shape[0]:
+                data, target, pad_target = self._static
+                self.ds.gather_into(idx, data, target, pad_target=pad_target, epoch=epoch, seed=self.seed,
+                                    augment=True)
+                yield data, target
+            else:
+                yield self.ds.gather(idx, epoch=epoch, seed=self.seed)

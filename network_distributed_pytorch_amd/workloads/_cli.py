@@ -9,7 +9,8 @@ default).  Additions: ``-spawn`` launches all ranks locally (127.0.0.1 rendezvou
 ``-checkpoint_dir``, ``-resume``, ``-log_file`` (``{rank}`` in the path = one file per rank),
 ``-log_every``, ``-dataset_size``, ``-check_replicas``, ``-bucket_mb``, ``-reuse_query``,
 ``-overlap``, ``-psgd_groups``, ``-emulate_world``, ``-eval_every`` / ``-eval_size`` / ``-eval_topk``
-(held-out evaluation every N epochs: loss, top-1, top-k).
+(held-out evaluation every N epochs: loss, top-1, top-k), ``-data_root`` / ``-augment`` / ``-normalize``
+(train and evaluate on the CIFAR-10 files in a directory instead of synthetic data).
 """
 from __future__ import annotations
 
@@ -57,6 +58,12 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-eval_every", type=int, default=None, help="held-out evaluation every N epochs (0 = off)")
     p.add_argument("-eval_size", type=int, default=None, help="held-out samples (cifar 10000, mlp 256, imdb: cap)")
     p.add_argument("-eval_topk", type=int, default=None, help="k of the top-k accuracy (default 5)")
+    p.add_argument("-data_root", type=str, default=None,
+                   help="directory with the CIFAR-10 files (cifar-10-batches-py or -bin); default: synthetic data")
+    p.add_argument("-augment", type=str, default=None, choices=[None, "none", "crop_flip"],
+                   help="crop_flip: random crop (pad 4) + horizontal flip of the training images (needs -data_root)")
+    p.add_argument("-normalize", type=str, default=None, choices=[None, "half", "cifar"],
+                   help="half: mean/std 0.5 (default); cifar: the dataset's channel statistics")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -69,7 +76,7 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "dataset_size": "dataset_size", "check_replicas": "check_replicas_every", "toy_steps": "toy_mlp_steps",
         "bucket_mb": "bucket_mb", "psgd_groups": "psgd_groups", "emulate_world": "emulate_world",
         "log_every": "log_every", "seq_len": "seq_len", "eval_every": "eval_every", "eval_size": "eval_size",
-        "eval_topk": "eval_topk"}
+        "eval_topk": "eval_topk", "data_root": "data_root", "augment": "augment", "normalize": "normalize"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):

@@ -2,13 +2,23 @@
 
     python tools/eval_bench.py [--batch 64 512] [--images 10000] [--passes 5] [--json-out FILE]
     python tools/eval_bench.py --arm native-eager --batch 64 --images 256 --passes 1   # one arm (kernel trace)
+    python tools/eval_bench.py --loader-batches 8 --batch 64                            # training-batch loads only
 
 Arms, all over the same synthetic held-out images and the same model:
 
 * ``native-graph``  forward + fused metrics kernel, captured once and replayed per batch;
 * ``native-eager``  the same launches issued eagerly;
 * ``aten-eager``    eager forward, then the same numbers from ATen ops with a host read per batch
-                    (``F.cross_entropy(sum)`` + ``topk`` + ``eq`` + ``any`` + ``sum`` + ``.item()``).
+                    (``F.cross_entropy(sum)`` + ``topk`` + ``eq`` + ``any`` + ``sum`` + ``.item()``);
+* ``bytes-graph`` / ``bytes-eager``  the native arms over the same images held as bytes
+                    (``Uint8ImageDataset``): each batch, its targets and the tail padding are
+                    loaded by one ``image_batch_kernel`` launch instead of gathers and copies.  The
+                    bytes are the synthetic images through the inverse of the 0.5 / 0.5
+                    normalisation, rounded: the same values up to the 8-bit quantisation.
+
+``--loader-batches N`` runs no model: a ``DeviceLoader`` delivers N full training batches into
+static tensors, from the fp32 dataset (``--loader fp32``: gather + copy) or the byte dataset
+(``--loader bytes``), for a kernel trace of the launches per training batch.
 
 Every pass ends in its host sync (``compute()`` / ``.item()``), so the host clock around a pass is
 the pass time.  Passes of the arms alternate; the median over ``--passes`` is reported together
@@ -33,9 +43,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from network_distributed_pytorch_amd import engine, ops  # noqa: E402
 from network_distributed_pytorch_amd.models import build_model  # noqa: E402
 from network_distributed_pytorch_amd.ops.metrics import classification_metrics  # noqa: E402
-from network_distributed_pytorch_amd.utils.data import SyntheticCIFAR10  # noqa: E402
+from network_distributed_pytorch_amd.utils.data import (NORMALIZE, DeviceLoader, SyntheticCIFAR10,  # noqa: E402
+                                                        Uint8ImageDataset)
 
-ARMS = ("native-graph", "native-eager", "aten-eager")
+ARMS = ("native-graph", "native-eager", "aten-eager", "bytes-graph", "bytes-eager")
+
+
+def as_bytes(ds):
+    """The fp32 images of ``ds`` (in [-1, 1], the 0.5 / 0.5 normalisation) as a byte dataset."""
+    mean, std = NORMALIZE["half"]
+    x = ds.columns["data"]
+    u8 = ((x * 0.5 + 0.5) * 255.0).round_().clamp_(0, 255).to(torch.uint8)
+    return Uint8ImageDataset(u8, ds.columns["target"], mean, std)
 
 
 def aten_metrics(logits, target, k, ignore_index=-100):
@@ -74,9 +93,11 @@ class AtenPass:
 
 def build_arms(model, val, batch, k, device, which):
     arms = {}
+    val_u8 = as_bytes(val) if any(n.startswith("bytes") for n in which) else None
     for name in which:
-        mode = "full" if name == "native-graph" else "none"
-        ev = engine.Evaluator(model, val, batch=batch, device=device, topk=k, graph_mode=mode)
+        mode = "full" if name.endswith("-graph") else "none"
+        ev = engine.Evaluator(model, val_u8 if name.startswith("bytes") else val, batch=batch, device=device, topk=k,
+                              graph_mode=mode)
         arms[name] = AtenPass(ev, k) if name == "aten-eager" else ev
     return arms
 
@@ -111,6 +132,27 @@ def bench_passes(args, device):
                             "loss": r["loss"], "top1": r["top1"], "topk": r["topk"], "n": r["n"]})
             print(json.dumps(results[-1]), flush=True)
     return results
+
+
+def run_loader(args, device):
+    """``--loader-batches`` full training batches delivered into static tensors, nothing else."""
+    batch = args.batch[0]
+    ds = SyntheticCIFAR10(batch * args.loader_batches, seed=0, device=device)
+    if args.loader == "bytes":
+        ds = as_bytes(ds)
+    loader = DeviceLoader(ds, batch, shuffle=True, seed=0, device=device)
+    static = (torch.empty(batch, 3, 32, 32, device=device), torch.empty(batch, dtype=torch.int64, device=device))
+    delivered = loader.deliver_into(*static)
+    n = 0
+    for b in loader:
+        if b[0] is not static[0]:  # what the engine does for a dataset that cannot deliver in place
+            static[0].copy_(b[0], non_blocking=True)
+            static[1].copy_(b[1], non_blocking=True)
+        n += 1
+    torch.cuda.synchronize()
+    rec = {"loader": args.loader, "batch": batch, "batches": n, "delivered_in_place": delivered}
+    print(json.dumps(rec), flush=True)
+    return [rec]
 
 
 def bench_metrics_only(args, device):
@@ -150,6 +192,8 @@ def main(argv=None):
     ap.add_argument("--num-classes", type=int, default=1000, help="the reference's ResNet head")
     ap.add_argument("--arm", choices=ARMS, default=None, help="run one arm only (kernel traces)")
     ap.add_argument("--metrics-only", action="store_true")
+    ap.add_argument("--loader-batches", type=int, default=0, help="deliver N training batches only (kernel traces)")
+    ap.add_argument("--loader", choices=("fp32", "bytes"), default="bytes")
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--json-out", default=None)
     args = ap.parse_args(argv)
@@ -157,7 +201,10 @@ def main(argv=None):
         raise SystemExit("eval_bench: no HIP device (a timing needs the GPU)")
     assert ops.native_available(), "native extension missing"
     device = torch.device("cuda", 0)
-    results = bench_metrics_only(args, device) if args.metrics_only else bench_passes(args, device)
+    if args.loader_batches:
+        results = run_loader(args, device)
+    else:
+        results = bench_metrics_only(args, device) if args.metrics_only else bench_passes(args, device)
     if args.json_out:
         with open(args.json_out, "w") as f:
             json.dump(results, f, indent=1)
