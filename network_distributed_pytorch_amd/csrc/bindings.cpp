@@ -275,10 +275,18 @@ void psgd_orth(torch::Tensor geom, torch::Tensor items, torch::Tensor p, double 
   check_launch("launch_psgd_orth");
 }
 
+// the optimiser's device block [lr, weight_decay, 0, 0] (csrc/hyper.h); None = by-value lr, no decay
+const float* hyper_ptr(const c10::optional<torch::Tensor>& hyper) {
+  if (!hyper.has_value()) return nullptr;
+  check_f32(*hyper, "hyper");
+  TORCH_CHECK(hyper->numel() >= 4, "hyper: [lr, weight_decay, 0, 0]");
+  return hyper->data_ptr<float>();
+}
+
 void psgd_update(torch::Tensor geom, torch::Tensor ptrs, torch::Tensor items, torch::Tensor p_hat,
                  torch::Tensor q_sum, double q_div, c10::optional<torch::Tensor> q_warm, int mode,
                  double lr, double momentum, int max_rank, c10::optional<torch::Tensor> p_prev,
-                 OptT r1_buf, double r1_div, OptT r1_mom, OptT r1_x, OptT r1_g) {
+                 OptT r1_buf, double r1_div, OptT r1_mom, OptT r1_x, OptT r1_g, OptT hyper) {
   check_dev(geom, "geom"); check_dev(ptrs, "ptrs"); check_dev(items, "items");
   check_f32(p_hat, "p_hat"); check_f32(q_sum, "q_sum");
   TORCH_CHECK(mode >= 0 && mode <= 3, "psgd_update: mode 0..3");
@@ -310,12 +318,13 @@ void psgd_update(torch::Tensor geom, torch::Tensor ptrs, torch::Tensor items, to
                           reinterpret_cast<const UItem*>(items.data_ptr()),
                           (int)n_of(items, sizeof(UItem)), p_hat.data_ptr<float>(),
                           q_sum.data_ptr<float>(), (float)q_div, qw, mode, (float)lr,
-                          (float)momentum, max_rank, cur_stream(), pp, r1);
+                          (float)momentum, max_rank, cur_stream(), pp, r1, hyper_ptr(hyper));
   check_launch("launch_psgd_update");
 }
 
 void rank1_step(torch::Tensor buf, double div, torch::Tensor mom, torch::Tensor x,
-                c10::optional<torch::Tensor> g, double lr, double momentum) {
+                c10::optional<torch::Tensor> g, double lr, double momentum,
+                c10::optional<torch::Tensor> hyper) {
   check_f32(buf, "buf"); check_f32(mom, "mom"); check_f32(x, "x");
   TORCH_CHECK(buf.numel() == mom.numel() && buf.numel() == x.numel(), "rank1_step size mismatch");
   float* gp = nullptr;
@@ -326,7 +335,7 @@ void rank1_step(torch::Tensor buf, double div, torch::Tensor mom, torch::Tensor 
   }
   ndp::launch_rank1_step(buf.data_ptr<float>(), (float)div, mom.data_ptr<float>(),
                          x.data_ptr<float>(), gp, buf.numel(), (float)lr, (float)momentum,
-                         cur_stream());
+                         cur_stream(), hyper_ptr(hyper));
   check_launch("launch_rank1_step");
 }
 
@@ -340,11 +349,11 @@ void seg_reduce(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, 
 }
 
 void sgd_momentum(torch::Tensor x, torch::Tensor g, torch::Tensor buf, double lr, double mu,
-                  double div) {
+                  double div, c10::optional<torch::Tensor> hyper) {
   check_f32(x, "x"); check_f32(g, "g"); check_f32(buf, "buf");
   TORCH_CHECK(x.numel() == g.numel() && x.numel() == buf.numel(), "sgd_momentum size mismatch");
   ndp::launch_sgd_momentum(x.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(),
-                           x.numel(), (float)lr, (float)mu, (float)div, cur_stream());
+                           x.numel(), (float)lr, (float)mu, (float)div, cur_stream(), hyper_ptr(hyper));
   check_launch("launch_sgd_momentum");
 }
 
@@ -1505,10 +1514,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("psgd_update", &psgd_update, py::arg("geom"), py::arg("ptrs"), py::arg("items"), py::arg("p_hat"),
         py::arg("q_sum"), py::arg("q_div"), py::arg("q_warm"), py::arg("mode"), py::arg("lr"), py::arg("momentum"),
         py::arg("max_rank"), py::arg("p_prev") = c10::optional<torch::Tensor>(), py::arg("r1_buf") = OptT(),
-        py::arg("r1_div") = 1.0, py::arg("r1_mom") = OptT(), py::arg("r1_x") = OptT(), py::arg("r1_g") = OptT());
-  m.def("rank1_step", &rank1_step);
+        py::arg("r1_div") = 1.0, py::arg("r1_mom") = OptT(), py::arg("r1_x") = OptT(), py::arg("r1_g") = OptT(),
+        py::arg("hyper") = OptT());
+  m.def("rank1_step", &rank1_step, py::arg("buf"), py::arg("div"), py::arg("mom"), py::arg("x"), py::arg("g"),
+        py::arg("lr"), py::arg("momentum"), py::arg("hyper") = OptT());
   m.def("seg_reduce", &seg_reduce);
-  m.def("sgd_momentum", &sgd_momentum);
+  m.def("sgd_momentum", &sgd_momentum, py::arg("x"), py::arg("g"), py::arg("buf"), py::arg("lr"), py::arg("mu"),
+        py::arg("div"), py::arg("hyper") = OptT());
   m.def("add", &add);
   m.def("delay_ns", &delay_ns);
   m.def("bn_fwd", &bn_fwd, py::arg("x"), py::arg("res"), py::arg("y"), py::arg("gamma"), py::arg("beta"),

@@ -6,12 +6,15 @@
 //      - deterministic split-K sum of the PowerSGD P / Q partial slabs
 //    The workgroup -> entry map is a block-prefix table searched in scalar registers.
 //  * sgd_momentum: dense-arm torch.optim.SGD(momentum) step with the all-reduce mean
-//    folded in (ddp_guide_cifar10/ddp_init.py:57-62,111,125) over the flat gradient arena.
+//    folded in (ddp_guide_cifar10/ddp_init.py:57-62,111,125) over the flat gradient arena;
+//    with the optimiser's hyper block (hyper.h) lr comes from the device and g/N + wd x replaces
+//    g/N: torch.optim.SGD(momentum, weight_decay) under a schedule, also in a captured step.
 //  * add: EF pack  send = g + e  (ddp_powersgd_guide_cifar10/ddp_init.py:156-157).
 //  * delay_ns: wall-clock spin used by the link emulator to pace collectives to a
 //    1/10/100 Gb budget on the stream (reference README.md:2 experiments).
 //  * checksum: deterministic fp64 sum of a flat buffer (cross-rank divergence detector).
 #include <hip/hip_runtime.h>
+#include "hyper.h"
 #include "ndp_kernels.h"
 #include "seg_block.h"
 
@@ -37,7 +40,10 @@ __global__ __launch_bounds__(256) void sgd_momentum_vec_kernel(float* __restrict
                                                                const float* __restrict__ g,
                                                                float* __restrict__ buf,
                                                                int64_t n4, float lr, float mu,
-                                                               float div) {
+                                                               float div, const float* __restrict__ hyper) {
+  const Hyper hp = load_hyper(hyper, lr);
+  lr = hp.lr;
+  const float wd = hp.wd;
   const bool scale = div != 1.0f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
        i += (int64_t)gridDim.x * blockDim.x) {
@@ -47,6 +53,7 @@ __global__ __launch_bounds__(256) void sgd_momentum_vec_kernel(float* __restrict
     if (scale) gg = gg / div;
     f32x4 b = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(buf + 4 * i));
     f32x4 xx = ld4(x + 4 * i);
+    gg = decayed(gg, xx, wd);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       b[j] = __fadd_rn(__fmul_rn(b[j], mu), gg[j]);
@@ -61,14 +68,20 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ x
                                                            const float* __restrict__ g,
                                                            float* __restrict__ buf,
                                                            int64_t start, int64_t n, float lr,
-                                                           float mu, float div) {
+                                                           float mu, float div,
+                                                           const float* __restrict__ hyper) {
+  const Hyper hp = load_hyper(hyper, lr);
+  lr = hp.lr;
+  const float wd = hp.wd;
   for (int64_t i = start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float gg = g[i];
     if (div != 1.0f) gg = gg / div;
+    const float xi = x[i];
+    gg = decayed(gg, xi, wd);
     const float b = __fadd_rn(__fmul_rn(buf[i], mu), gg);
     buf[i] = b;
-    x[i] = fmaf(-lr, b, x[i]);
+    x[i] = fmaf(-lr, b, xi);
   }
 }
 
@@ -191,19 +204,19 @@ void launch_seg_reduce(const SegEntry* entries, const int64_t* block_prefix, int
 }
 
 void launch_sgd_momentum(float* x, const float* g, float* buf, int64_t n, float lr, float mu,
-                         float div, hipStream_t s) {
+                         float div, hipStream_t s, const float* hyper) {
   if (n <= 0) return;
   int64_t done = 0;
   if (aligned16(x) && aligned16(g) && aligned16(buf)) {
     const int64_t n4 = n / 4;
     if (n4 > 0)
       hipLaunchKernelGGL(sgd_momentum_vec_kernel, dim3(grid_for(n4)), dim3(256), 0, s, x, g, buf,
-                         n4, lr, mu, div);
+                         n4, lr, mu, div, hyper);
     done = n4 * 4;
   }
   if (done < n)
     hipLaunchKernelGGL(sgd_momentum_kernel, dim3(grid_for(n - done)), dim3(256), 0, s, x, g, buf,
-                       done, n, lr, mu, div);
+                       done, n, lr, mu, div, hyper);
 }
 
 void launch_add(const float* a, const float* b, float* out, int64_t n, hipStream_t s) {

@@ -142,21 +142,26 @@ constexpr unsigned kErrDeadTapGrad = 2u;
 // mode 0 = api (out/mem), 1 = engine (EF + momentum + SGD), 2 = engine + write grad,
 // 3 = e -= p_hat q_sum^T / q_div only (materialise the lazy error, rank <= kUWideMaxRank);
 // p_prev (modes 1 / 2, rank <= kUWideMaxRank): lazy error feedback — e is not written, the
-// P-hat rows are kept in p_prev for the next P pass
+// P-hat rows are kept in p_prev for the next P pass.
+// hyper (every update launcher below; hyper.h): the device block [lr, weight_decay, 0, 0] the
+// kernels read instead of the by-value lr — nullptr keeps lr by value and weight_decay = 0.
+// With d = (wd != 0 ? fmaf(wd, x, out) : out):  m = lam*m + d;  x -= lr*(d + m)
 void launch_psgd_update(const MatGeom* geom, const MatPtrs* ptrs, const UItem* items,
                         int n_items, const float* p_hat, const float* q_sum, float q_div,
                         float* q_warm, int mode, float lr, float momentum, int max_rank,
-                        hipStream_t s, float* p_prev = nullptr, R1Step r1 = R1Step{});
+                        hipStream_t s, float* p_prev = nullptr, R1Step r1 = R1Step{},
+                        const float* hyper = nullptr);
 // rank-1 (<=1-D) group of the fused engine: out = buf/div; m = lam*m + out; x -= lr*(out+m)
 void launch_rank1_step(const float* buf, float div, float* mom, float* x, float* g,
-                       int64_t n, float lr, float momentum, hipStream_t s);
+                       int64_t n, float lr, float momentum, hipStream_t s, const float* hyper = nullptr);
 
 // ---- launchers (multitensor.hip) -----------------------------------------------
 void launch_seg_reduce(const SegEntry* entries, const int64_t* block_prefix, int n_entries,
                        int64_t n_blocks, hipStream_t s);
-// dense arm: b = mu*b + g/div ; x -= lr*b   (torch.optim.SGD(momentum) with zero-init buf)
+// dense arm: b = mu*b + g/div ; x -= lr*b   (torch.optim.SGD(momentum) with zero-init buf);
+// with a hyper block: b = mu*b + (g/div + wd*x), torch.optim.SGD(momentum, weight_decay)
 void launch_sgd_momentum(float* x, const float* g, float* buf, int64_t n, float lr, float mu,
-                         float div, hipStream_t s);
+                         float div, hipStream_t s, const float* hyper = nullptr);
 // out = a + b  (EF pack: send = g + e)
 void launch_add(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
 // spin the stream for `ns` nanoseconds of wall time (link-emulation pacing)

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include "hyper.h"
 #include "ndp_kernels.h"
 #include "seg_block.h"
 
@@ -712,12 +713,19 @@ __global__ __launch_bounds__(256) void psgd_q_kernel(const MatGeom* __restrict__
 // computed as D = Qs * Phat^T on MFMA so each lane holds 4 consecutive b of one row a
 // (16-B accesses of e / m / x).  Qs = Q_sum / q_div (reducer.py:147).  One designated
 // wave per column block also writes Qs into the warm-start buffer (reducer.py:101-111).
+// hyper (hyper.h; this kernel, the wide one below and rank1_step_kernel): the optimiser's device
+// block [lr, weight_decay, 0, 0], read instead of the by-value lr so that a captured step follows
+// a schedule; nullptr = lr by value, no decay.  The decay joins the decompressed value after the
+// error memory is formed:  d = wd != 0 ? fmaf(wd, x, out) : out;  m = lam m + d;  x -= lr (d + m).
 // ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void psgd_update_kernel(
     const MatGeom* __restrict__ geom, const MatPtrs* __restrict__ ptrs,
     const UItem* __restrict__ items, const float* __restrict__ p_hat,
     const float* __restrict__ q_sum, float q_div, float* __restrict__ q_warm, int mode,
-    float lr, float momentum) {
+    float lr, float momentum, const float* __restrict__ hyper) {
+  const Hyper hp = load_hyper(hyper, lr);
+  lr = hp.lr;
+  const float wd = hp.wd;
   const UItem it = items[blockIdx.x];
   const MatGeom g = geom[it.mat];
   const GPtrs pt = gptrs(ptrs[it.mat]);
@@ -782,9 +790,10 @@ __global__ __launch_bounds__(256) void psgd_update_kernel(
         f32x4 mm = Mm[t];
         f32x4 xx = Xv[t];
         st4(pt.e + ro + b, M - o);
+        const f32x4 d = decayed(o, xx, wd);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mm[j] = __fadd_rn(__fmul_rn(mm[j], momentum), o[j]);
-        const f32x4 up = o + mm;
+        for (int j = 0; j < 4; ++j) mm[j] = __fadd_rn(__fmul_rn(mm[j], momentum), d[j]);
+        const f32x4 up = d + mm;
 #pragma unroll
         for (int j = 0; j < 4; ++j) xx[j] = fmaf(-lr, up[j], xx[j]);
         st4(pt.mom + ro + b, mm);
@@ -802,10 +811,12 @@ __global__ __launch_bounds__(256) void psgd_update_kernel(
           pt.mem[k] = M - o[j];
         } else {
           pt.e[k] = M - o[j];
-          const float mm = __fadd_rn(__fmul_rn(pt.mom[k], momentum), o[j]);
+          const float xk = pt.x[k];
+          const float d = decayed(o[j], xk, wd);
+          const float mm = __fadd_rn(__fmul_rn(pt.mom[k], momentum), d);
           pt.mom[k] = mm;
-          const float up = o[j] + mm;
-          pt.x[k] = fmaf(-lr, up, pt.x[k]);
+          const float up = d + mm;
+          pt.x[k] = fmaf(-lr, up, xk);
           if (mode == 2) pt.g[k] = up;
         }
       }
@@ -941,15 +952,19 @@ void psgd_update_wide_kernel(
     const MatGeom* __restrict__ geom, const MatPtrs* __restrict__ ptrs,
     const UItem* __restrict__ items, const float* __restrict__ p_hat,
     const float* __restrict__ q_sum, float q_div, float* __restrict__ q_warm, int mode,
-    float lr, float momentum, float* __restrict__ p_prev, R1Step r1) {
+    float lr, float momentum, float* __restrict__ p_prev, R1Step r1, const float* __restrict__ hyper) {
+  const Hyper hp = load_hyper(hyper, lr);
+  lr = hp.lr;
+  const float wd = hp.wd;
   if ((int)blockIdx.x >= r1.n_items) {  // the rank-1 group's step, same launch (rank1_step_kernel)
     const int64_t stride = (int64_t)(gridDim.x - r1.n_items) * 256;
     for (int64_t k = (int64_t)(blockIdx.x - r1.n_items) * 256 + threadIdx.x; k < r1.n; k += stride) {
-      const float o = r1.buf[k] / r1.div;
-      const float mm = __fadd_rn(__fmul_rn(r1.mom[k], momentum), o);
+      const float xk = r1.x[k];
+      const float d = decayed(r1.buf[k] / r1.div, xk, wd);
+      const float mm = __fadd_rn(__fmul_rn(r1.mom[k], momentum), d);
       r1.mom[k] = mm;
-      const float up = o + mm;
-      r1.x[k] = fmaf(-lr, up, r1.x[k]);
+      const float up = d + mm;
+      r1.x[k] = fmaf(-lr, up, xk);
       if (r1.g) r1.g[k] = up;
     }
     return;
@@ -1055,9 +1070,10 @@ void psgd_update_wide_kernel(
         f32x4 mm = Mm[i];
         f32x4 xx = Xv[i];
         if (!lazy) st4(pt.e + ro + b, M - o);
+        const f32x4 d = decayed(o, xx, wd);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mm[j] = __fadd_rn(__fmul_rn(mm[j], momentum), o[j]);
-        const f32x4 up = o + mm;
+        for (int j = 0; j < 4; ++j) mm[j] = __fadd_rn(__fmul_rn(mm[j], momentum), d[j]);
+        const f32x4 up = d + mm;
 #pragma unroll
         for (int j = 0; j < 4; ++j) xx[j] = fmaf(-lr, up[j], xx[j]);
         if constexpr (NT >= 2) __builtin_nontemporal_store(mm, reinterpret_cast<f32x4 NDP_GLOBAL*>(pt.mom + ro + b));
@@ -1078,10 +1094,12 @@ void psgd_update_wide_kernel(
           pt.e[k] = M - o[j];
         } else {
           if (!lazy) pt.e[k] = M - o[j];
-          const float mm = __fadd_rn(__fmul_rn(pt.mom[k], momentum), o[j]);
+          const float xk = pt.x[k];
+          const float d = decayed(o[j], xk, wd);
+          const float mm = __fadd_rn(__fmul_rn(pt.mom[k], momentum), d);
           pt.mom[k] = mm;
-          const float up = o[j] + mm;
-          pt.x[k] = fmaf(-lr, up, pt.x[k]);
+          const float up = d + mm;
+          pt.x[k] = fmaf(-lr, up, xk);
           if (mode == 2) pt.g[k] = up;
         }
       }
@@ -1093,14 +1111,19 @@ __global__ __launch_bounds__(256) void rank1_step_kernel(const float* __restrict
                                                          float* __restrict__ mom,
                                                          float* __restrict__ x,
                                                          float* __restrict__ g, int64_t n,
-                                                         float lr, float momentum) {
+                                                         float lr, float momentum,
+                                                         const float* __restrict__ hyper) {
+  const Hyper hp = load_hyper(hyper, lr);
+  lr = hp.lr;
+  const float wd = hp.wd;
   for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n;
        k += (int64_t)gridDim.x * blockDim.x) {
-    const float o = buf[k] / div;
-    const float mm = __fadd_rn(__fmul_rn(mom[k], momentum), o);
+    const float xk = x[k];
+    const float d = decayed(buf[k] / div, xk, wd);
+    const float mm = __fadd_rn(__fmul_rn(mom[k], momentum), d);
     mom[k] = mm;
-    const float up = o + mm;
-    x[k] = fmaf(-lr, up, x[k]);
+    const float up = d + mm;
+    x[k] = fmaf(-lr, up, xk);
     if (g) g[k] = up;
   }
 }
@@ -1183,7 +1206,7 @@ void launch_psgd_q(const MatGeom* geom, const MatPtrs* ptrs, const QItem* items,
 void launch_psgd_update(const MatGeom* geom, const MatPtrs* ptrs, const UItem* items,
                         int n_items, const float* p_hat, const float* q_sum, float q_div,
                         float* q_warm, int mode, float lr, float momentum, int max_rank,
-                        hipStream_t s, float* p_prev, R1Step r1) {
+                        hipStream_t s, float* p_prev, R1Step r1, const float* hyper) {
   r1.n_items = n_items;
   int64_t r1_blocks = r1.n > 0 ? std::min<int64_t>((r1.n + 255) / 256, 512) : 0;
   if (n_items <= 0 && r1_blocks <= 0) return;
@@ -1194,28 +1217,28 @@ void launch_psgd_update(const MatGeom* geom, const MatPtrs* ptrs, const UItem* i
   // batch 64 0.8245 / 0.8233 -> 0.7896 / 0.7855 ms, batch 512 unchanged (1.4905 / 1.4930)
   if (max_rank <= 4)
     hipLaunchKernelGGL((psgd_update_wide_kernel<4, 2>), dim3(grid), dim3(256), 0, s, geom, ptrs,
-                       items, p_hat, q_sum, q_div, q_warm, mode, lr, momentum, p_prev, r1);
+                       items, p_hat, q_sum, q_div, q_warm, mode, lr, momentum, p_prev, r1, hyper);
   else if (max_rank <= 8)
     hipLaunchKernelGGL((psgd_update_wide_kernel<8, 2>), dim3(grid), dim3(256), 0, s, geom, ptrs,
-                       items, p_hat, q_sum, q_div, q_warm, mode, lr, momentum, p_prev, r1);
+                       items, p_hat, q_sum, q_div, q_warm, mode, lr, momentum, p_prev, r1, hyper);
   else if (max_rank <= kUWideMaxRank)
     hipLaunchKernelGGL(psgd_update_wide_kernel<kUWideMaxRank>, dim3(grid), dim3(256), 0, s,
-                       geom, ptrs, items, p_hat, q_sum, q_div, q_warm, mode, lr, momentum, p_prev, r1);
+                       geom, ptrs, items, p_hat, q_sum, q_div, q_warm, mode, lr, momentum, p_prev, r1, hyper);
   else {
     if (n_items > 0)
       hipLaunchKernelGGL(psgd_update_kernel, dim3(n_items), dim3(256), 0, s, geom, ptrs, items,
-                         p_hat, q_sum, q_div, q_warm, mode, lr, momentum);
-    if (r1.n > 0) launch_rank1_step(r1.buf, r1.div, r1.mom, r1.x, r1.g, r1.n, lr, momentum, s);
+                         p_hat, q_sum, q_div, q_warm, mode, lr, momentum, hyper);
+    if (r1.n > 0) launch_rank1_step(r1.buf, r1.div, r1.mom, r1.x, r1.g, r1.n, lr, momentum, s, hyper);
   }
 }
 
 void launch_rank1_step(const float* buf, float div, float* mom, float* x, float* g, int64_t n,
-                       float lr, float momentum, hipStream_t s) {
+                       float lr, float momentum, hipStream_t s, const float* hyper) {
   if (n <= 0) return;
   int64_t blocks = (n + 255) / 256;
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(rank1_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, buf, div, mom,
-                     x, g, n, lr, momentum);
+                     x, g, n, lr, momentum, hyper);
 }
 
 }  // namespace ndp

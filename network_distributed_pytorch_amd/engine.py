@@ -17,7 +17,9 @@ IMDb split (Q2), a private PowerSGD RNG (Q1), configurable ``n_workers`` / batch
 replica-divergence checks, link emulation, hipGraph step capture, held-out evaluation
 (``eval_every``: :func:`evaluate`, the fused loss / top-1 / top-k pass of ops/metrics.py), and
 training / evaluating on the CIFAR-10 files of ``data_root`` (utils/cifar.py), held as bytes and
-turned into batches by one launch each (ops/image_batch.py); ``data_root=None`` = synthetic data.
+turned into batches by one launch each (ops/image_batch.py); ``data_root=None`` = synthetic data;
+a learning-rate schedule (utils/schedule.py) and L2 weight decay, handed to the gradient sync before
+every step (``sync.set_hyper``), which on the native engines reaches the captured step too.
 """
 from __future__ import annotations
 
@@ -38,13 +40,14 @@ from .models import build_model
 from .parallel.comm import LINK_PRESETS, Communicator
 from .parallel.trainer import build_grad_sync
 from .utils.checkpoint import load_checkpoint, save_checkpoint
-from .utils.config import validate_config
+from .utils.config import ConfigError, validate_config
 from .utils.cifar import load_cifar10
 from .utils.data import (NORMALIZE, DeviceLoader, SyntheticCIFAR10, SyntheticIMDb, SyntheticMLPData,
                          TensorDictDataset, Uint8ImageDataset, train_val_split)
 from .utils.divergence import ReplicaChecker
 from .utils.metrics import JsonlLogger, PhaseTimer, print_epoch, print_eval
 from .utils.partition_helper import DataPartitioner
+from .utils.schedule import LrSchedule
 
 __all__ = ["setup", "run_task", "cleanup", "device_for", "default_config", "evaluate", "Evaluator"]
 
@@ -67,6 +70,8 @@ def default_config(**over) -> Dict[str, Any]:
         eval_every=0, eval_size=None, eval_topk=5,
         # CIFAR-10 from files (None = synthetic data), training augmentation, normalisation
         data_root=None, augment="none", normalize="half",
+        # learning-rate schedule (utils/schedule.py) and L2 weight decay
+        lr_schedule="constant", lr_warmup_steps=0, lr_min=0.0, lr_milestones="", lr_gamma=0.1, weight_decay=0.0,
     )
     cfg.update(over)
     return cfg
@@ -427,6 +432,18 @@ def run_task(config) -> Dict[str, Any]:
     loader.set_epoch(start_epoch)
     num_batches = math.ceil(len(part) / float(bsz))  # reference: ceil(len(partition) / bsz)
     health_every = int(config.get("check_health_every") or 0)
+    # learning-rate schedule and weight decay: a pure function of the global step, which continues
+    # across epochs and a resume.  With the defaults nothing below is called, logged or uploaded.
+    steps_per_epoch = min(num_batches, config.get("max_steps_per_epoch") or num_batches)
+    try:
+        schedule = LrSchedule.from_config(config, steps_per_epoch)  # checks lr_warmup_steps < total steps
+    except ValueError as exc:
+        raise ConfigError(str(exc)) from None
+    weight_decay = float(config.get("weight_decay") or 0.0)
+    hyper_on = schedule.varies or weight_decay != 0.0
+    lr_now = None
+    if hyper_on and hasattr(sync, "plan_hyper"):  # the pinned source rows of the whole run, written once
+        sync.plan_hyper((schedule.lr_at(s), weight_decay) for s in range(step, schedule.T))
 
     timer = PhaseTimer() if (config.get("trace_phases") and runner is None) else None
     eval_every = int(config.get("eval_every") or 0)
@@ -447,6 +464,9 @@ def run_task(config) -> Dict[str, Any]:
         for batch in loader:
             if config.get("max_steps_per_epoch") and i >= config["max_steps_per_epoch"]:
                 break
+            if hyper_on:  # before a replay, the ragged eager step and the plain eager step alike
+                lr_now = schedule.lr_at(step)
+                sync.set_hyper(lr_now, weight_decay)
             if runner is not None and "batch" in static and not _same_shape(static["batch"], batch):
                 runner.join()  # ragged batch: eager step, ordered after the last replay
                 sync.zero_grad()
@@ -510,7 +530,8 @@ def run_task(config) -> Dict[str, Any]:
                            wire_bytes=(comm.stats.wire_bytes - wire_prev) / n
                            if runner is None or graph_mode == "piecewise" else
                            _ring_wire(getattr(sync, "bytes_per_step", 0) or 0, comm.paced_world),
-                           bytes_per_step=getattr(sync, "bytes_per_step", None))
+                           bytes_per_step=getattr(sync, "bytes_per_step", None),
+                           **({"lr": lr_now} if hyper_on else {}))
                 last_log = (now, comm.stats.payload_bytes, comm.stats.wire_bytes, step)
         if runner is not None:
             runner.join()  # parameters / sync state are read below (checks, checkpoint)
@@ -527,7 +548,7 @@ def run_task(config) -> Dict[str, Any]:
             print(">>>>> Rank ", rank, ", epoch ", epoch, " Finished...\n", flush=True)
         logger.log(kind="epoch", epoch=epoch, mean_loss=mean, steps=i, num_batches=num_batches,
                    bytes_per_step=getattr(sync, "bytes_per_step", None), comm=comm.stats.as_dict(),
-                   phase_ms=timer.summary() if timer is not None else None)
+                   phase_ms=timer.summary() if timer is not None else None, **({"lr": lr_now} if hyper_on else {}))
         if config.get("checkpoint_dir"):
             save_checkpoint(os.path.join(config["checkpoint_dir"], "last.pt"), model, sync, epoch=epoch, step=step,
                             rank=rank, world=world)
@@ -558,6 +579,9 @@ def run_task(config) -> Dict[str, Any]:
                "bytes_per_step": getattr(sync, "bytes_per_step", None), "comm": comm.stats.as_dict(),
                "comm_backend": comm.backend, "world_size": world, "per_rank_batch": bsz, "graph_mode": graph_mode,
                "param_checksum": float(flat.double().sum().item())}
+    if hyper_on:
+        summary["lr_schedule"] = schedule.schedule
+        summary["weight_decay"] = weight_decay
     if eval_every:
         summary["eval"] = evals
         summary["eval_s"] = eval_s

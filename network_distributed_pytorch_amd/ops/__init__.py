@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import contextlib
 
-from typing import Sequence
+from typing import Optional, Sequence
 
 import torch
 
@@ -46,16 +46,23 @@ def add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
 
 
 def sgd_momentum_(x: torch.Tensor, g: torch.Tensor, buf: torch.Tensor, lr: float, momentum: float,
-                  div: float = 1.0) -> None:
-    """Flat-arena ``torch.optim.SGD(momentum)`` step with the all-reduce mean folded in.
+                  div: float = 1.0, weight_decay: float = 0.0, hyper: Optional[torch.Tensor] = None) -> None:
+    """Flat-arena ``torch.optim.SGD(momentum, weight_decay)`` step with the all-reduce mean folded in.
 
     Matches ``b = mu*b + g/div ; x -= lr*b`` with a zero-initialised buffer, which is the
-    reference's first-step ``buf = g.clone()`` (ddp_guide_cifar10/ddp_init.py:111,125).
+    reference's first-step ``buf = g.clone()`` (ddp_guide_cifar10/ddp_init.py:111,125); with a
+    decay ``g/div`` becomes ``g/div + wd*x``.  On the device ``lr`` goes by value and there is no
+    decay unless ``hyper``, the optimiser's device block ``[lr, weight_decay, 0, 0]`` (ops/hyper.py),
+    is given: then the kernel reads both from it (``lr`` / ``weight_decay`` here are ignored).
     """
     if x.is_cuda:
-        ext().sgd_momentum(x, g, buf, float(lr), float(momentum), float(div))
+        if hyper is None and weight_decay != 0.0:
+            raise ValueError("sgd_momentum_: weight decay on the device goes through the hyper block")
+        ext().sgd_momentum(x, g, buf, float(lr), float(momentum), float(div), hyper)
     else:
         gg = g / div if div != 1.0 else g
+        if weight_decay != 0.0:
+            gg = gg.add(x, alpha=weight_decay)
         buf.mul_(momentum).add_(gg)
         x.add_(buf, alpha=-lr)
 

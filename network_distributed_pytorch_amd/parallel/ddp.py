@@ -27,14 +27,19 @@ backward-overlapped MI355X arm.
   backward.  Modelled, not measured at N > 1 (no multi-GPU box in the build loop); the
   knob is ``bucket_mb`` / ``-bucket_mb`` / ``--bucket-mb``.
   Parameters are broadcast from rank 0 at construction (quirk Q4 fixed).
+  ``set_hyper(lr, weight_decay)`` changes the learning rate and the L2 weight decay of later
+  steps, captured replays included: on a device the SGD kernel then reads both from the
+  optimiser's 16-byte block (ops/hyper.py) instead of taking ``lr`` by value.
 """
 from __future__ import annotations
 
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from ..ops import SegPlan, capturing, gradarena, gradfinish, sgd_momentum_
+from ..ops.hyper import HyperBlock
 from .comm import Communicator, all_reduce, world_size
 
 __all__ = ["average_gradients", "BucketedDataParallel", "DEFAULT_BUCKET_MB"]
@@ -61,14 +66,21 @@ def average_gradients(model: torch.nn.Module, comm: Optional[Communicator] = Non
 class BucketedDataParallel:
     def __init__(self, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                  momentum: float = 0.9, bucket_mb: Optional[float] = None, broadcast_params: bool = True,
-                 overlap: Optional[bool] = None):
+                 overlap: Optional[bool] = None, weight_decay: float = 0.0):
+        assert weight_decay >= 0, "weight_decay >= 0"
         bucket_mb = DEFAULT_BUCKET_MB if bucket_mb is None else float(bucket_mb)
         self.model = model
         self.comm = comm if comm is not None else Communicator()
         self.lr = float(lr)
         self.momentum = float(momentum)
+        self.weight_decay = float(weight_decay)
         self.params: List[torch.nn.Parameter] = [p for p in model.parameters() if p.requires_grad]
         self.device = self.params[0].device
+        # device block [lr, weight_decay, 0, 0], allocated before any capture; the SGD kernel reads it
+        # once set_hyper() was called or a decay is on, else lr goes by value
+        self.hyper = HyperBlock(self.device, self.lr, self.weight_decay) if self.device.type == "cuda" else None
+        self._hyper_on = self.hyper is not None and self.weight_decay != 0.0
+        self._captured_by_value = False
         order = list(reversed(self.params))
         offs, o = {}, 0
         for p in order:
@@ -210,12 +222,56 @@ class BucketedDataParallel:
                 w.wait()
             self._works[b] = None
 
+    def _sgd(self):
+        """This step's fused SGD launch, bound to the current lr / decay (or to the device block)."""
+        lr, mu, wd, n = self.lr, self.momentum, self.weight_decay, float(self.comm.world_size)
+        hy = self.hyper.dev if self._hyper_on else None
+        if capturing() and hy is None:
+            self._captured_by_value = True
+        return lambda: sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+
+    def plan_hyper(self, pairs):
+        """Write the pinned source rows of the coming steps' ``(lr, weight_decay)`` ahead of time."""
+        if self.hyper is not None:
+            self.hyper.prefill(pairs)
+
+    def set_hyper(self, lr: float, weight_decay: Optional[float] = None):
+        """Learning rate and L2 weight decay of the steps from now on (fp32 values), captured replays
+        included; never called inside a capture.  On a device: one 16-byte async copy into the block,
+        none when neither value changed.
+
+        Ordering of the copy (after the previous step's SGD launch, before this step's): in stream
+        mode the SGD launch runs on the communicator's side stream — replayed, at the tail of the
+        comm graph, which is not joined with the current stream between steps — so the copy goes on
+        the side stream, behind it in stream order.  Otherwise the whole step is on the current
+        stream and so is the copy."""
+        wd = self.weight_decay if weight_decay is None else float(weight_decay)
+        assert wd >= 0, "weight_decay >= 0"
+        lr, wd = float(np.float32(lr)), float(np.float32(wd))
+        if self._captured_by_value and (lr != float(np.float32(self.lr)) or wd != 0.0):
+            raise RuntimeError("dense arm: the captured step holds lr by value; call set_hyper() before capturing")
+        self.lr, self.weight_decay = lr, wd
+        if self.hyper is not None:
+            self._hyper_on = True
+            self._upload_hyper()
+
+    def _upload_hyper(self, force: bool = False):
+        assert not capturing(), "set_hyper() inside a graph capture"
+        if self.stream_mode:
+            with self.comm.on_side():
+                self.hyper.set(self.lr, self.weight_decay, force)
+        else:
+            self.hyper.set(self.lr, self.weight_decay, force)
+
     @torch.no_grad()
     def phase_sgd(self):
-        sgd_momentum_(self.x, self.g, self.buf, self.lr, self.momentum, float(self.comm.world_size))
+        self._sgd()()
         self.count_step()
 
     def phases(self):
+        if self.stream_mode and self.hyper is not None:  # the block's uploads change stream with the SGD launch
+            self.comm.fork()
+            self.comm.join()
         self.overlap = False  # piecewise capture: collectives run eagerly between segments
         self.stream_mode = False
         return [(self.phase_flatten, False), (self.comm_buckets, True), (self.phase_sgd, False)]
@@ -234,20 +290,18 @@ class BucketedDataParallel:
 
     @torch.no_grad()
     def step(self) -> int:
-        n = self.comm.world_size
         for b in range(len(self.buckets)):
             if not self._launched[b]:  # overlap disabled / unused params
                 self._launch(b)
         if self.stream_mode:
             # the fused SGD runs on the side stream too (it needs every bucket), then join
-            lr, mu = self.lr, self.momentum
-            self.comm.side_launch(lambda: sgd_momentum_(self.x, self.g, self.buf, lr, mu, float(n)))
+            self.comm.side_launch(self._sgd())
             self.comm.side_join()
         else:
             for w in self._works:
                 if w is not None:
                     w.wait()
-            sgd_momentum_(self.x, self.g, self.buf, self.lr, self.momentum, float(n))
+            self._sgd()()
         self._reset()
         self.count_step()
         return 8 * self.bytes_per_step
@@ -265,9 +319,14 @@ class BucketedDataParallel:
             self.step_count += 1
 
     def state_dict(self):
-        return {"momentum_buffer": self.buf.detach().cpu().clone(), "lr": self.lr, "momentum": self.momentum}
+        return {"momentum_buffer": self.buf.detach().cpu().clone(), "lr": self.lr, "momentum": self.momentum,
+                "weight_decay": self.weight_decay}
 
     def load_state_dict(self, sd):
         self.buf.copy_(sd["momentum_buffer"])
         self.lr = float(sd["lr"])
+        self.weight_decay = float(sd.get("weight_decay", 0.0))
         self.momentum = float(sd["momentum"])
+        if self.hyper is not None:  # the block follows the loaded values
+            self._hyper_on = self._hyper_on or self.weight_decay != 0.0
+            self._upload_hyper(force=True)

@@ -41,6 +41,7 @@ import numpy as np
 import torch
 
 from ..ops import SegPlan, capturing, ext, gradfinish, taps, upload, upload_epoch
+from ..ops.hyper import HyperBlock
 from .comm import Communicator, n_bits
 from ..knobs import fusion_on
 
@@ -516,16 +517,28 @@ class PowerSGDOptimizer:
     P-hat; the next P pass forms ``e`` element by element with the update kernel's exact
     arithmetic (csrc/powersgd.hip), so every step is bitwise the eager formula's.  :attr:`e`
     (and ``state_dict``) materialise the true error memory first.
+
+    **Hyper-parameter block** (:meth:`set_hyper`): the native optimiser owns a 16-byte device tensor
+    ``hyper = [lr, weight_decay, 0, 0]`` (ops/hyper.py, csrc/hyper.h).  Once :meth:`set_hyper` has
+    been called (or with ``weight_decay != 0``) the update kernels read both values from it, so a
+    schedule reaches a captured step: the block is overwritten between graph replays.  An
+    optimiser that never calls it passes ``lr`` by value as before, bitwise the same step.
+    ``weight_decay`` is L2 on every parameter, ``d = out + wd x`` after decompression; it never
+    enters the error memory, P, Q or the all-reduced bytes.  Dead taps acquire momentum under it,
+    so with ``weight_decay != 0`` every matrix keeps the full layout.
     """
 
     def __init__(self, params, lr: float, momentum: float = 0.9, rank: int = 4,
                  random_seed: int = 714, reuse_query: bool = True,
                  comm: Optional[Communicator] = None, write_grad: bool = False,
                  broadcast_params: bool = True, rng_compat: bool = False, eps: float = 1e-8,
-                 native: Optional[bool] = None, overlap: Optional[bool] = None, groups: Optional[int] = None):
+                 native: Optional[bool] = None, overlap: Optional[bool] = None, groups: Optional[int] = None,
+                 weight_decay: float = 0.0):
         self.params: List[torch.nn.Parameter] = [p for p in params]
         assert self.params, "no parameters"
+        assert weight_decay >= 0, "weight_decay >= 0"
         self.lr = float(lr)
+        self.weight_decay = float(weight_decay)
         self.momentum = float(momentum)
         self.rank = int(rank)
         self.reuse_query = reuse_query
@@ -577,6 +590,11 @@ class PowerSGDOptimizer:
         self.r1_upd = torch.zeros(self.r1_numel if write_grad else 0, **f32)
         self.buf = _PlanBuffers(shapes, self.rank, self.r1_numel, self.device, native=native is not False)
         self.native = self.buf.native
+        # device block [lr, weight_decay, 0, 0], allocated before any capture; the kernels read it
+        # once set_hyper() was called or a decay is on, else lr goes by value (see set_hyper)
+        self.hyper = HyperBlock(self.device, self.lr, self.weight_decay) if self.native else None
+        self._hyper_on = self.native and self.weight_decay != 0.0
+        self._captured: Optional[Tuple[bool, bool]] = None  # (block read, decay on) of a captured step
         # dead-tap compaction (ops/taps.py; NDP_FUSION_OFF=dead_taps): the support version the plan
         # was last compared with (None: compare at the next step)
         self.dead_taps = self.native and bool(shapes) and fusion_on("dead_taps")
@@ -685,6 +703,7 @@ class PowerSGDOptimizer:
         p0, p1 = B.p_range(g.lo, g.hi)
         q0, q1 = B.q_range(g.lo, g.hi)
         mode, lr, mom, spins = 2 if self.write_grad else 1, self.lr, self.momentum, self.orth_max_spins
+        hy = self._hyper()
 
         pp = self.p_prev if self.lazy_ef else None
 
@@ -695,7 +714,7 @@ class PowerSGDOptimizer:
             B.run_q(B.items("q", g.lo, g.hi), g.q_seg, g.q_seg_fused)
             self.comm.all_reduce(B.q_memory[q0:q1])                       # reducer.py:145 (group g)
             X.psgd_update(B.geom, B.ptrs, B.items("u", g.lo, g.hi), B.comm_buf, B.q_memory, float(N),
-                          B.q_warm, mode, lr, mom, B.max_rank, pp)
+                          B.q_warm, mode, lr, mom, B.max_rank, pp, hyper=hy)
         self.comm.side_launch(pipeline)
         g.launched = True
 
@@ -726,13 +745,13 @@ class PowerSGDOptimizer:
                 self._r1_out.set(outs)
                 self._r1_key = key
             r1 = slice(self.r1_start, self.arena_numel)
-            lr, mom = self.lr, self.momentum
+            lr, mom, hy = self.lr, self.momentum, self._hyper()
 
             def rank1():
                 self._r1_pack.run()
                 self.comm.all_reduce(B.rank1_buf)                           # reducer.py:132
                 ext().rank1_step(B.rank1_buf, float(N), self._m[r1], self.x[r1],
-                                 self.r1_upd if self.write_grad else None, lr, mom)
+                                 self.r1_upd if self.write_grad else None, lr, mom, hyper=hy)
                 if self.write_grad:
                     self._r1_out.run()
             self.comm.side_launch(rank1)
@@ -885,20 +904,22 @@ class PowerSGDOptimizer:
         if self.native:
             X = ext()
             r1 = slice(self.r1_start, self.arena_numel)
+            hy = self._hyper()
             if B.shapes and B.fused and self.r1_numel:  # the rank-1 step rides in the update launch
                 X.psgd_update(B.geom, B.ptrs, B.u_items, B.comm_buf, B.q_memory, float(N), B.q_warm,
                               2 if self.write_grad else 1, self.lr, self.momentum, B.max_rank,
                               self.p_prev if self.lazy_ef else None, r1_buf=B.rank1_buf, r1_div=float(N),
-                              r1_mom=self._m[r1], r1_x=self.x[r1], r1_g=self.r1_upd if self.write_grad else None)
+                              r1_mom=self._m[r1], r1_x=self.x[r1], r1_g=self.r1_upd if self.write_grad else None,
+                              hyper=hy)
                 if self.write_grad:
                     self._r1_out.run()
             elif B.shapes:
                 X.psgd_update(B.geom, B.ptrs, B.u_items, B.comm_buf, B.q_memory, float(N), B.q_warm,
                               2 if self.write_grad else 1, self.lr, self.momentum, B.max_rank,
-                              self.p_prev if self.lazy_ef else None)
+                              self.p_prev if self.lazy_ef else None, hyper=hy)
             if self.r1_numel and not (B.shapes and B.fused):
                 X.rank1_step(B.rank1_buf, float(N), self._m[r1], self.x[r1],
-                             self.r1_upd if self.write_grad else None, self.lr, self.momentum)
+                             self.r1_upd if self.write_grad else None, self.lr, self.momentum, hyper=hy)
                 if self.write_grad:
                     self._r1_out.run()
         else:
@@ -939,12 +960,70 @@ class PowerSGDOptimizer:
     def set_overlap(self, on: bool):
         if on and not self.groups:
             raise ValueError("optimizer was built without overlap groups")
+        if self.hyper is not None and bool(on) != bool(self.overlap):
+            # the block's uploads follow the update launches' stream (set_hyper): order both ways
+            self.comm.fork()
+            self.comm.join()
         self.overlap = on
         self._reset_groups()
 
+    # -- hyper-parameter block -----------------------------------------------------------------
+    def _hyper(self) -> Optional[torch.Tensor]:
+        """The ``hyper=`` argument of this step's update launches (None: lr by value, no decay)."""
+        if capturing():
+            self._captured = (self._hyper_on, self.weight_decay != 0.0)
+        return self.hyper.dev if self._hyper_on else None
+
+    def plan_hyper(self, pairs):
+        """Write the pinned source rows of the coming steps' ``(lr, weight_decay)`` ahead of time."""
+        if self.hyper is not None:
+            self.hyper.prefill(pairs)
+
+    def set_hyper(self, lr: float, weight_decay: Optional[float] = None):
+        """Learning rate and L2 weight decay of the steps from now on, captured replays included.
+
+        Both are rounded to fp32 once, kept in ``self.lr`` / ``self.weight_decay`` (what the torch
+        twin uses) and, on the native path, uploaded into the device block by one 16-byte async copy
+        from a pinned row; nothing is enqueued when neither changed.  Never called inside a
+        capture.  A step captured before the first call holds ``lr`` by value, and a captured step
+        holds its dead-tap plan: changing what such a graph froze raises.
+
+        Ordering of the copy: it must follow the previous step's last update launch and precede
+        this step's first one.  Without overlap every launch of a step — eager or replayed — is on
+        the current stream, and so is the copy.  With overlap groups the update launches run on
+        the communicator's side stream; replayed, they sit at the tail of the comm graph, which is
+        launched on that stream and is not joined with the current one between steps (a device
+        flag, not the stream, releases the next compute graph), so a copy on the current stream
+        could overtake them.  The copy therefore goes on the side stream itself: stream order puts
+        it after the previous comm graph (or eager side work) and before the next."""
+        wd = self.weight_decay if weight_decay is None else float(weight_decay)
+        assert wd >= 0, "weight_decay >= 0"
+        lr, wd = float(np.float32(lr)), float(np.float32(wd))
+        if self._captured is not None:
+            block, decay = self._captured
+            if not block and (lr != float(np.float32(self.lr)) or wd != 0.0):
+                raise RuntimeError("PowerSGD: the captured step holds lr by value; call set_hyper() before capturing")
+            if decay != (wd != 0.0):
+                raise RuntimeError("PowerSGD: weight_decay cannot be switched on or off after capture (the step "
+                                   "froze its dead-tap plan); capture again")
+        if (wd != 0.0) != (self.weight_decay != 0.0):
+            self._taps_seen = None  # decay on: every matrix full (_wanted_supports); off: compact again
+        self.lr, self.weight_decay = lr, wd
+        if self.hyper is not None:
+            self._hyper_on = True
+            self._upload_hyper()
+
+    def _upload_hyper(self, force: bool = False):
+        assert not capturing(), "set_hyper() inside a graph capture"
+        if self.overlap:  # the update launches run on the side stream (see set_hyper)
+            with self.comm.on_side():
+                self.hyper.set(self.lr, self.weight_decay, force)
+        else:
+            self.hyper.set(self.lr, self.weight_decay, force)
+
     def _step_torch(self, N, grads):
         B = self.buf
-        lam, lr = self.momentum, self.lr
+        lam, lr, wd = self.momentum, self.lr, self.weight_decay
         gmap = {id(p): g for p, g in zip(self.params, grads)}
         Ms = []
         for i, p in enumerate(self.high):
@@ -969,6 +1048,8 @@ class PowerSGDOptimizer:
         for i, (p, M) in enumerate(zip(self.high, Ms)):
             out = torch.matmul(B.p_view(i), B.q_view(i).t()).view(-1)
             self._view(self._e, p).copy_(M.reshape(-1) - out)
+            if wd != 0.0:  # after decompression and the error memory: d = out + wd x
+                out = out.add(self._view(self.x, p), alpha=wd)
             mom = self._view(self._m, p)
             mom.mul_(lam).add_(out)
             upd = out + mom
@@ -978,6 +1059,8 @@ class PowerSGDOptimizer:
         if self.r1_numel:
             r1 = slice(self.r1_start, self.arena_numel)
             out = B.rank1_buf / N
+            if wd != 0.0:
+                out = out.add(self.x[r1], alpha=wd)
             self._m[r1].mul_(lam).add_(out)
             upd = out + self._m[r1]
             self.x[r1].add_(upd, alpha=-lr)
@@ -988,7 +1071,11 @@ class PowerSGDOptimizer:
 
     # -- dead-tap compaction -----------------------------------------------------------------------
     def _wanted_supports(self) -> List[Tuple[int, int]]:
-        """(T, mask) of every high-rank parameter whose recorded support has dead taps, else (0, 0)."""
+        """(T, mask) of every high-rank parameter whose recorded support has dead taps, else (0, 0).
+        With weight decay a dead tap's weight still moves (d = wd x), so it needs its momentum:
+        every matrix reports (0, 0), the full plan."""
+        if self.weight_decay != 0.0:
+            return [(0, 0)] * len(self.high)
         out = []
         for p in self.high:
             s = taps.support_of(p) if p.dim() == 4 else None
@@ -1137,6 +1224,7 @@ class PowerSGDOptimizer:
             "q_ready": self._q_ready,
             "rng_state": _rng_state_to_dict(self.rng.get_state()),
             "lr": self.lr,
+            "weight_decay": self.weight_decay,
             "momentum_coef": self.momentum,
             "rank": self.rank,
         }
@@ -1157,7 +1245,11 @@ class PowerSGDOptimizer:
         self._q_ready = bool(sd.get("q_ready", self.step_count > 0)) and self.reuse_query
         self.rng.set_state(_rng_state_from_dict(sd["rng_state"]))
         self.lr = float(sd["lr"])
+        self.weight_decay = float(sd.get("weight_decay", 0.0))
         self.momentum = float(sd["momentum_coef"])
+        if self.hyper is not None:  # the block follows the loaded values
+            self._hyper_on = self._hyper_on or self.weight_decay != 0.0
+            self._upload_hyper(force=True)
 
 
 def _rng_state_to_dict(st):

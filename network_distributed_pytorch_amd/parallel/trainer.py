@@ -12,6 +12,11 @@
 ``dense-ref``      reference dense arm: blocking per-parameter all-reduce + torch.optim.SGD
                    (ddp_guide_cifar10/ddp_init.py:57-62,111,124-125).
 =================  ===========================================================================
+
+Every strategy has ``set_hyper(lr, weight_decay)``: the learning rate and the L2 weight decay of
+the steps from now on (the engine calls it before every step when a schedule or a decay is on).
+The native engines forward it to their optimiser's device block, the reference loops apply it
+in torch.
 """
 from __future__ import annotations
 
@@ -50,6 +55,12 @@ class PowerSGDSync:
     def step(self):
         return self.opt.step()
 
+    def set_hyper(self, lr, weight_decay=None):
+        self.opt.set_hyper(lr, weight_decay)
+
+    def plan_hyper(self, pairs):
+        self.opt.plan_hyper(pairs)
+
     def phases(self):
         return self.opt.phases()
 
@@ -81,7 +92,7 @@ class ReferencePowerSGDLoop:
     def __init__(self, model, comm, lr, momentum, rank, seed=714, native_reducer=False):
         self.model = model
         self.params = list(model.parameters())
-        self.lr, self.lam = lr, momentum
+        self.lr, self.lam, self.weight_decay = lr, momentum, 0.0
         self.reducer = PowerSGDReducer(seed, self.params[0].device, 0, True, rank=rank, comm=comm)
         self.native_reducer = native_reducer
         self.memories = [torch.zeros_like(p) for p in self.params]
@@ -101,6 +112,11 @@ class ReferencePowerSGDLoop:
         for p in self.params:
             p.grad = None
 
+    def set_hyper(self, lr, weight_decay=None):
+        self.lr = float(lr)
+        if weight_decay is not None:
+            self.weight_decay = float(weight_decay)
+
     @torch.no_grad()
     def step(self):
         grads = [p.grad for p in self.params]
@@ -110,6 +126,9 @@ class ReferencePowerSGDLoop:
             self.bits += self.reducer.reduce(self.send_buffers, grads, self.memories)
         else:
             self.bits += self.reducer.reduce_torch(self.send_buffers, grads, self.memories)
+        if self.weight_decay != 0.0:  # L2 on the decompressed gradient: never in the memory or on the wire
+            for p, g in zip(self.params, grads):
+                g.add_(p, alpha=self.weight_decay)
         for g, m in zip(grads, self.momenta):
             if self.first:
                 m.data = g.clone().detach()
@@ -136,6 +155,9 @@ class ReferenceDenseLoop:
 
     def zero_grad(self):
         self.opt.zero_grad()
+
+    def set_hyper(self, lr, weight_decay=None):
+        _set_param_groups(self.opt, lr, weight_decay)
 
     def step(self):
         bits = average_gradients(self.model, self.comm)
@@ -174,6 +196,12 @@ class _DenseSync:
     def step(self):
         return self.ddp.step()
 
+    def set_hyper(self, lr, weight_decay=None):
+        self.ddp.set_hyper(lr, weight_decay)
+
+    def plan_hyper(self, pairs):
+        self.ddp.plan_hyper(pairs)
+
     def phases(self):
         return self.ddp.phases()
 
@@ -185,6 +213,13 @@ class _DenseSync:
 
     def load_state_dict(self, sd):
         self.ddp.load_state_dict(sd)
+
+
+def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
+    for group in opt.param_groups:
+        group["lr"] = float(lr)
+        if weight_decay is not None:
+            group["weight_decay"] = float(weight_decay)
 
 
 def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
@@ -222,6 +257,9 @@ class LocalOptimizer:
 
     def zero_grad(self):
         self.opt.zero_grad()
+
+    def set_hyper(self, lr, weight_decay=None):
+        _set_param_groups(self.opt, lr, weight_decay)
 
     def step(self):
         self.opt.step()

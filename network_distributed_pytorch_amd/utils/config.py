@@ -28,6 +28,7 @@ LINKS = ("none", "1g", "10g", "100g")
 BACKENDS = ("nccl", "gloo")
 AUGMENTS = ("none", "crop_flip")
 NORMALIZES = ("half", "cifar")
+LR_SCHEDULES = ("constant", "step", "cosine")  # utils/schedule.py
 
 
 @dataclasses.dataclass
@@ -84,6 +85,14 @@ class TrainConfig:
     data_root: Optional[str] = None  # directory with the CIFAR-10 files; None = synthetic data
     augment: str = "none"  # "crop_flip": random crop (pad 4) + horizontal flip, training only
     normalize: str = "half"  # "half" = 0.5 / 0.5 per channel (the reference), "cifar" = dataset statistics
+    # learning-rate schedule (utils/schedule.py) and L2 weight decay; the update kernels read both from
+    # the optimiser's device block, so they reach a captured step too
+    lr_schedule: str = "constant"  # after the warm-up: "constant", "step" (milestones / gamma), "cosine" (to lr_min)
+    lr_warmup_steps: int = 0  # linear warm-up over the first N steps: base * (s + 1) / N
+    lr_min: float = 0.0  # floor of the cosine
+    lr_milestones: str = ""  # "step": comma-separated epochs, e.g. "15,25"
+    lr_gamma: float = 0.1  # "step": factor per milestone passed
+    weight_decay: float = 0.0  # L2, every parameter (torch.optim.SGD's weight_decay)
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -130,7 +139,8 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
             config[name] = _check_type(name, config[name])
     c = config
     for key, allowed in (("grad_sync", GRAD_SYNCS), ("task", TASKS), ("graph_mode", GRAPH_MODES), ("link", LINKS),
-                         ("distributed_backend", BACKENDS), ("augment", AUGMENTS), ("normalize", NORMALIZES)):
+                         ("distributed_backend", BACKENDS), ("augment", AUGMENTS), ("normalize", NORMALIZES),
+                         ("lr_schedule", LR_SCHEDULES)):
         if c[key] not in allowed:
             raise ConfigError(f"config[{key!r}] = {c[key]!r}; allowed: {list(allowed)}")
     if c["n_workers"] < 1 or not 0 <= c["rank"] < c["n_workers"]:
@@ -157,6 +167,19 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError(f"data_root is for task='cifar' only (task = {c['task']!r})")
     if c["augment"] != "none" and c["data_root"] is None:
         raise ConfigError(f"augment = {c['augment']!r} needs data_root (the synthetic data is never augmented)")
+    if c["weight_decay"] < 0:
+        raise ConfigError("weight_decay must be >= 0")
+    if not 0 <= c["lr_min"] <= c["learning_rate"]:
+        raise ConfigError(f"lr_min {c['lr_min']} must lie in [0, learning_rate = {c['learning_rate']}]")
+    if c["lr_warmup_steps"] < 0 or not c["lr_gamma"] > 0:
+        raise ConfigError("lr_warmup_steps >= 0 and lr_gamma > 0 required")
+    from .schedule import parse_milestones
+    try:
+        milestones = parse_milestones(c["lr_milestones"])
+    except ValueError as exc:
+        raise ConfigError(f"config['lr_milestones'] = {c['lr_milestones']!r}: {exc}") from None
+    if milestones and c["lr_schedule"] != "step":
+        raise ConfigError(f"lr_milestones are for lr_schedule='step' only (lr_schedule = {c['lr_schedule']!r})")
     if unknown:
         config["_unknown_keys"] = unknown
     return config

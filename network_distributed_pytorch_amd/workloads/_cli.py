@@ -10,7 +10,9 @@ default).  Additions: ``-spawn`` launches all ranks locally (127.0.0.1 rendezvou
 ``-log_every``, ``-dataset_size``, ``-check_replicas``, ``-bucket_mb``, ``-reuse_query``,
 ``-overlap``, ``-psgd_groups``, ``-emulate_world``, ``-eval_every`` / ``-eval_size`` / ``-eval_topk``
 (held-out evaluation every N epochs: loss, top-1, top-k), ``-data_root`` / ``-augment`` / ``-normalize``
-(train and evaluate on the CIFAR-10 files in a directory instead of synthetic data).
+(train and evaluate on the CIFAR-10 files in a directory instead of synthetic data), ``-lr_schedule`` /
+``-lr_warmup_steps`` / ``-lr_min`` / ``-lr_milestones`` / ``-lr_gamma`` / ``-weight_decay`` (learning-rate
+schedule and L2 weight decay, utils/schedule.py).
 """
 from __future__ import annotations
 
@@ -64,6 +66,13 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
                    help="crop_flip: random crop (pad 4) + horizontal flip of the training images (needs -data_root)")
     p.add_argument("-normalize", type=str, default=None, choices=[None, "half", "cifar"],
                    help="half: mean/std 0.5 (default); cifar: the dataset's channel statistics")
+    p.add_argument("-lr_schedule", type=str, default=None, choices=[None, "constant", "step", "cosine"],
+                   help="learning rate after the warm-up (default constant)")
+    p.add_argument("-lr_warmup_steps", type=int, default=None, help="linear warm-up over the first N steps")
+    p.add_argument("-lr_min", type=float, default=None, help="cosine: final learning rate (default 0)")
+    p.add_argument("-lr_milestones", type=str, default=None, help="step: comma-separated epochs, e.g. 15,25")
+    p.add_argument("-lr_gamma", type=float, default=None, help="step: factor per milestone (default 0.1)")
+    p.add_argument("-weight_decay", type=float, default=None, help="L2 weight decay, every parameter (default 0)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -76,7 +85,9 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "dataset_size": "dataset_size", "check_replicas": "check_replicas_every", "toy_steps": "toy_mlp_steps",
         "bucket_mb": "bucket_mb", "psgd_groups": "psgd_groups", "emulate_world": "emulate_world",
         "log_every": "log_every", "seq_len": "seq_len", "eval_every": "eval_every", "eval_size": "eval_size",
-        "eval_topk": "eval_topk", "data_root": "data_root", "augment": "augment", "normalize": "normalize"}
+        "eval_topk": "eval_topk", "data_root": "data_root", "augment": "augment", "normalize": "normalize",
+        "lr_schedule": "lr_schedule", "lr_warmup_steps": "lr_warmup_steps", "lr_min": "lr_min",
+        "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
