@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <string>
 
 #include "ndp_kernels.h"
@@ -618,7 +619,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(
 // per-channel finalize kernel folds the slice partials in a fixed order (deterministic).
 // part layout: [c][s][2] partial sums, then 3*C doubles of per-channel coefficients.
 constexpr int kSmallNPer = 4;  // images per stats slice: 4 independent loads in flight per thread
-int bn_small_slices(int N, int C, int HW) { return (N + kSmallNPer - 1) / kSmallNPer; }
+static int bn_small_slices(int N) { return (N + kSmallNPer - 1) / kSmallNPer; }
 
 template <int HW>
 __global__ __launch_bounds__(256) void bn_small_stats_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -817,22 +818,7 @@ __device__ __forceinline__ int xcd_block(int bid, int nblk) {
 // downsample branch's BN output is never stored.  Backward: both BNs see the same
 // dz = dy * (out > 0), so one pass forms sum dz, sum dz * xhat, sum dz * xhat2 and writes both
 // input gradients (out, p2.out2).  One launch and one tensor round trip fewer per direction and
-// downsample block than two single launches.
-struct BnPair {
-  const float* x2;
-  const float* gamma2;
-  const float* beta2;
-  float* rmean2;
-  float* rvar2;
-  int64_t* nbt2;
-  float* save_mean2;
-  float* save_invstd2;
-  float* dgamma2;
-  float* dbeta2;
-  float* out2;
-  const float* src2;  // forward: x2 as nslab2 unsummed split-K slabs (summed here, stored to x2), or null
-  int nslab2;
-};
+// downsample block than two single launches.  (struct BnPair: ndp_kernels.h)
 
 template <int HW, int BWD, int CW, int MAXN = kFusedMaxN, int PAIR = 0>
 __global__ __launch_bounds__(kFusedThreads) void bn_small_fused_kernel(
@@ -1429,11 +1415,6 @@ __global__ __launch_bounds__(kFusedThreads) void bn_small_fused_v4_kernel(
 // workgroup, <= 128 rows): the split-K convs there emit no epilogue statistics, so the two-kernel
 // path ran a statistics pass and an apply pass per direction.
 constexpr int kFusedMaxN64 = 128;
-static bool bn_fused_ok(int N, int C, int HW) {
-  return (((HW == 1 || HW == 2 || HW == 4 || HW == 8 || HW == 16) && N <= kFusedMaxN) ||
-          (HW == 64 && N <= kFusedMaxN64 && !vec_off())) &&
-         N >= 1 && (int64_t)N * C * HW < (1LL << 30);
-}
 
 // column-block width for one launch: the widest block that still gives >= 256 workgroups (one per
 // CU), else the narrowest allowed one (4 columns, 16-B row segments: grid size matters more than
@@ -1443,58 +1424,12 @@ static bool bn_fused_ok(int N, int C, int HW) {
 // Round 5 (float4 kernel): 4-column blocks at every batch, not only <= 128 — ResNet-18 r=4 batch
 // 512 1.4994 / 1.4922 -> 1.4864 / 1.4862 ms, batch 256 1.1095 -> 1.1033 (layer3 / layer4 BNs get
 // 2x the workgroups; profiles/r5/bench_bn_colw.jsonl).
-static int bn_colw_for(int HW, int C, int N) {
-  (void)N;
+static int bn_colw_for(int HW, int C) {
   const int lo = 4;
   const int64_t cols = (int64_t)C * HW;
   for (int cw = 16; cw >= lo; cw >>= 1)
     if (cw >= HW && cols / cw >= 256) return cw;
   return HW > lo ? HW : lo;
-}
-
-template <int BWD, int CW>
-static void launch_small_fused_cw(int HW, const float* x, const float* res, const float* dy, const float* yin,
-                                  const float* gamma, const float* beta, float* rmean, float* rvar, int64_t* nbt,
-                                  float* sm, float* si, float* dgamma, float* dbeta, float* out, float* dres, int N,
-                                  int C, float eps, float momentum, int relu, hipStream_t s, const float* src,
-                                  int nslab, const BnPair* pr) {
-  const int nblk = (int)(((int64_t)C * HW + CW - 1) / CW);
-  const BnPair pp = pr ? *pr : BnPair{};
-  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  // float4 kernel: rows of whole float4s, 16-B aligned operands.  Not for small maps at small
-  // batches: with HW <= 4 and N <= 128 the scalar kernel's 4-column blocks keep 4x more threads
-  // busy per row and its reduction is shorter — ResNet-18 at batch 64: HW = 1 4.8 vs 6.7 µs, HW = 4
-  // 4.8 vs 5.0 µs per launch (v4 wins everywhere at batch 512 and for HW = 16: 8.0 -> 5.3 µs at 64)
-  const bool v4 = ((int64_t)C * HW) % 4 == 0 && a16(x) && a16(res) && a16(dy) && a16(yin) && a16(out) &&
-                  a16(dres) && a16(src) && (pr == nullptr || (a16(pr->x2) && a16(pr->out2) && a16(pr->src2) && HW >= 4)) &&
-                  !vec_off() && (HW >= 8 || N > 128);  // (pair at HW < 4: 4 channels' operands per float4 spill)
-#define NDP_BN_FUSED_P(HWV, P)                                                                                     \
-  if (v4) {                                                                                                        \
-    if constexpr (P == 0 || HWV >= 4)                                                                              \
-      hipLaunchKernelGGL((bn_small_fused_v4_kernel<HWV, BWD, CW, kFusedMaxN, P>), dim3((unsigned)nblk),            \
-                         dim3(kFusedThreads), 0, s, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma,  \
-                         dbeta, out, dres, N, C, eps, momentum, relu, src, nslab, pp);                               \
-  } else                                                                                                           \
-    hipLaunchKernelGGL((bn_small_fused_kernel<HWV, BWD, CW, kFusedMaxN, P>), dim3((unsigned)nblk),                 \
-                       dim3(kFusedThreads), 0, s, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma,    \
-                       dbeta, out, dres, N, C, eps, momentum, relu, src, nslab, pp);
-#define NDP_BN_FUSED(HWV)                                                                                          \
-  if constexpr (CW % HWV == 0) {                                                                                   \
-    if (pr) {                                                                                                      \
-      NDP_BN_FUSED_P(HWV, 1)                                                                                       \
-    } else {                                                                                                       \
-      NDP_BN_FUSED_P(HWV, 0)                                                                                       \
-    }                                                                                                              \
-  }
-  switch (HW) {  // the caller picks CW >= HW
-    case 1: NDP_BN_FUSED(1); break;
-    case 2: NDP_BN_FUSED(2); break;
-    case 4: NDP_BN_FUSED(4); break;
-    case 8: NDP_BN_FUSED(8); break;
-    default: NDP_BN_FUSED(16); break;
-  }
-#undef NDP_BN_FUSED
-#undef NDP_BN_FUSED_P
 }
 
 // Row splits of the 8x8-map single-launch BN (bn_small_fused_v4_kernel SPLIT): workgroups per
@@ -1515,7 +1450,7 @@ static int bn_row_split(int N, int C) {
   return sp;
 }
 
-static BnSplitCtx bn_split_ctx(int C, int split) {
+static BnSplitCtx bn_split_ctx(int split) {
   constexpr int kCols = 1024;  // column blocks (channels) covered
   struct Buf { double* part = nullptr; unsigned long long* ctr = nullptr; };
   static Buf bufs[64];
@@ -1528,291 +1463,302 @@ static BnSplitCtx bn_split_ctx(int C, int split) {
     (void)hipMemset(b.ctr, 0, sizeof(unsigned long long) * kCols * 3);
     (void)hipDeviceSynchronize();
   }
-  (void)C;
   // one counter range per split factor: a counter only ever moves in steps of its own SPLIT
   return BnSplitCtx{b.part, b.ctr + (split == 2 ? 0 : kCols), 1u << 22};
 }
 
-template <int BWD>
-static void launch_small_fused(int HW, const float* x, const float* res, const float* dy, const float* yin,
-                               const float* gamma, const float* beta, float* rmean, float* rvar, int64_t* nbt,
-                               float* sm, float* si, float* dgamma, float* dbeta, float* out, float* dres, int N,
-                               int C, float eps, float momentum, int relu, hipStream_t s, const float* src,
-                               int nslab, const BnPair* pr = nullptr) {
-  if (HW == 64) {  // one channel per workgroup (bn_fused_ok); float4 unless an operand is unaligned
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (pr != nullptr) return;  // (bn_pair_ok: no pair on the 8x8 maps)
-    const int split = bn_row_split(N, C);
-    if (a16(x) && a16(res) && a16(dy) && a16(yin) && a16(out) && a16(dres) && a16(src) && split > 1) {
-      const BnSplitCtx sx = bn_split_ctx(C, split);
-#define NDP_BN_SPLIT_LAUNCH(SP)                                                                                  \
-  hipLaunchKernelGGL((bn_small_fused_v4_kernel<64, BWD, 64, kFusedMaxN64, 0, SP>), dim3((unsigned)(C * SP)),     \
-                     dim3(kFusedThreads), 0, s, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma,  \
-                     dbeta, out, dres, N, C, eps, momentum, relu, src, nslab, BnPair{}, sx)
-      if (split == 2) NDP_BN_SPLIT_LAUNCH(2);
-      else NDP_BN_SPLIT_LAUNCH(4);
-#undef NDP_BN_SPLIT_LAUNCH
-    } else if (a16(x) && a16(res) && a16(dy) && a16(yin) && a16(out) && a16(dres) && a16(src))
-      hipLaunchKernelGGL((bn_small_fused_v4_kernel<64, BWD, 64, kFusedMaxN64>), dim3((unsigned)C),
-                         dim3(kFusedThreads), 0, s, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma,
-                         dbeta, out, dres, N, C, eps, momentum, relu, src, nslab, BnPair{});
-    else
-      hipLaunchKernelGGL((bn_small_fused_kernel<64, BWD, 64, kFusedMaxN64>), dim3((unsigned)C), dim3(kFusedThreads),
-                         0, s, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma, dbeta, out, dres, N, C,
-                         eps, momentum, relu, src, nslab, BnPair{});
-    return;
-  }
-  switch (bn_colw_for(HW, C, N)) {
-    case 16:
-      launch_small_fused_cw<BWD, 16>(HW, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma, dbeta, out,
-                                     dres, N, C, eps, momentum, relu, s, src, nslab, pr);
-      break;
-    case 4:
-      launch_small_fused_cw<BWD, 4>(HW, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma, dbeta, out,
-                                    dres, N, C, eps, momentum, relu, s, src, nslab, pr);
-      break;
-    default:
-      launch_small_fused_cw<BWD, 8>(HW, x, res, dy, yin, gamma, beta, rmean, rvar, nbt, sm, si, dgamma, dbeta, out,
-                                    dres, N, C, eps, momentum, relu, s, src, nslab, pr);
-  }
-}
-
-
-template <int HW>
-static void small_stats(const float* x, const float* dy, const float* y, const float* sm, const float* si,
-                        double* part, int N, int C, int S, int bwd, int relu, hipStream_t s) {
-  const dim3 grid(S, (C * HW + 255) / 256);
-  hipLaunchKernelGGL(bn_small_stats_kernel<HW>, grid, dim3(256), 0, s, x, dy, y, sm, si, part, N, C, S, bwd, relu);
-}
-
-static void small_stats_any(int HW, const float* x, const float* dy, const float* y, const float* sm, const float* si,
-                            double* part, int N, int C, int S, int bwd, int relu, hipStream_t s) {
-  switch (HW) {
-    case 1: small_stats<1>(x, dy, y, sm, si, part, N, C, S, bwd, relu, s); break;
-    case 2: small_stats<2>(x, dy, y, sm, si, part, N, C, S, bwd, relu, s); break;
-    case 4: small_stats<4>(x, dy, y, sm, si, part, N, C, S, bwd, relu, s); break;
-    case 8: small_stats<8>(x, dy, y, sm, si, part, N, C, S, bwd, relu, s); break;
-    default: small_stats<16>(x, dy, y, sm, si, part, N, C, S, bwd, relu, s); break;
-  }
-}
-
-// the three-kernel small-map path (statistics, finalize, apply) for HW <= 4 where the
-// single-launch kernel does not apply (batch > 512); HW = 16 measured faster on the
-// per-channel kernels
-bool bn_small_path(int N, int C, int HW) {
-  return (HW == 1 || HW == 2 || HW == 4) && (int64_t)N * C * HW < (1LL << 30);
-}
-
-// scratch: the per-launch slice partials and coefficients (fp64)
-int64_t bn_part_numel(int N, int C, int HW) {
-  const int64_t big = (int64_t)C * bn_slices(N, C, HW) * 2;
-  const int64_t small = (int64_t)C * bn_small_slices(N, C, HW) * 2 + 3 * (int64_t)C;
-  return big > small ? big : small;
-}
-
-// ----------------------------------- launchers -------------------------------------------
+// ------------------------------------- the route ------------------------------------------
 // Deferred conv slabs are summed inside the single-launch BN kernel only up to this many:
 // ResNet-18 step on 1x MI355X, layer2 (HW 16) at per-GPU batch 256 (2 slabs) 1.4968 ->
 // 1.4688 ms, batch 128 (4) 1.2158 -> 1.2176 (even), batch 64 (8 slabs) 1.0689 -> 1.0746 (the
 // BN's 128 workgroups read 8 slabs slower than the 256-CU sum kernel plus a launch).
-constexpr int kMaxFusedSlabs = 4;
 // Two-kernel path (8x8 maps of layer1): the statistics pass adds the deferred slabs and writes
 // the summed tensor, no separate sum launch.  ResNet-18 step on 1x MI355X: batch 128 1.196 /
 // 1.198 -> 1.164 / 1.165 ms, batch 64 1.061 / 1.058 -> 1.046 / 1.053.
-int bn_slices(int N, int C, int HW) {
-  // ~4 workgroups per CU over the whole launch, >= ~2K elements per workgroup
-  int64_t s = (1024 + C - 1) / C;
-  const int64_t by_work = ((int64_t)N * HW) / 2048;
-  if (s > by_work) s = by_work;
-  if (s > N) s = N;
-  if (s < 1) s = 1;
-  return (int)s;
+constexpr int kMaxFusedSlabs = 4;
+
+static bool a16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (((uintptr_t)p & 15) != 0) return false;
+  return true;
 }
 
-// apply-pass slices when the statistics come from a conv epilogue: every apply workgroup folds
-// ALL the conv's per-image partials of its channel (fewer, larger workgroups measured slower:
-// ResNet-18 r=4 batch 512, S / 1 / 2 / 4 / 8 = 1.862-1.874 / 1.864 / 1.884 / 1.926 ms, round 4)
-static int ext_apply_slices(int S) { return S < 1 ? 1 : S; }
+BnAlign bn_alignment(int bwd, const BnOps& o, const BnPair* pr) {
+  BnAlign a;
+  const float* x2 = pr ? pr->x2 : nullptr;
+  a.fused = bwd ? a16({o.x, o.dy, o.yin, o.out, o.dres, x2, pr ? pr->out2 : nullptr}) : a16({o.x, o.res, o.out, x2});
+  // (the stem tail reads x alone as float4s: its pooled output is no operand of the statistics pass)
+  a.two = bwd ? a16({o.dy, o.x, o.out, o.relu ? o.yin : nullptr, o.dres}) : a16({o.x, o.idx ? nullptr : o.out, o.res});
+  a.slabs = a16({o.slabs, o.addend});
+  a.slabs2 = a16({pr ? pr->src2 : nullptr});
+  return a;
+}
 
-void launch_bn_fwd(const float* x, const float* res, float* y, const float* gamma, const float* beta,
-                   float* rmean, float* rvar, int64_t* nbt, float* save_mean, float* save_invstd,
-                   double* part, int N, int C, int HW, int S, float eps, float momentum, int relu,
-                   int training, int single, hipStream_t s, const float* xpart, int nslab, const double* xstats,
-                   int xS) {
-  if (!training || xpart != nullptr) xstats = nullptr;
-  if (xpart != nullptr && nslab < 2) xpart = nullptr;
-  if (xpart != nullptr && nslab > kMaxFusedSlabs) {  // many slabs: the wide sum kernel first
-    launch_slab_sum(xpart, const_cast<float*>(x), (int64_t)N * C * HW, nslab, s);
-    xpart = nullptr;
+// Paths.  Single launch: HW in {1, 2, 4, 8, 16} at N <= kFusedMaxN, and the 8x8 maps at N <=
+// kFusedMaxN64 (float4 builds only), when the caller allows it (`single`).  Three kernels
+// (statistics, finalize, apply): HW <= 4 where the single launch does not apply (batch > 512);
+// HW = 16 measured faster on the per-channel kernels.  Two kernels over a (slice, channel) grid:
+// everything else, evaluation mode and the stem tail.
+BnRoute bn_make_route(const BnQuery& q) {
+  const int N = q.N, C = q.C, HW = q.HW;
+  BnRoute r{};
+  r.bwd = q.bwd; r.N = N; r.C = C; r.HW = HW; r.pool_w = q.pool_w; r.pair = q.pair;
+  r.training = q.bwd || q.pool_w > 0 || q.training;
+  // ~4 workgroups per CU over the whole two-kernel launch, >= ~2K elements per workgroup
+  int64_t S = (1024 + C - 1) / C;
+  if (S > ((int64_t)N * HW) / 2048) S = ((int64_t)N * HW) / 2048;
+  if (S > N) S = N;
+  r.S = r.Sa = S < 1 ? 1 : (int)S;  // (the apply keeps the statistics pass's slices, external statistics or not)
+  r.Ss = bn_small_slices(N);
+  // scratch: the per-launch slice partials, or the small-map partials and coefficients (fp64)
+  const int64_t big = (int64_t)C * r.S * 2, small = (int64_t)C * r.Ss * 2 + 3 * (int64_t)C;
+  r.part_numel = big > small ? big : small;
+
+  const bool in_range = (int64_t)N * C * HW < (1LL << 30);
+  const bool fused_ok = N >= 1 && in_range &&
+                        (((HW == 1 || HW == 2 || HW == 4 || HW == 8 || HW == 16) && N <= kFusedMaxN) ||
+                         (HW == 64 && N <= kFusedMaxN64 && !vec_off()));
+  if (q.pool_w > 0) r.path = kBnTwoKernel;
+  else if (q.pair) r.path = HW != 64 && fused_ok ? kBnFused : kBnNone;  // (no pair on the 8x8 maps)
+  else if (r.training && q.single && fused_ok) r.path = HW == 64 ? kBnFused64 : kBnFused;
+  else if (r.training && (HW == 1 || HW == 2 || HW == 4) && in_range) r.path = kBnThreeKernel;
+  else r.path = kBnTwoKernel;
+  // the mask recomputed from x: the float4 two-kernel backward only
+  if (q.mbeta && !(q.bwd && q.relu && HW % 4 == 0 && r.path == kBnTwoKernel)) r.path = kBnNone;
+  if (r.path == kBnNone) return r;
+
+  // fewer than two slabs count as none; more than kMaxFusedSlabs take the wide sum kernel first
+  auto slab_rule = [](int n) { return n < 2 ? kBnSlabNone : n > kMaxFusedSlabs ? kBnSlabSumFirst : kBnSlabInKernel; };
+  r.slab = slab_rule(q.nslab);
+  r.slab2 = q.pair && !q.bwd ? slab_rule(q.nslab2) : kBnSlabNone;
+  r.addend = q.addend && r.slab != kBnSlabNone;
+
+  if (r.path == kBnFused || r.path == kBnFused64) {
+    const bool aligned = q.al.fused && (r.slab != kBnSlabInKernel || q.al.slabs) &&
+                         (r.slab2 != kBnSlabInKernel || q.al.slabs2);
+    if (r.path == kBnFused64) {  // one channel per column block; float4 unless an operand is unaligned
+      r.CW = 64;
+      r.MAXN = kFusedMaxN64;
+      r.v4 = aligned;
+      r.split = aligned ? bn_row_split(N, C) : 1;
+      r.grid = C * r.split;
+    } else {
+      r.CW = bn_colw_for(HW, C);
+      r.MAXN = kFusedMaxN;
+      // float4 kernel: rows of whole float4s, 16-B aligned operands.  Not for small maps at small
+      // batches: with HW <= 4 and N <= 128 the scalar kernel's 4-column blocks keep 4x more threads
+      // busy per row and its reduction is shorter — ResNet-18 at batch 64: HW = 1 4.8 vs 6.7 µs, HW = 4
+      // 4.8 vs 5.0 µs per launch (v4 wins everywhere at batch 512 and for HW = 16: 8.0 -> 5.3 µs at 64)
+      // (pair at HW < 4: 4 channels' operands per float4 spill)
+      r.v4 = ((int64_t)C * HW) % 4 == 0 && aligned && (!q.pair || HW >= 4) && !vec_off() && (HW >= 8 || N > 128);
+      r.split = 1;
+      r.grid = (int)(((int64_t)C * HW + r.CW - 1) / r.CW);
+    }
+    return r;
   }
-  if (training && single && bn_fused_ok(N, C, HW)) {
-    launch_small_fused<0>(HW, x, res, nullptr, nullptr, gamma, beta, rmean, rvar, nbt, save_mean, save_invstd,
-                          nullptr, nullptr, y, nullptr, N, C, eps, momentum, relu, s, xpart, nslab);
+  r.vec = HW % 4 == 0 && q.al.two;
+  // no fused consumer for the slabs (only the float4 statistics pass adds them): sum them first
+  if (r.slab == kBnSlabInKernel && !(r.path == kBnTwoKernel && r.training && r.vec && q.al.slabs))
+    r.slab = kBnSlabSumFirst;
+  if (r.path == kBnThreeKernel) {
+    r.vec = 0;
+    return r;
+  }
+  // statistics from the producing conv's epilogue: no statistics pass, every apply workgroup folds
+  // ALL the conv's partials of its channel (fewer, larger workgroups measured slower: ResNet-18 r=4
+  // batch 512, S / 1 / 2 / 4 / 8 = 1.862-1.874 / 1.864 / 1.884 / 1.926 ms, round 4)
+  const bool ext = q.ext_slices > 0 && (q.bwd ? r.vec && r.slab != kBnSlabInKernel : r.training && q.nslab < 2);
+  r.Sp = ext ? q.ext_slices : 0;
+  r.stats_pass = r.training && !ext;
+  return r;
+}
+
+static BnRoute shape_route(int N, int C, int HW, int single, bool pair) {
+  BnQuery q;
+  q.bwd = 1; q.N = N; q.C = C; q.HW = HW; q.single = single != 0; q.pair = pair;
+  return bn_make_route(q);
+}
+int bn_slices(int N, int C, int HW) { return shape_route(N, C, HW, 0, false).S; }
+int64_t bn_part_numel(int N, int C, int HW) { return shape_route(N, C, HW, 0, false).part_numel; }
+bool bn_two_kernel_path(int N, int C, int HW, int single) {
+  return shape_route(N, C, HW, single, false).path == kBnTwoKernel;
+}
+bool bn_pair_ok(int N, int C, int HW) { return shape_route(N, C, HW, 0, true).path == kBnFused; }
+
+// ----------------------------------- launchers -------------------------------------------
+// They execute a route: no launcher decides anything about a shape or a pointer.
+static void sum_slabs_first(const BnOps& o, const BnRoute& r, const float* dst, hipStream_t s) {
+  if (r.slab == kBnSlabSumFirst)
+    launch_slab_sum(o.slabs, const_cast<float*>(dst), (int64_t)r.N * r.C * r.HW, o.nslab, s,
+                    r.addend ? o.addend : nullptr);
+}
+
+// one instantiation of the single-launch kernels: V = 4 the float4 kernel, V = 1 the scalar one
+template <int BWD, int HW, int CW, int MAXN, int PAIR, int V, int SPLIT = 1>
+static void fused_launch(const BnOps& o, const BnRoute& r, const BnPair& pp, hipStream_t s) {
+  const bool in = r.slab == kBnSlabInKernel;
+  const float* src = in ? o.slabs : nullptr;
+  // (the backward kernel's `res` slot: the slab addend)
+  const float* res = BWD ? (in && r.addend ? o.addend : nullptr) : o.res;
+  if constexpr (V == 4) {
+    const BnSplitCtx sx = SPLIT > 1 ? bn_split_ctx(SPLIT) : BnSplitCtx{};
+    hipLaunchKernelGGL((bn_small_fused_v4_kernel<HW, BWD, CW, MAXN, PAIR, SPLIT>), dim3((unsigned)r.grid),
+                       dim3(kFusedThreads), 0, s, o.x, res, o.dy, o.yin, o.gamma, o.beta, o.rmean, o.rvar, o.nbt,
+                       o.save_mean, o.save_invstd, o.dgamma, o.dbeta, o.out, o.dres, r.N, r.C, o.eps, o.momentum,
+                       o.relu, src, o.nslab, pp, sx);
+  } else {
+    hipLaunchKernelGGL((bn_small_fused_kernel<HW, BWD, CW, MAXN, PAIR>), dim3((unsigned)r.grid), dim3(kFusedThreads),
+                       0, s, o.x, res, o.dy, o.yin, o.gamma, o.beta, o.rmean, o.rvar, o.nbt, o.save_mean,
+                       o.save_invstd, o.dgamma, o.dbeta, o.out, o.dres, r.N, r.C, o.eps, o.momentum, o.relu, src,
+                       o.nslab, pp);
+  }
+}
+
+template <int BWD, int HW, int CW>
+static void fused_small(const BnOps& o, const BnRoute& r, const BnPair& pp, hipStream_t s) {
+  if constexpr (CW % HW == 0) {  // the route picks CW >= HW
+    if (r.pair) {  // (no float4 pair below HW = 4: the route never asks for one)
+      if (r.v4) {
+        if constexpr (HW >= 4) fused_launch<BWD, HW, CW, kFusedMaxN, 1, 4>(o, r, pp, s);
+      } else {
+        fused_launch<BWD, HW, CW, kFusedMaxN, 1, 1>(o, r, pp, s);
+      }
+    } else {
+      if (r.v4) fused_launch<BWD, HW, CW, kFusedMaxN, 0, 4>(o, r, pp, s);
+      else fused_launch<BWD, HW, CW, kFusedMaxN, 0, 1>(o, r, pp, s);
+    }
+  }
+}
+
+template <int BWD, int CW>
+static void fused_cw(const BnOps& o, const BnRoute& r, const BnPair& pp, hipStream_t s) {
+  switch (r.HW) {
+    case 1: fused_small<BWD, 1, CW>(o, r, pp, s); break;
+    case 2: fused_small<BWD, 2, CW>(o, r, pp, s); break;
+    case 4: fused_small<BWD, 4, CW>(o, r, pp, s); break;
+    case 8: fused_small<BWD, 8, CW>(o, r, pp, s); break;
+    default: fused_small<BWD, 16, CW>(o, r, pp, s); break;
+  }
+}
+
+// the single-launch paths: one dispatch on the route's (HW, CW, pair, float4, split)
+template <int BWD>
+static void launch_fused(const BnOps& o, const BnRoute& r, const BnPair* pr, hipStream_t s) {
+  BnPair pp = pr ? *pr : BnPair{};
+  if (r.slab2 != kBnSlabInKernel) {
+    pp.src2 = nullptr;
+    pp.nslab2 = 0;
+  }
+  if (r.path == kBnFused64) {
+    if (r.split == 2) fused_launch<BWD, 64, 64, kFusedMaxN64, 0, 4, 2>(o, r, pp, s);
+    else if (r.split == 4) fused_launch<BWD, 64, 64, kFusedMaxN64, 0, 4, 4>(o, r, pp, s);
+    else if (r.v4) fused_launch<BWD, 64, 64, kFusedMaxN64, 0, 4>(o, r, pp, s);
+    else fused_launch<BWD, 64, 64, kFusedMaxN64, 0, 1>(o, r, pp, s);
     return;
   }
-  const bool vec_ok = (HW % 4) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 &&
-                      (res == nullptr || ((uintptr_t)res & 15) == 0) && ((uintptr_t)xpart & 15) == 0;
-  if (xpart != nullptr && !(training && vec_ok && !bn_small_path(N, C, HW))) {
-    // no fused consumer for this shape: finish the conv's split-K sum here
-    launch_slab_sum(xpart, const_cast<float*>(x), (int64_t)N * C * HW, nslab, s);
-    xpart = nullptr;
+  switch (r.CW) {
+    case 16: fused_cw<BWD, 16>(o, r, pp, s); break;
+    case 4: fused_cw<BWD, 4>(o, r, pp, s); break;
+    default: fused_cw<BWD, 8>(o, r, pp, s);
   }
-  if (training && bn_small_path(N, C, HW)) {
-    const int Ss = bn_small_slices(N, C, HW);
-    double* coef = part + (int64_t)C * Ss * 2;
-    small_stats_any(HW, x, nullptr, nullptr, nullptr, nullptr, part, N, C, Ss, 0, 0, s);
-    hipLaunchKernelGGL(bn_small_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, part, coef, gamma, beta, rmean,
-                       rvar, nbt, save_mean, save_invstd, nullptr, nullptr, N, C, HW, Ss, eps, momentum, 0);
-    const int total = N * C * HW;
-    hipLaunchKernelGGL(bn_small_apply_kernel, dim3((unsigned)((total / 4 + 255) / 256 + 1)), dim3(256), 0, s, x, res,
-                       nullptr, nullptr, nullptr, nullptr, coef, y, nullptr, total, C, HW, relu, 0);
-    return;
+}
+
+// the three-kernel small-map path: part = [c][Ss][2] partials, then the coefficients
+static void launch_three(const BnOps& o, const BnRoute& r, hipStream_t s) {
+  const int N = r.N, C = r.C, HW = r.HW, Ss = r.Ss, bwd = r.bwd;
+  double* coef = o.part + (int64_t)C * Ss * 2;
+  const dim3 grid(Ss, (C * HW + 255) / 256);
+  auto stats = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, o.x, o.dy, o.yin, bwd ? o.save_mean : nullptr,
+                       bwd ? o.save_invstd : nullptr, o.part, N, C, Ss, bwd, bwd ? o.relu : 0);
+  };
+  switch (HW) {
+    case 1: stats(bn_small_stats_kernel<1>); break;
+    case 2: stats(bn_small_stats_kernel<2>); break;
+    case 4: stats(bn_small_stats_kernel<4>); break;
+    case 8: stats(bn_small_stats_kernel<8>); break;
+    default: stats(bn_small_stats_kernel<16>); break;
   }
-  const bool vec = (HW % 4) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 &&
-                   (res == nullptr || ((uintptr_t)res & 15) == 0);
-  const dim3 grid(S, C);
-  // statistics from the conv epilogue (xstats): no statistics pass, the apply folds xS partials
-  const double* ap = xstats != nullptr ? xstats : part;
-  const int Sp = xstats != nullptr ? xS : 0;
-  if (training && xstats == nullptr) {  // the statistics pass also adds deferred conv slabs (xpart), writes x
-    if (vec) hipLaunchKernelGGL(bn_fwd_stats_kernel<true>, grid, dim3(256), 0, s, x, part, N, C, HW, S, xpart, nslab);
-    else hipLaunchKernelGGL(bn_fwd_stats_kernel<false>, grid, dim3(256), 0, s, x, part, N, C, HW, S, nullptr, 0);
+  hipLaunchKernelGGL(bn_small_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, o.part, coef, o.gamma, o.beta,
+                     o.rmean, o.rvar, o.nbt, bwd ? nullptr : o.save_mean, o.save_invstd, o.dgamma, o.dbeta, N, C, HW, Ss,
+                     o.eps, o.momentum, bwd);
+  const int total = N * C * HW;
+  hipLaunchKernelGGL(bn_small_apply_kernel, dim3((unsigned)((total / 4 + 255) / 256 + 1)), dim3(256), 0, s, o.x, o.res,
+                     o.dy, o.yin, bwd ? o.save_mean : nullptr, bwd ? o.save_invstd : nullptr, coef, o.out, o.dres,
+                     total, C, HW, o.relu, bwd);
+}
+
+void launch_bn_fwd(const BnOps& o, const BnRoute& r, hipStream_t s) {
+  sum_slabs_first(o, r, o.x, s);
+  if (r.path == kBnFused || r.path == kBnFused64) return launch_fused<0>(o, r, nullptr, s);
+  if (r.path == kBnThreeKernel) return launch_three(o, r, s);
+  const int N = r.N, C = r.C, HW = r.HW;
+  if (r.stats_pass) {  // the statistics pass also adds deferred conv slabs, writes x
+    const dim3 grid(r.S, C);
+    if (r.vec)
+      hipLaunchKernelGGL(bn_fwd_stats_kernel<true>, grid, dim3(256), 0, s, o.x, o.part, N, C, HW, r.S,
+                         r.slab == kBnSlabInKernel ? o.slabs : nullptr, o.nslab);
+    else hipLaunchKernelGGL(bn_fwd_stats_kernel<false>, grid, dim3(256), 0, s, o.x, o.part, N, C, HW, r.S, nullptr, 0);
   }
-  const int Sa = Sp > 0 ? ext_apply_slices(S) : S;
-  const dim3 agrid(Sa, C);
-  if (vec)
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<true>, agrid, dim3(256), 0, s, x, res, y, gamma, beta, rmean, rvar, nbt,
-                       save_mean, save_invstd, ap, N, C, HW, Sa, eps, momentum, relu, training, Sp);
+  const double* ap = r.Sp > 0 ? o.stats : o.part;
+  const dim3 agrid(r.Sa, C);
+  if (r.vec)
+    hipLaunchKernelGGL(bn_fwd_apply_kernel<true>, agrid, dim3(256), 0, s, o.x, o.res, o.out, o.gamma, o.beta, o.rmean,
+                       o.rvar, o.nbt, o.save_mean, o.save_invstd, ap, N, C, HW, r.Sa, o.eps, o.momentum, o.relu,
+                       r.training, r.Sp);
   else
-    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, agrid, dim3(256), 0, s, x, res, y, gamma, beta, rmean, rvar, nbt,
-                       save_mean, save_invstd, ap, N, C, HW, Sa, eps, momentum, relu, training, Sp);
+    hipLaunchKernelGGL(bn_fwd_apply_kernel<false>, agrid, dim3(256), 0, s, o.x, o.res, o.out, o.gamma, o.beta, o.rmean,
+                       o.rvar, o.nbt, o.save_mean, o.save_invstd, ap, N, C, HW, r.Sa, o.eps, o.momentum, o.relu,
+                       r.training, r.Sp);
 }
 
-// training-mode stem tail (bn_relu_maxpool_kernel); xstats as in launch_bn_fwd (nullable)
-void launch_bn_relu_maxpool(const float* x, float* y, uint8_t* idx, const float* gamma, const float* beta,
-                            float* rmean, float* rvar, int64_t* nbt, float* save_mean, float* save_invstd,
-                            double* part, int N, int C, int H, int W, float eps, float momentum, hipStream_t s,
-                            const double* xstats, int xS) {
-  const int HW = H * W;
-  const int S = bn_slices(N, C, HW);
-  const dim3 grid(S, C);
-  if (xstats == nullptr) {
-    const bool vec = (HW % 4) == 0 && ((uintptr_t)x & 15) == 0;
-    if (vec) hipLaunchKernelGGL(bn_fwd_stats_kernel<true>, grid, dim3(256), 0, s, x, part, N, C, HW, S, nullptr, 0);
-    else hipLaunchKernelGGL(bn_fwd_stats_kernel<false>, grid, dim3(256), 0, s, x, part, N, C, HW, S, nullptr, 0);
+// training-mode stem tail (bn_relu_maxpool_kernel)
+void launch_bn_relu_maxpool(const BnOps& o, const BnRoute& r, hipStream_t s) {
+  const int N = r.N, C = r.C, HW = r.HW;
+  if (r.stats_pass) {
+    const dim3 grid(r.S, C);
+    if (r.vec) hipLaunchKernelGGL(bn_fwd_stats_kernel<true>, grid, dim3(256), 0, s, o.x, o.part, N, C, HW, r.S, nullptr, 0);
+    else hipLaunchKernelGGL(bn_fwd_stats_kernel<false>, grid, dim3(256), 0, s, o.x, o.part, N, C, HW, r.S, nullptr, 0);
   }
-  const int Sa = xstats != nullptr ? ext_apply_slices(S) : S;
-  hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(Sa, C), dim3(256), 0, s, x, y, idx, gamma, beta, rmean, rvar, nbt,
-                     save_mean, save_invstd, xstats != nullptr ? xstats : part, N, C, H, W, Sa, eps, momentum,
-                     xstats != nullptr ? xS : 0);
+  hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(r.Sa, C), dim3(256), 0, s, o.x, o.out, o.idx, o.gamma, o.beta,
+                     o.rmean, o.rvar, o.nbt, o.save_mean, o.save_invstd, r.Sp > 0 ? o.stats : o.part, N, C, HW / r.pool_w,
+                     r.pool_w, r.Sa, o.eps, o.momentum, r.Sp);
 }
 
 // The downsample block's two BatchNorms in one launch (BnPair): the small-map single-launch
 // kernels, i.e. layers 2-4 of the ResNet-18 step at per-GPU batch <= 512 (not the 8x8 maps).
-bool bn_pair_ok(int N, int C, int HW) { return HW != 64 && bn_fused_ok(N, C, HW); }
-
-void launch_bn_pair_fwd(const float* x, const float* x2, float* y, const float* gamma, const float* beta,
-                        float* rmean, float* rvar, int64_t* nbt, float* save_mean, float* save_invstd,
-                        const float* gamma2, const float* beta2, float* rmean2, float* rvar2, int64_t* nbt2,
-                        float* save_mean2, float* save_invstd2, int N, int C, int HW, float eps, float momentum,
-                        hipStream_t s, const float* xpart, int nslab, const float* x2part, int nslab2) {
-  if (xpart != nullptr && nslab < 2) xpart = nullptr;
-  if (xpart != nullptr && nslab > kMaxFusedSlabs) {
-    launch_slab_sum(xpart, const_cast<float*>(x), (int64_t)N * C * HW, nslab, s);
-    xpart = nullptr;
-  }
-  if (x2part != nullptr && nslab2 < 2) x2part = nullptr;
-  if (x2part != nullptr && nslab2 > kMaxFusedSlabs) {
-    launch_slab_sum(x2part, const_cast<float*>(x2), (int64_t)N * C * HW, nslab2, s);
-    x2part = nullptr;
-  }
-  const BnPair pr{x2, gamma2, beta2, rmean2, rvar2, nbt2, save_mean2, save_invstd2, nullptr, nullptr, nullptr,
-                  x2part, x2part ? nslab2 : 0};
-  launch_small_fused<0>(HW, x, nullptr, nullptr, nullptr, gamma, beta, rmean, rvar, nbt, save_mean, save_invstd,
-                        nullptr, nullptr, y, nullptr, N, C, eps, momentum, 1, s, xpart, nslab, &pr);
+void launch_bn_pair_fwd(const BnOps& o, const BnPair& pr, const BnRoute& r, hipStream_t s) {
+  sum_slabs_first(o, r, o.x, s);
+  if (r.slab2 == kBnSlabSumFirst)
+    launch_slab_sum(pr.src2, const_cast<float*>(pr.x2), (int64_t)r.N * r.C * r.HW, pr.nslab2, s);
+  launch_fused<0>(o, r, &pr, s);
 }
 
-void launch_bn_pair_bwd(const float* dy, const float* y, const float* x, const float* x2, const float* gamma,
-                        const float* save_mean, const float* save_invstd, const float* gamma2,
-                        const float* save_mean2, const float* save_invstd2, float* dx, float* dx2, float* dgamma,
-                        float* dbeta, float* dgamma2, float* dbeta2, int N, int C, int HW, hipStream_t s,
-                        const float* dypart, int nslab, const float* dyadd) {
-  if (dypart != nullptr && nslab < 2) dypart = nullptr;
-  if (dypart == nullptr) dyadd = nullptr;
-  if (dypart != nullptr && nslab > kMaxFusedSlabs) {
-    launch_slab_sum(dypart, const_cast<float*>(dy), (int64_t)N * C * HW, nslab, s, dyadd);
-    dypart = nullptr;
-    dyadd = nullptr;
-  }
-  const BnPair pr{x2, gamma2, nullptr, nullptr, nullptr, nullptr, const_cast<float*>(save_mean2),
-                  const_cast<float*>(save_invstd2), dgamma2, dbeta2, dx2, nullptr, 0};
-  launch_small_fused<1>(HW, x, dyadd, dy, y, gamma, nullptr, nullptr, nullptr, nullptr, const_cast<float*>(save_mean),
-                        const_cast<float*>(save_invstd), dgamma, dbeta, dx, nullptr, N, C, 0.f, 0.f, 1, s, dypart,
-                        nslab, &pr);
+void launch_bn_pair_bwd(const BnOps& o, const BnPair& pr, const BnRoute& r, hipStream_t s) {
+  sum_slabs_first(o, r, o.dy, s);
+  launch_fused<1>(o, r, &pr, s);
 }
 
-bool bn_two_kernel_path(int N, int C, int HW, int single) {
-  return !(single && bn_fused_ok(N, C, HW)) && !bn_small_path(N, C, HW);
-}
-
-void launch_bn_bwd(const float* dy, const float* y, const float* x, const float* gamma, const float* save_mean,
-                   const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, double* part,
-                   int N, int C, int HW, int S, int relu, int single, hipStream_t s, const float* dypart,
-                   int nslab, const float* dyadd, const float* mbeta, const double* dstats, int dS) {
-  if (dypart != nullptr && nslab < 2) dypart = nullptr;
-  if (dypart == nullptr) dyadd = nullptr;
-  if (dypart != nullptr && nslab > kMaxFusedSlabs) {
-    launch_slab_sum(dypart, const_cast<float*>(dy), (int64_t)N * C * HW, nslab, s, dyadd);
-    dypart = nullptr;
-    dyadd = nullptr;
-  }
-  if (single && bn_fused_ok(N, C, HW)) {  // (the backward kernel's `res` slot: the slab addend)
-    launch_small_fused<1>(HW, x, dyadd, dy, y, gamma, nullptr, nullptr, nullptr, nullptr,
-                          const_cast<float*>(save_mean), const_cast<float*>(save_invstd), dgamma, dbeta, dx, dres, N, C,
-                          0.f, 0.f, relu, s, dypart, nslab);
-    return;
-  }
-  const bool vec_ok = (HW % 4) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 &&
-                      ((uintptr_t)dx & 15) == 0 && (!relu || ((uintptr_t)y & 15) == 0) &&
-                      (dres == nullptr || ((uintptr_t)dres & 15) == 0) && ((uintptr_t)dypart & 15) == 0;
-  if (dypart != nullptr && !(vec_ok && !bn_small_path(N, C, HW) &&
-                             (dyadd == nullptr || ((uintptr_t)dyadd & 15) == 0))) {
-    // no fused consumer: finish the conv's split-K grad-x sum into dy
-    launch_slab_sum(dypart, const_cast<float*>(dy), (int64_t)N * C * HW, nslab, s, dyadd);
-    dypart = nullptr;
-    dyadd = nullptr;
-  }
-  if (bn_small_path(N, C, HW)) {
-    const int Ss = bn_small_slices(N, C, HW);
-    double* coef = part + (int64_t)C * Ss * 2;
-    small_stats_any(HW, x, dy, y, save_mean, save_invstd, part, N, C, Ss, 1, relu, s);
-    hipLaunchKernelGGL(bn_small_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, part, coef, gamma, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, const_cast<float*>(save_invstd), dgamma, dbeta, N, C, HW, Ss,
-                       0.f, 0.f, 1);
-    const int total = N * C * HW;
-    hipLaunchKernelGGL(bn_small_apply_kernel, dim3((unsigned)((total / 4 + 255) / 256 + 1)), dim3(256), 0, s, x,
-                       nullptr, dy, y, save_mean, save_invstd, coef, dx, dres, total, C, HW, relu, 1);
-    return;
-  }
-  const bool vec = (HW % 4) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 &&
-                   ((uintptr_t)dx & 15) == 0 && (!relu || ((uintptr_t)y & 15) == 0) &&
-                   (dres == nullptr || ((uintptr_t)dres & 15) == 0);
-  const dim3 grid(S, C);
-  if (vec) {  // the statistics pass also adds deferred grad-x slabs (dypart) and writes dy
-    // (dstats: the statistics came from the producing conv's grad-x epilogue, no pass)
-    if (dstats == nullptr || dypart != nullptr)
-      hipLaunchKernelGGL(bn_bwd_stats_kernel<true>, grid, dim3(256), 0, s, dy, y, x, save_mean, save_invstd, part, N,
-                         C, HW, S, relu, dypart, nslab, dyadd, gamma, mbeta);
-    const bool ext_st = dstats != nullptr && dypart == nullptr;
-    const int Sa = ext_st ? ext_apply_slices(S) : S;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(Sa, C), dim3(256), 0, s, dy, y, x, gamma, save_mean,
-                       save_invstd, dx, dres, dgamma, dbeta, ext_st ? dstats : part, N, C, HW, Sa, relu, mbeta,
-                       ext_st ? dS : 0);
+void launch_bn_bwd(const BnOps& o, const BnRoute& r, hipStream_t s) {
+  sum_slabs_first(o, r, o.dy, s);
+  if (r.path == kBnFused || r.path == kBnFused64) return launch_fused<1>(o, r, nullptr, s);
+  if (r.path == kBnThreeKernel) return launch_three(o, r, s);
+  const int N = r.N, C = r.C, HW = r.HW;
+  const dim3 grid(r.S, C);
+  if (r.vec) {  // the statistics pass also adds deferred grad-x slabs and writes dy
+    const bool in = r.slab == kBnSlabInKernel;
+    if (r.stats_pass)
+      hipLaunchKernelGGL(bn_bwd_stats_kernel<true>, grid, dim3(256), 0, s, o.dy, o.yin, o.x, o.save_mean, o.save_invstd,
+                         o.part, N, C, HW, r.S, o.relu, in ? o.slabs : nullptr, o.nslab,
+                         in && r.addend ? o.addend : nullptr, o.gamma, o.mbeta);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(r.Sa, C), dim3(256), 0, s, o.dy, o.yin, o.x, o.gamma,
+                       o.save_mean, o.save_invstd, o.out, o.dres, o.dgamma, o.dbeta, r.Sp > 0 ? o.stats : o.part, N, C, HW,
+                       r.Sa, o.relu, o.mbeta, r.Sp);
   } else {
-    hipLaunchKernelGGL(bn_bwd_stats_kernel<false>, grid, dim3(256), 0, s, dy, y, x, save_mean, save_invstd, part, N,
-                       C, HW, S, relu);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(256), 0, s, dy, y, x, gamma, save_mean, save_invstd, dx,
-                       dres, dgamma, dbeta, part, N, C, HW, S, relu);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel<false>, grid, dim3(256), 0, s, o.dy, o.yin, o.x, o.save_mean, o.save_invstd,
+                       o.part, N, C, HW, r.S, o.relu);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(256), 0, s, o.dy, o.yin, o.x, o.gamma, o.save_mean,
+                       o.save_invstd, o.out, o.dres, o.dgamma, o.dbeta, o.part, N, C, HW, r.S, o.relu);
   }
 }
 

@@ -389,6 +389,51 @@ void slab_sum(torch::Tensor part, torch::Tensor out, int64_t nslab) {
   check_launch("launch_slab_sum");
 }
 
+static double* bn_part(torch::Tensor& part) {
+  TORCH_CHECK(part.scalar_type() == torch::kFloat64, "bn part must be float64");
+  return part.data_ptr<double>();
+}
+
+// the operands every BN forward has (part: null for the pair, which needs no scratch)
+static ndp::BnOps bn_fwd_ops(const torch::Tensor& x, torch::Tensor& y, const c10::optional<torch::Tensor>& gamma,
+                             const c10::optional<torch::Tensor>& beta, const c10::optional<torch::Tensor>& rmean,
+                             const c10::optional<torch::Tensor>& rvar, const c10::optional<torch::Tensor>& nbt,
+                             torch::Tensor& save_mean, torch::Tensor& save_invstd, torch::Tensor* part, double eps,
+                             double momentum) {
+  ndp::BnOps o;
+  o.x = x.data_ptr<float>();
+  o.out = y.data_ptr<float>();
+  o.gamma = opt_f32(gamma, "gamma");
+  o.beta = opt_f32(beta, "beta");
+  o.rmean = const_cast<float*>(opt_f32(rmean, "running_mean"));
+  o.rvar = const_cast<float*>(opt_f32(rvar, "running_var"));
+  if (nbt.has_value()) {
+    check_dev(*nbt, "nbt");
+    TORCH_CHECK(nbt->scalar_type() == torch::kInt64, "num_batches_tracked must be int64");
+    o.nbt = nbt->data_ptr<int64_t>();
+  }
+  o.save_mean = save_mean.data_ptr<float>();
+  o.save_invstd = save_invstd.data_ptr<float>();
+  o.part = part ? bn_part(*part) : nullptr;
+  o.eps = (float)eps;
+  o.momentum = (float)momentum;
+  return o;
+}
+
+// xstats / dstats: [C][S][2] fp64 partial sums from the producing conv's epilogue
+static const double* ext_stats(const torch::Tensor& st, int C, int64_t S, const char* who) {
+  check_dev(st, "stats");
+  TORCH_CHECK(st.scalar_type() == torch::kFloat64 && st.is_contiguous() && S > 0 && st.numel() >= (int64_t)C * S * 2,
+              who, ": the conv's statistics must hold C * S * 2 doubles");
+  return st.data_ptr<double>();
+}
+
+static ndp::BnQuery bn_query(int bwd, int N, int C, int HW, bool single, int nslab, int ext_slices) {
+  ndp::BnQuery q;
+  q.bwd = bwd; q.N = N; q.C = C; q.HW = HW; q.single = single; q.nslab = nslab; q.ext_slices = ext_slices;
+  return q;
+}
+
 // fused BN(+res)(+relu) forward; returns nothing, writes y / save_mean / save_invstd
 void bn_fwd(torch::Tensor x, c10::optional<torch::Tensor> res, torch::Tensor y,
             c10::optional<torch::Tensor> gamma, c10::optional<torch::Tensor> beta,
@@ -402,33 +447,25 @@ void bn_fwd(torch::Tensor x, c10::optional<torch::Tensor> res, torch::Tensor y,
   TORCH_CHECK(x.dim() >= 2 && x.sizes() == y.sizes(), "bn_fwd: bad shapes");
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int HW = (int)(x.numel() / ((int64_t)N * C));
-  const int S = ndp::bn_slices(N, C, HW);
-  TORCH_CHECK(part.scalar_type() == torch::kFloat64 && part.numel() >= ndp::bn_part_numel(N, C, HW),
-              "bn part too small");
   TORCH_CHECK(save_mean.numel() >= C && save_invstd.numel() >= C, "bn save buffers too small");
   if (res.has_value()) TORCH_CHECK(res->sizes() == x.sizes(), "bn residual shape");
-  int64_t* nb = nullptr;
-  if (nbt.has_value()) {
-    check_dev(*nbt, "nbt");
-    TORCH_CHECK(nbt->scalar_type() == torch::kInt64, "num_batches_tracked must be int64");
-    nb = nbt->data_ptr<int64_t>();
-  }
-  const float* xp = slab_input(xpart, nslab, x.numel(), "bn_fwd");
-  TORCH_CHECK(xp == nullptr || training, "bn_fwd: deferred conv slabs need training mode");
-  const double* xst = nullptr;
+  ndp::BnOps o = bn_fwd_ops(x, y, gamma, beta, rmean, rvar, nbt, save_mean, save_invstd, &part, eps, momentum);
+  o.res = opt_f32(res, "res");
+  o.relu = relu ? 1 : 0;
+  o.slabs = slab_input(xpart, nslab, x.numel(), "bn_fwd");
+  o.nslab = (int)nslab;
+  TORCH_CHECK(o.slabs == nullptr || training, "bn_fwd: deferred conv slabs need training mode");
   if (xstats.has_value()) {  // [C][xS][2] partial sums from the producing conv's epilogue
-    check_dev(*xstats, "xstats");
-    TORCH_CHECK(xstats->scalar_type() == torch::kFloat64 && xstats->is_contiguous() && xS > 0 &&
-                    xstats->numel() >= (int64_t)C * xS * 2 && training && xp == nullptr,
-                "bn_fwd: xstats must hold C * xS * 2 doubles (training, no deferred slabs)");
-    xst = xstats->data_ptr<double>();
+    TORCH_CHECK(training && o.slabs == nullptr, "bn_fwd: xstats need training mode and no deferred slabs");
+    o.stats = ext_stats(*xstats, C, xS, "bn_fwd");
   }
-  ndp::launch_bn_fwd(x.data_ptr<float>(), opt_f32(res, "res"), y.data_ptr<float>(), opt_f32(gamma, "gamma"),
-                     opt_f32(beta, "beta"), const_cast<float*>(opt_f32(rmean, "running_mean")),
-                     const_cast<float*>(opt_f32(rvar, "running_var")), nb, save_mean.data_ptr<float>(),
-                     save_invstd.data_ptr<float>(), part.data_ptr<double>(), N, C, HW, S, (float)eps,
-                     (float)momentum, relu ? 1 : 0, training ? 1 : 0, single ? 1 : 0, cur_stream(), xp, (int)nslab,
-                     xst, (int)xS);
+  ndp::BnQuery q = bn_query(0, N, C, HW, single, o.slabs ? (int)nslab : 0, o.stats ? (int)xS : 0);
+  q.training = training;
+  q.relu = relu;
+  q.al = ndp::bn_alignment(0, o);
+  const ndp::BnRoute r = ndp::bn_make_route(q);
+  TORCH_CHECK(part.numel() >= r.part_numel, "bn part too small");
+  ndp::launch_bn_fwd(o, r, cur_stream());
   check_launch("launch_bn_fwd");
 }
 
@@ -447,30 +484,42 @@ void bn_relu_maxpool(torch::Tensor x, torch::Tensor y, torch::Tensor idx, c10::o
                   y.size(3) == OW, "bn_relu_maxpool: y must be [N, C, (H-1)/2+1, (W-1)/2+1]");
   TORCH_CHECK(idx.scalar_type() == torch::kUInt8 && idx.is_contiguous() && idx.sizes() == y.sizes(),
               "bn_relu_maxpool: uint8 idx shaped like y");
-  TORCH_CHECK(part.scalar_type() == torch::kFloat64 && part.numel() >= ndp::bn_part_numel(N, C, H * W),
-              "bn part too small");
   TORCH_CHECK(save_mean.numel() >= C && save_invstd.numel() >= C, "bn save buffers too small");
   TORCH_CHECK((int64_t)N * C * H * W < (1LL << 31), "bn_relu_maxpool: tensor too large");
-  int64_t* nb = nullptr;
-  if (nbt.has_value()) {
-    check_dev(*nbt, "nbt");
-    TORCH_CHECK(nbt->scalar_type() == torch::kInt64, "num_batches_tracked must be int64");
-    nb = nbt->data_ptr<int64_t>();
-  }
-  const double* xst = nullptr;
-  if (xstats.has_value()) {
-    check_dev(*xstats, "xstats");
-    TORCH_CHECK(xstats->scalar_type() == torch::kFloat64 && xstats->is_contiguous() && xS > 0 &&
-                    xstats->numel() >= (int64_t)C * xS * 2, "bn_relu_maxpool: xstats must hold C * xS * 2 doubles");
-    xst = xstats->data_ptr<double>();
-  }
-  ndp::launch_bn_relu_maxpool(x.data_ptr<float>(), y.data_ptr<float>(), idx.data_ptr<uint8_t>(),
-                              opt_f32(gamma, "gamma"), opt_f32(beta, "beta"),
-                              const_cast<float*>(opt_f32(rmean, "running_mean")),
-                              const_cast<float*>(opt_f32(rvar, "running_var")), nb, save_mean.data_ptr<float>(),
-                              save_invstd.data_ptr<float>(), part.data_ptr<double>(), N, C, H, W, (float)eps,
-                              (float)momentum, cur_stream(), xst, (int)xS);
+  ndp::BnOps o = bn_fwd_ops(x, y, gamma, beta, rmean, rvar, nbt, save_mean, save_invstd, &part, eps, momentum);
+  o.idx = idx.data_ptr<uint8_t>();
+  if (xstats.has_value()) o.stats = ext_stats(*xstats, C, xS, "bn_relu_maxpool");
+  ndp::BnQuery q = bn_query(0, N, C, H * W, false, 0, o.stats ? (int)xS : 0);
+  q.pool_w = W;
+  q.al = ndp::bn_alignment(0, o);
+  const ndp::BnRoute r = ndp::bn_make_route(q);
+  TORCH_CHECK(part.numel() >= r.part_numel, "bn part too small");
+  ndp::launch_bn_relu_maxpool(o, r, cur_stream());
   check_launch("launch_bn_relu_maxpool");
+}
+
+// the operands every BN backward has (bn_bwd, bn_pair_bwd)
+static ndp::BnOps bn_bwd_ops(const torch::Tensor& dy, const c10::optional<torch::Tensor>& y, const torch::Tensor& x,
+                             const c10::optional<torch::Tensor>& gamma, torch::Tensor& save_mean,
+                             torch::Tensor& save_invstd, torch::Tensor& dx, const c10::optional<torch::Tensor>& dgamma,
+                             const c10::optional<torch::Tensor>& dbeta, bool relu,
+                             const c10::optional<torch::Tensor>& dypart, int64_t nslab,
+                             const c10::optional<torch::Tensor>& dyadd) {
+  ndp::BnOps o;
+  o.dy = dy.data_ptr<float>();
+  o.yin = opt_f32(y, "y");
+  o.x = x.data_ptr<float>();
+  o.gamma = opt_f32(gamma, "gamma");
+  o.save_mean = save_mean.data_ptr<float>();
+  o.save_invstd = save_invstd.data_ptr<float>();
+  o.out = dx.data_ptr<float>();
+  o.dgamma = const_cast<float*>(opt_f32(dgamma, "dgamma"));
+  o.dbeta = const_cast<float*>(opt_f32(dbeta, "dbeta"));
+  o.relu = relu ? 1 : 0;
+  o.slabs = slab_input(dypart, nslab, dy.numel(), "bn_bwd");
+  o.nslab = (int)nslab;
+  o.addend = opt_f32(dyadd, "dyadd");
+  return o;
 }
 
 void bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor> y, torch::Tensor x, c10::optional<torch::Tensor> gamma,
@@ -489,29 +538,27 @@ void bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor> y, torch::Tensor x, c
   TORCH_CHECK(!relu || y.has_value() || mbeta.has_value(), "bn_bwd: relu needs y (or mbeta)");
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int HW = (int)(x.numel() / ((int64_t)N * C));
-  const int S = ndp::bn_slices(N, C, HW);
-  TORCH_CHECK(part.scalar_type() == torch::kFloat64 && part.numel() >= ndp::bn_part_numel(N, C, HW),
-              "bn part too small");
-  const double* dst = nullptr;
+  ndp::BnOps o = bn_bwd_ops(dy, y, x, gamma, save_mean, save_invstd, dx, dgamma, dbeta, relu, dypart, nslab, dyadd);
+  o.dres = const_cast<float*>(opt_f32(dres, "dres"));
+  o.part = bn_part(part);
   if (dstats.has_value()) {  // [C][dS][2] partial sums from the producing conv's grad-x epilogue
-    check_dev(*dstats, "dstats");
-    TORCH_CHECK(dstats->scalar_type() == torch::kFloat64 && dstats->is_contiguous() && dS > 0 &&
-                    dstats->numel() >= (int64_t)C * dS * 2 && !dypart.has_value(),
-                "bn_bwd: dstats must hold C * dS * 2 doubles (no slabs)");
-    dst = dstats->data_ptr<double>();
+    TORCH_CHECK(!dypart.has_value(), "bn_bwd: dstats come without slabs");
+    o.stats = ext_stats(*dstats, C, dS, "bn_bwd");
   }
-  if (mbeta.has_value()) {  // ReLU mask recomputed from x: the vectorised two-kernel path only
+  if (mbeta.has_value()) {  // ReLU mask recomputed from x
     check_f32(*mbeta, "mbeta");
-    TORCH_CHECK(relu && !y.has_value() && !dypart.has_value() && mbeta->numel() >= C && HW % 4 == 0 &&
-                    ndp::bn_two_kernel_path(N, C, HW, single ? 1 : 0),
-                "bn_bwd: mbeta needs relu, no y, no slabs, HW % 4 == 0 and the large-map path");
+    TORCH_CHECK(!y.has_value() && !dypart.has_value() && mbeta->numel() >= C, "bn_bwd: mbeta needs no y and no slabs");
+    o.mbeta = mbeta->data_ptr<float>();
   }
-  ndp::launch_bn_bwd(dy.data_ptr<float>(), opt_f32(y, "y"), x.data_ptr<float>(), opt_f32(gamma, "gamma"),
-                     save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), dx.data_ptr<float>(),
-                     const_cast<float*>(opt_f32(dres, "dres")), const_cast<float*>(opt_f32(dgamma, "dgamma")),
-                     const_cast<float*>(opt_f32(dbeta, "dbeta")), part.data_ptr<double>(), N, C, HW, S,
-                     relu ? 1 : 0, single ? 1 : 0, cur_stream(), slab_input(dypart, nslab, dy.numel(), "bn_bwd"),
-                     (int)nslab, opt_f32(dyadd, "dyadd"), opt_f32(mbeta, "mbeta"), dst, (int)dS);
+  ndp::BnQuery q = bn_query(1, N, C, HW, single, o.slabs ? (int)nslab : 0, o.stats ? (int)dS : 0);
+  q.relu = relu;
+  q.addend = o.addend != nullptr;
+  q.mbeta = o.mbeta != nullptr;
+  q.al = ndp::bn_alignment(1, o);
+  const ndp::BnRoute r = ndp::bn_make_route(q);
+  TORCH_CHECK(r.path != ndp::kBnNone, "bn_bwd: mbeta needs relu, HW % 4 == 0 and the large-map path");
+  TORCH_CHECK(part.numel() >= r.part_numel, "bn part too small");
+  ndp::launch_bn_bwd(o, r, cur_stream());
   check_launch("launch_bn_bwd");
 }
 
@@ -529,20 +576,28 @@ void bn_pair_fwd(torch::Tensor x, torch::Tensor x2, torch::Tensor y, torch::Tens
                   x2.is_contiguous() && y.is_contiguous(), "bn_pair_fwd: x, x2, y must be contiguous, one shape");
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int HW = (int)(x.numel() / ((int64_t)N * C));
-  TORCH_CHECK(ndp::bn_pair_ok(N, C, HW), "bn_pair_fwd: shape outside the single-launch path (bn_pair_ok)");
   for (auto* t : {&gamma, &beta, &rmean, &rvar, &save_mean, &save_invstd, &gamma2, &beta2, &rmean2, &rvar2,
                   &save_mean2, &save_invstd2})
     TORCH_CHECK(t->numel() >= C, "bn_pair_fwd: per-channel operand too small");
-  check_dev(nbt, "nbt"); check_dev(nbt2, "nbt2");
-  TORCH_CHECK(nbt.scalar_type() == torch::kInt64 && nbt2.scalar_type() == torch::kInt64, "num_batches_tracked int64");
-  ndp::launch_bn_pair_fwd(x.data_ptr<float>(), x2.data_ptr<float>(), y.data_ptr<float>(), gamma.data_ptr<float>(),
-                          beta.data_ptr<float>(), rmean.data_ptr<float>(), rvar.data_ptr<float>(),
-                          nbt.data_ptr<int64_t>(), save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
-                          gamma2.data_ptr<float>(), beta2.data_ptr<float>(), rmean2.data_ptr<float>(),
-                          rvar2.data_ptr<float>(), nbt2.data_ptr<int64_t>(), save_mean2.data_ptr<float>(),
-                          save_invstd2.data_ptr<float>(), N, C, HW, (float)eps, (float)momentum, cur_stream(),
-                          slab_input(xpart, nslab, x.numel(), "bn_pair_fwd"), (int)nslab,
-                          slab_input(x2part, nslab2, x.numel(), "bn_pair_fwd"), (int)nslab2);
+  check_dev(nbt2, "nbt2");
+  TORCH_CHECK(nbt2.scalar_type() == torch::kInt64, "num_batches_tracked must be int64");
+  ndp::BnOps o = bn_fwd_ops(x, y, gamma, beta, rmean, rvar, nbt, save_mean, save_invstd, nullptr, eps, momentum);
+  o.relu = 1;
+  o.slabs = slab_input(xpart, nslab, x.numel(), "bn_pair_fwd");
+  o.nslab = (int)nslab;
+  const float* x2p = slab_input(x2part, nslab2, x.numel(), "bn_pair_fwd");
+  const ndp::BnPair pr{x2.data_ptr<float>(), gamma2.data_ptr<float>(), beta2.data_ptr<float>(),
+                       rmean2.data_ptr<float>(), rvar2.data_ptr<float>(), nbt2.data_ptr<int64_t>(),
+                       save_mean2.data_ptr<float>(), save_invstd2.data_ptr<float>(), nullptr, nullptr, nullptr, x2p,
+                       x2p ? (int)nslab2 : 0};
+  ndp::BnQuery q = bn_query(0, N, C, HW, true, o.slabs ? (int)nslab : 0, 0);
+  q.pair = true;
+  q.relu = true;
+  q.nslab2 = pr.nslab2;
+  q.al = ndp::bn_alignment(0, o, &pr);
+  const ndp::BnRoute r = ndp::bn_make_route(q);
+  TORCH_CHECK(r.path != ndp::kBnNone, "bn_pair_fwd: shape outside the single-launch path (bn_pair_ok)");
+  ndp::launch_bn_pair_fwd(o, pr, r, cur_stream());
   check_launch("launch_bn_pair_fwd");
 }
 
@@ -564,14 +619,18 @@ void bn_pair_bwd(torch::Tensor dy, torch::Tensor y, torch::Tensor x, torch::Tens
   }
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int HW = (int)(x.numel() / ((int64_t)N * C));
-  TORCH_CHECK(ndp::bn_pair_ok(N, C, HW), "bn_pair_bwd: shape outside the single-launch path (bn_pair_ok)");
-  ndp::launch_bn_pair_bwd(dy.data_ptr<float>(), y.data_ptr<float>(), x.data_ptr<float>(), x2.data_ptr<float>(),
-                          gamma.data_ptr<float>(), save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
-                          gamma2.data_ptr<float>(), save_mean2.data_ptr<float>(), save_invstd2.data_ptr<float>(),
-                          dx.data_ptr<float>(), dx2.data_ptr<float>(), dgamma.data_ptr<float>(),
-                          dbeta.data_ptr<float>(), dgamma2.data_ptr<float>(), dbeta2.data_ptr<float>(), N, C, HW,
-                          cur_stream(), slab_input(dypart, nslab, dy.numel(), "bn_pair_bwd"), (int)nslab,
-                          opt_f32(dyadd, "dyadd"));
+  const ndp::BnOps o = bn_bwd_ops(dy, y, x, gamma, save_mean, save_invstd, dx, dgamma, dbeta, true, dypart, nslab, dyadd);
+  const ndp::BnPair pr{x2.data_ptr<float>(), gamma2.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr,
+                       save_mean2.data_ptr<float>(), save_invstd2.data_ptr<float>(), dgamma2.data_ptr<float>(),
+                       dbeta2.data_ptr<float>(), dx2.data_ptr<float>(), nullptr, 0};
+  ndp::BnQuery q = bn_query(1, N, C, HW, true, o.slabs ? (int)nslab : 0, 0);
+  q.pair = true;
+  q.relu = true;
+  q.addend = o.addend != nullptr;
+  q.al = ndp::bn_alignment(1, o, &pr);
+  const ndp::BnRoute r = ndp::bn_make_route(q);
+  TORCH_CHECK(r.path != ndp::kBnNone, "bn_pair_bwd: shape outside the single-launch path (bn_pair_ok)");
+  ndp::launch_bn_pair_bwd(o, pr, r, cur_stream());
   check_launch("launch_bn_pair_bwd");
 }
 
@@ -664,8 +723,19 @@ void stem_pool_bwd_apply(torch::Tensor dy, torch::Tensor idx, torch::Tensor x, c
   check_launch("launch_stem_pool_bwd_apply");
 }
 
-int bn_slices(int N, int C, int HW) { return ndp::bn_slices(N, C, HW); }
-int64_t bn_part_numel(int N, int C, int HW) { return ndp::bn_part_numel(N, C, HW); }
+// What a BN call with these facts would launch (batchnorm.hip bn_make_route), host code only:
+// (path, v4, CW, MAXN, split, grid, vec, S, Sa, stats_pass, Sp, Ss, slab, slab2, addend, part_numel);
+// `align` = (fused, two, slabs, slabs2), the BnAlign bools.  tools/bn_route_table.py names the values.
+py::tuple bn_route(bool bwd, int N, int C, int HW, bool training, bool single, bool pair, int pool_w, int nslab,
+                   int nslab2, int ext_slices, bool relu, bool addend, bool mbeta, std::array<bool, 4> align) {
+  ndp::BnQuery q = bn_query(bwd ? 1 : 0, N, C, HW, single, nslab, ext_slices);
+  q.training = training; q.pair = pair; q.pool_w = pool_w; q.nslab2 = nslab2;
+  q.relu = relu; q.addend = addend; q.mbeta = mbeta;
+  q.al.fused = align[0]; q.al.two = align[1]; q.al.slabs = align[2]; q.al.slabs2 = align[3];
+  const ndp::BnRoute r = ndp::bn_make_route(q);
+  return py::make_tuple(r.path, r.v4, r.CW, r.MAXN, r.split, r.grid, r.vec, r.S, r.Sa, r.stats_pass, r.Sp, r.Ss, r.slab,
+                        r.slab2, r.addend, r.part_numel);
+}
 
 void delay_ns(int64_t ns) {
   ndp::launch_delay_ns(ns, cur_stream());
@@ -1552,9 +1622,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("conv_pair_launches", &ndp::conv_pair_launches);
   m.def("wino_set_wgrad_prefetch", &ndp::wino_set_wgrad_prefetch);
-  m.def("bn_slices", &bn_slices);
+  m.def("bn_slices", &ndp::bn_slices);
+  m.def("bn_route", &bn_route, py::arg("bwd"), py::arg("N"), py::arg("C"), py::arg("HW"), py::arg("training") = true,
+        py::arg("single") = false, py::arg("pair") = false, py::arg("pool_w") = 0, py::arg("nslab") = 0,
+        py::arg("nslab2") = 0, py::arg("ext_slices") = 0, py::arg("relu") = false, py::arg("addend") = false,
+        py::arg("mbeta") = false, py::arg("align") = std::array<bool, 4>{true, true, true, true});
   m.def("slab_sum", &slab_sum);
-  m.def("bn_part_numel", &bn_part_numel);
+  m.def("bn_part_numel", &ndp::bn_part_numel);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("maxpool_bwd_bnstats", &maxpool_bwd_bnstats, py::arg("dy"), py::arg("idx"), py::arg("dx"), py::arg("x"),

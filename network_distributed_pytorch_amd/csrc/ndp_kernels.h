@@ -177,51 +177,113 @@ void launch_checksum(const float* x, int64_t n, double* out, hipStream_t s);
 }  // namespace ndp
 
 // ---- fused BatchNorm2d (+residual) (+ReLU), NCHW fp32 (batchnorm.hip) -------------------
+// A call is decided once: the binding states what it offers in a BnQuery, bn_make_route answers
+// with a BnRoute, validates against it and hands it to the launcher, which only executes it.
 namespace ndp {
-int bn_slices(int N, int C, int HW);
-// doubles of `part` scratch a (N, C, HW) BN needs (large-map slices or the small-map path)
-int64_t bn_part_numel(int N, int C, int HW);
-// part: C * S * 2 doubles of scratch; rmean/rvar/nbt may be null; training=0 uses running stats;
-// single: allow the one-launch small-map path (HW <= 4, N <= 512)
-void launch_bn_fwd(const float* x, const float* res, float* y, const float* gamma, const float* beta,
-                   float* rmean, float* rvar, int64_t* nbt, float* save_mean, float* save_invstd,
-                   double* part, int N, int C, int HW, int S, float eps, float momentum, int relu,
-                   int training, int single, hipStream_t s, const float* xpart = nullptr, int nslab = 0,
-                   const double* xstats = nullptr, int xS = 0);
-// xstats (nullable, training): [C][xS][2] fp64 partial sums of x from the producing conv's
-// epilogue (ConvPlan::fwd_stats_slices); the large-map path then skips its statistics pass
-// xpart / dypart (nullable): the input x (forward) / dy (backward) is the sum of `nslab`
-// split-K slabs of numel(x) floats (a deferred conv sum); the forward also writes the sum to x
-void launch_bn_bwd(const float* dy, const float* y, const float* x, const float* gamma, const float* save_mean,
-                   const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, double* part,
-                   int N, int C, int HW, int S, int relu, int single, hipStream_t s, const float* dypart = nullptr,
-                   int nslab = 0, const float* dyadd = nullptr, const float* mbeta = nullptr,
-                   const double* dstats = nullptr, int dS = 0);
-// dstats (nullable; large-map path, no slabs): [C][dS][2] partial sums of dz and dz * xhat from the
-// grad-x epilogue of the conv that produced dy (conv_dgrad bst); the statistics pass is skipped
-// mbeta (nullable, relu, two-kernel path only): y was never stored; the ReLU mask is recomputed
-// from x as fmaf(x, gamma * invstd, beta - mean * gamma * invstd) > 0 (the forward's own ops)
-bool bn_two_kernel_path(int N, int C, int HW, int single);
-// the downsample block's BN(x) + BN2(x2) -> ReLU in one launch per direction (batchnorm.hip BnPair)
-bool bn_pair_ok(int N, int C, int HW);
-void launch_bn_pair_fwd(const float* x, const float* x2, float* y, const float* gamma, const float* beta,
-                        float* rmean, float* rvar, int64_t* nbt, float* save_mean, float* save_invstd,
-                        const float* gamma2, const float* beta2, float* rmean2, float* rvar2, int64_t* nbt2,
-                        float* save_mean2, float* save_invstd2, int N, int C, int HW, float eps, float momentum,
-                        hipStream_t s, const float* xpart, int nslab, const float* x2part, int nslab2);
-void launch_bn_pair_bwd(const float* dy, const float* y, const float* x, const float* x2, const float* gamma,
-                        const float* save_mean, const float* save_invstd, const float* gamma2,
-                        const float* save_mean2, const float* save_invstd2, float* dx, float* dx2, float* dgamma,
-                        float* dbeta, float* dgamma2, float* dbeta2, int N, int C, int HW, hipStream_t s,
-                        const float* dypart, int nslab, const float* dyadd);
-void bn_set_vec4(bool on);
+enum BnPath { kBnNone = 0, kBnFused, kBnFused64, kBnThreeKernel, kBnTwoKernel };
+// deferred split-K slabs of the input: none (fewer than two count as none), added inside the BN
+// launch, or by a launch_slab_sum of their own first (with the grad-x addend when one came along)
+enum BnSlab { kBnSlabNone = 0, kBnSlabInKernel, kBnSlabSumFirst };
+
+// 16-byte alignment of the operand sets the float4 kernels read or write (bn_alignment)
+struct BnAlign {
+  bool fused = true;   // single-launch set: forward x, res, out; backward x, dy, yin, out, dres; the pair's x2, out2
+  bool two = true;     // two-kernel set: forward x, out, res; backward dy, x, out, dres and yin under relu
+  bool slabs = true;   // the slabs of the main input and the addend
+  bool slabs2 = true;  // the slabs of the pair's x2
+};
+
+struct BnQuery {
+  int bwd = 0;
+  int N = 0, C = 0, HW = 0;
+  bool training = true;  // forward only
+  bool single = false;   // allow the single-launch paths
+  bool pair = false;     // the downsample block's two BNs in one launch (BnPair)
+  int pool_w = 0;        // > 0: the stem tail (BN -> ReLU -> max-pool) on maps of this width
+  int nslab = 0, nslab2 = 0;  // slabs offered for x / dy, and for the pair's x2
+  int ext_slices = 0;    // > 0: xstats / dstats offered, this many partials per channel
+  bool relu = false;
+  bool addend = false;   // dyadd
+  bool mbeta = false;    // ReLU mask recomputed from x
+  BnAlign al;
+};
+
+struct BnRoute {
+  int bwd, N, C, HW, pool_w, pair;
+  int training;  // batch statistics (every backward, the stem tail, a training forward)
+  int path;      // BnPath; kBnNone: the query cannot be served (pair or mbeta outside their paths)
+  // single-launch paths
+  int v4;        // the float4 kernel (else the scalar one)
+  int CW, MAXN;  // column-block width, rows the register arrays hold
+  int split;     // workgroups per column block (8x8 maps: 1, 2 or 4)
+  int grid;
+  // two-kernel path
+  int vec;         // float4 kernels
+  int S, Sa;       // slices of the statistics pass, of the apply pass
+  int stats_pass;  // the statistics pass runs
+  int Sp;          // > 0: the apply folds this many external partials per channel instead of `part`
+  // three-kernel path
+  int Ss;
+  int slab, slab2;     // BnSlab of x / dy, of the pair's x2
+  int addend;          // dyadd goes wherever the slabs are summed (dropped when there are none)
+  int64_t part_numel;  // doubles of `part` scratch the call may touch
+};
+BnRoute bn_make_route(const BnQuery& q);
+
+// the downsample block's second BN (over x2, same shape) for the single-launch kernels
+struct BnPair {
+  const float* x2;
+  const float* gamma2;
+  const float* beta2;
+  float* rmean2;
+  float* rvar2;
+  int64_t* nbt2;
+  float* save_mean2;
+  float* save_invstd2;
+  float* dgamma2;
+  float* dbeta2;
+  float* out2;
+  const float* src2;  // forward: x2 as nslab2 unsummed split-K slabs (summed here, stored to x2), or null
+  int nslab2;
+};
+
+// Operands of one BN call; unused ones stay null.  Forward: x, res -> out.  Backward: dy, yin (the
+// forward output, for the ReLU mask), x -> out (dx), dres, dgamma, dbeta.
+struct BnOps {
+  const float *x = nullptr, *res = nullptr, *dy = nullptr, *yin = nullptr, *gamma = nullptr, *beta = nullptr;
+  float *rmean = nullptr, *rvar = nullptr;
+  int64_t* nbt = nullptr;
+  float *save_mean = nullptr, *save_invstd = nullptr, *dgamma = nullptr, *dbeta = nullptr, *out = nullptr, *dres = nullptr;
+  float eps = 0.f, momentum = 0.f;
+  int relu = 0;
+  double* part = nullptr;  // BnRoute::part_numel doubles of scratch
+  // x (forward) / dy (backward) as `nslab` unsummed split-K slabs of numel(x) floats (a deferred conv
+  // sum; the forward also writes the sum to x), and dyadd: dy = sum of the slabs + addend, added last
+  const float* slabs = nullptr;
+  int nslab = 0;
+  const float* addend = nullptr;
+  // xstats / dstats: [C][BnRoute::Sp][2] fp64 partial sums from the producing conv's epilogue
+  const double* stats = nullptr;
+  // y was never stored (stem tail): the ReLU mask is recomputed from x as
+  // fmaf(x, gamma * invstd, mbeta - mean * gamma * invstd) > 0 (the forward's own ops)
+  const float* mbeta = nullptr;
+  uint8_t* idx = nullptr;  // stem tail: the pooled output's uint8 window offsets (pool.hip layout)
+};
+BnAlign bn_alignment(int bwd, const BnOps& o, const BnPair* pr = nullptr);
+
+void launch_bn_fwd(const BnOps& o, const BnRoute& r, hipStream_t s);
+void launch_bn_bwd(const BnOps& o, const BnRoute& r, hipStream_t s);
+void launch_bn_pair_fwd(const BnOps& o, const BnPair& pr, const BnRoute& r, hipStream_t s);
+void launch_bn_pair_bwd(const BnOps& o, const BnPair& pr, const BnRoute& r, hipStream_t s);
 // BN (training) -> ReLU -> MaxPool(3, 2, 1) in one pass without storing the BN output (the
-// ResNet stem tail); y / idx: the pooled output and its uint8 window offsets (pool.hip layout)
-void launch_bn_relu_maxpool(const float* x, float* y, uint8_t* idx, const float* gamma, const float* beta,
-                            float* rmean, float* rvar, int64_t* nbt, float* save_mean, float* save_invstd,
-                            double* part, int N, int C, int H, int W, float eps, float momentum, hipStream_t s,
-                            const double* xstats = nullptr, int xS = 0);
-// dyadd (nullable, with dypart): dy = sum of the slabs + dyadd (added last, as conv_slab_sum does)
+// ResNet stem tail); o.out / o.idx: the pooled output and its window offsets
+void launch_bn_relu_maxpool(const BnOps& o, const BnRoute& r, hipStream_t s);
+// shape-only views of the route
+int bn_slices(int N, int C, int HW);
+int64_t bn_part_numel(int N, int C, int HW);
+bool bn_two_kernel_path(int N, int C, int HW, int single);
+bool bn_pair_ok(int N, int C, int HW);
+void bn_set_vec4(bool on);
 }  // namespace ndp
 
 // ---- embedding backward (embedding.hip) -------------------------------------------------

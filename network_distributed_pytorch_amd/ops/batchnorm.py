@@ -3,9 +3,13 @@
 :class:`BatchNormAct2d` is a drop-in ``nn.BatchNorm2d`` (same parameters, buffers and
 ``state_dict`` keys, so torchvision checkpoints load unchanged) whose forward optionally
 fuses the residual add and the ReLU that follow BN in every ResNet block:
-``y = relu(bn(x) + residual)``.  On device it runs two kernels per direction
-(csrc/batchnorm.hip) instead of MIOpen BN + ATen ReLU + ATen add + the
-``num_batches_tracked`` increment; on CPU it computes the same math with torch ops.
+``y = relu(bn(x) + residual)``.  On device one of four paths of csrc/batchnorm.hip runs per
+direction instead of MIOpen BN + ATen ReLU + ATen add + the ``num_batches_tracked``
+increment: a single launch for the small maps (HW in 1, 2, 4, 8, 16 up to batch 512), a
+single launch with row splits for 8x8 maps up to batch 128, three kernels (statistics,
+finalize, apply) for HW <= 4 at larger batches, and two kernels (statistics, apply) for
+everything else and for evaluation mode.  ``bn_make_route`` picks the path once per call
+(``ext().bn_route`` reports it).  On CPU the same math runs with torch ops.
 Training statistics follow ``torch.nn.BatchNorm2d`` exactly (biased variance for the
 normalisation, unbiased in ``running_var``, momentum 0.1).
 """

@@ -191,3 +191,70 @@ def test_bn_vec4_vs_fp64(device, shape, res, relu):
     torch.testing.assert_close(db.double().cpu(), bd.grad, rtol=1e-5, atol=1e-4)
     if res:
         torch.testing.assert_close(runs[0][4].double().cpu(), rd.grad, rtol=0, atol=1e-6)
+
+
+def _off1(t):
+    """A contiguous copy of t one float past a 16-byte boundary (no float4 access is aligned)."""
+    buf = torch.empty(t.numel() + 1, device=t.device, dtype=t.dtype)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+def _fp64_bn(x, w, b, eps):
+    xd, wd, bd = (t.detach().double().cpu().requires_grad_(True) for t in (x, w, b))
+    return F.batch_norm(xd, None, None, wd, bd, True, 0.0, eps), [xd, wd, bd]
+
+
+# the arm each shape reaches when x, the residual and the output gradient are misaligned
+@pytest.mark.parametrize("shape,pair", [((130, 8, 4, 4), False),   # single launch: float4 -> scalar
+                                        ((20, 16, 8, 8), False),   # 8x8 maps: row-split float4 -> scalar, 64 columns
+                                        ((4, 8, 16, 16), False),   # two kernels: float4 -> scalar
+                                        ((600, 8, 2, 2), False),   # three kernels
+                                        ((130, 8, 4, 4), True)])   # BN pair, only x2 misaligned
+def test_bn_unaligned_operands(device, shape, pair):
+    """Operands at a storage offset of one float (contiguous, not 16-byte aligned) take the scalar
+    arms of every path: forward and backward with residual and ReLU against the fp64 reference and
+    tolerances of test_bn_vec4_vs_fp64, and against the same modules on aligned copies at the
+    tolerances of test_bn_single_launch_small_path."""
+    from network_distributed_pytorch_amd.ops.batchnorm import bn_pair_act
+    torch.manual_seed(5)
+    C = shape[1]
+    ms = [BatchNormAct2d(C).to(device) for _ in range(2 if pair else 1)]
+    with torch.no_grad():
+        for m in ms:
+            m.weight.uniform_(0.5, 1.5)
+            m.bias.uniform_(-0.5, 0.5)
+    x = torch.randn(shape, device=device) * 1.7 + 0.4
+    r = torch.randn(shape, device=device) * (0.7 if pair else 1.0)  # the pair's x2, else the residual
+    g = torch.randn(shape, device=device)
+    # fp64 reference: relu(bn(x) + r), or relu(bn(x) + bn2(r)) for the pair
+    yd, leaves = _fp64_bn(x, ms[0].weight, ms[0].bias, ms[0].eps)
+    if pair:
+        y2, leaves2 = _fp64_bn(r, ms[1].weight, ms[1].bias, ms[1].eps)
+        yd, leaves = yd + y2, leaves + leaves2
+    else:
+        rd = r.double().cpu().requires_grad_(True)
+        yd, leaves = yd + rd, leaves + [rd]
+    yd = F.relu(yd)
+    yd.backward(g.double().cpu())
+    want = [yd.detach()] + [t.grad for t in leaves]
+    runs = []
+    for shift in (True, False):
+        xx = (x.clone() if pair or not shift else _off1(x)).requires_grad_(True)
+        rr = (_off1(r) if shift else r.clone()).requires_grad_(True)
+        gg = g.clone() if pair or not shift else _off1(g)
+        for m in ms:
+            m.weight.grad = m.bias.grad = None
+        y = bn_pair_act(ms[0], ms[1], xx, rr) if pair else ms[0](xx, residual=rr, relu=True)
+        assert y is not None
+        y.backward(gg)
+        got = [y.detach(), xx.grad, ms[0].weight.grad.clone(), ms[0].bias.grad.clone(), rr.grad]
+        runs.append(got + ([ms[1].weight.grad.clone(), ms[1].bias.grad.clone()] if pair else []))
+    # (y, dx, dgamma, dbeta, dres | dx2, dgamma2, dbeta2)
+    tols = [(1e-5, 2e-5), (1e-4, 5e-5), (1e-5, 1e-4), (1e-5, 1e-4)] + \
+        ([(1e-4, 5e-5), (1e-5, 1e-4), (1e-5, 1e-4)] if pair else [(0, 1e-6)])
+    for a, b, w, (rtol, atol) in zip(runs[0], runs[1], want, tols):
+        torch.testing.assert_close(a.double().cpu(), w, rtol=rtol, atol=atol)
+        torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-5)
