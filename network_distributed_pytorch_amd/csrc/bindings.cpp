@@ -1307,6 +1307,44 @@ void cls_metrics(torch::Tensor x, torch::Tensor tgt, torch::Tensor state, torch:
   check_launch("launch_cls_metrics");
 }
 
+// global-norm gradient clipping (gradclip.hip) over a SegPlan table of the gradients: partial
+// [>= n_blocks] fp64 scratch, ctr: grad_clip_ctr_words(n_blocks) zeroed int32 (re-armed), clip: the ClipBlock
+// {norm, coef, clipped, steps} as 4 int32 words.  No allocation, no sync: capture-safe.
+void grad_sqnorm(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
+                 torch::Tensor partial, torch::Tensor ctr, torch::Tensor clip, double max_norm, double div) {
+  check_dev(entries, "entries"); check_dev(prefix, "prefix"); check_dev(partial, "partial");
+  check_dev(ctr, "ctr"); check_dev(clip, "clip");
+  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "grad_sqnorm: table too large");
+  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
+              "seg table size mismatch");
+  TORCH_CHECK(partial.scalar_type() == torch::kFloat64 && partial.numel() >= n_blocks,
+              "grad_sqnorm: partial must be float64 of >= n_blocks elements");
+  TORCH_CHECK(ctr.scalar_type() == torch::kInt32 && ctr.numel() >= ndp::grad_clip_ctr_words(n_blocks),
+              "grad_sqnorm: ctr must be int32 of >= grad_clip_ctr_words(n_blocks) elements");
+  TORCH_CHECK(clip.scalar_type() == torch::kInt32 && clip.numel() == 4, "grad_sqnorm: clip block is 4 int32 words");
+  TORCH_CHECK(max_norm > 0.0, "grad_sqnorm: max_norm must be > 0 (inf: measure only)");
+  TORCH_CHECK(div >= 1.0, "grad_sqnorm: div must be >= 1");
+  ndp::launch_grad_sqnorm(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
+                          (int)n_entries, n_blocks, partial.data_ptr<double>(),
+                          reinterpret_cast<unsigned*>(ctr.data_ptr<int32_t>()),
+                          reinterpret_cast<ndp::ClipBlock*>(clip.data_ptr<int32_t>()), (float)max_norm, (float)div,
+                          cur_stream());
+  check_launch("launch_grad_sqnorm");
+}
+
+void grad_scale(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
+                torch::Tensor clip) {
+  check_dev(entries, "entries"); check_dev(prefix, "prefix"); check_dev(clip, "clip");
+  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "grad_scale: table too large");
+  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
+              "seg table size mismatch");
+  TORCH_CHECK(clip.scalar_type() == torch::kInt32 && clip.numel() == 4, "grad_scale: clip block is 4 int32 words");
+  ndp::launch_grad_scale(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
+                         (int)n_entries, n_blocks, reinterpret_cast<const ndp::ClipBlock*>(clip.data_ptr<int32_t>()),
+                         cur_stream());
+  check_launch("launch_grad_scale");
+}
+
 // batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
 // [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
 // shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
@@ -1701,6 +1739,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("cls_metrics", &cls_metrics, py::arg("x"), py::arg("tgt"), py::arg("state"), py::arg("rowbuf"),
         py::arg("ctr"), py::arg("ignore_index"), py::arg("k"), py::arg("pred") = py::none());
+  m.def("grad_sqnorm", &grad_sqnorm, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
+        py::arg("partial"), py::arg("ctr"), py::arg("clip"), py::arg("max_norm"), py::arg("div"));
+  m.def("grad_clip_ctr_words", &ndp::grad_clip_ctr_words);
+  m.def("grad_scale", &grad_scale, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
+        py::arg("clip"));
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));

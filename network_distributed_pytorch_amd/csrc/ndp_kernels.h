@@ -318,6 +318,29 @@ void launch_cls_metrics(const float* x, const int64_t* tgt, int B, int K, int64_
                         float* rowbuf, unsigned* ctr, int64_t* pred, hipStream_t s);
 }  // namespace ndp
 
+// ---- global-norm gradient clipping (gradclip.hip) -----------------------------------------
+// A SegEntry table over the gradients (src read, dst written, chunks = 1); partial [n_blocks]
+// fp64 scratch, ctr: grad_clip_ctr_words(n_blocks) zeroed uint32 (the two-level arrival tickets,
+// re-armed by the kernel), clip: the 16-byte ClipBlock.
+namespace ndp {
+constexpr int kClipGroup = 64;      // workgroups that share one first-level ticket
+constexpr int kClipCtrStride = 64;  // uint32 between two tickets: 256 B apart, never one cache line
+inline int64_t grad_clip_ctr_words(int64_t n_blocks) {
+  return (int64_t)kClipCtrStride * (1 + (n_blocks + kClipGroup - 1) / kClipGroup);
+}
+struct ClipBlock {
+  float norm;        // (float)(sqrt(sum v^2) / div) of the last run
+  float coef;        // q = max_norm / (norm + 1e-6f);  q < 1 or NaN ? q : 1
+  uint32_t clipped;  // runs whose coef != 1
+  uint32_t steps;    // runs
+};
+void launch_grad_sqnorm(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
+                        double* partial, unsigned* ctr, ClipBlock* clip, float max_norm, float div, hipStream_t s);
+// v *= clip->coef over the table; every workgroup returns at once when coef == 1
+void launch_grad_scale(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
+                       const ClipBlock* clip, hipStream_t s);
+}  // namespace ndp
+
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------
 // src [N, C, 32, 32] bytes, labels [N], idx [m]; out [B, C, 32, 32] fp32 and out_target [B] are
 // written in full: rows < m gathered, normalised (fmaf(byte, scale[c], shift[c])) and optionally

@@ -72,6 +72,8 @@ def default_config(**over) -> Dict[str, Any]:
         data_root=None, augment="none", normalize="half",
         # learning-rate schedule (utils/schedule.py) and L2 weight decay
         lr_schedule="constant", lr_warmup_steps=0, lr_min=0.0, lr_milestones="", lr_gamma=0.1, weight_decay=0.0,
+        # clip the gradient by its global L2 norm (ops/gradclip.py): 0 = off, inf = measure only
+        max_grad_norm=0.0,
     )
     cfg.update(over)
     return cfg
@@ -387,6 +389,9 @@ def run_task(config) -> Dict[str, Any]:
             graph_mode = "none"  # the per-step query re-draw is host-side (not capturable)
     elif config["grad_sync"] == "dense":
         extra = {"overlap": config.get("overlap")}
+    max_grad_norm = float(config.get("max_grad_norm") or 0.0)
+    if max_grad_norm > 0:  # off: build_grad_sync is called exactly as before
+        extra["max_grad_norm"] = max_grad_norm
     sync = build_grad_sync(config["grad_sync"], model, comm, lr=config["learning_rate"],
                            momentum=config["momentum"], rank=config["reducer_rank"],
                            bucket_mb=config.get("bucket_mb"), seed=config["seed"], **extra)
@@ -454,6 +459,16 @@ def run_task(config) -> Dict[str, Any]:
     evals = []
     eval_s = 0.0
     losses = []
+    clip_on = max_grad_norm > 0
+    clipped_base = None  # the block's counter when this run began (a resume restarts clipped_steps)
+
+    def clip_read():
+        # host read of the clip block; after a replay the block's last write may sit on the side stream
+        if runner is not None:
+            runner.join()
+        return sync.clip_stats()
+    if clip_on:
+        clipped_base = clip_read()["clipped"]
     t_start = time.perf_counter()
     samples = 0
     last_log = (time.perf_counter(), comm.stats.payload_bytes, comm.stats.wire_bytes, step)
@@ -531,7 +546,8 @@ def run_task(config) -> Dict[str, Any]:
                            if runner is None or graph_mode == "piecewise" else
                            _ring_wire(getattr(sync, "bytes_per_step", 0) or 0, comm.paced_world),
                            bytes_per_step=getattr(sync, "bytes_per_step", None),
-                           **({"lr": lr_now} if hyper_on else {}))
+                           **({"lr": lr_now} if hyper_on else {}),
+                           **(_clip_step_record(clip_read()) if clip_on else {}))
                 last_log = (now, comm.stats.payload_bytes, comm.stats.wire_bytes, step)
         if runner is not None:
             runner.join()  # parameters / sync state are read below (checks, checkpoint)
@@ -543,12 +559,16 @@ def run_task(config) -> Dict[str, Any]:
         if hasattr(loader.ds, "check_errors"):
             loader.ds.check_errors()
         losses.append(mean)
+        clip_rec = {}
+        if clip_on:
+            clip_rec = {"clipped_steps": clip_read()["clipped"] - clipped_base, "max_grad_norm": max_grad_norm}
         if config.get("verbose", True):
             print_epoch(rank, epoch, mean)
             print(">>>>> Rank ", rank, ", epoch ", epoch, " Finished...\n", flush=True)
         logger.log(kind="epoch", epoch=epoch, mean_loss=mean, steps=i, num_batches=num_batches,
                    bytes_per_step=getattr(sync, "bytes_per_step", None), comm=comm.stats.as_dict(),
-                   phase_ms=timer.summary() if timer is not None else None, **({"lr": lr_now} if hyper_on else {}))
+                   phase_ms=timer.summary() if timer is not None else None, **({"lr": lr_now} if hyper_on else {}),
+                   **clip_rec)
         if config.get("checkpoint_dir"):
             save_checkpoint(os.path.join(config["checkpoint_dir"], "last.pt"), model, sync, epoch=epoch, step=step,
                             rank=rank, world=world)
@@ -582,6 +602,9 @@ def run_task(config) -> Dict[str, Any]:
     if hyper_on:
         summary["lr_schedule"] = schedule.schedule
         summary["weight_decay"] = weight_decay
+    if clip_on:
+        summary["clipped_steps"] = sync.clip_stats()["clipped"] - clipped_base
+        summary["max_grad_norm"] = max_grad_norm
     if eval_every:
         summary["eval"] = evals
         summary["eval_s"] = eval_s
@@ -590,6 +613,10 @@ def run_task(config) -> Dict[str, Any]:
     summary["model"] = model
     summary["sync"] = sync
     return summary
+
+
+def _clip_step_record(stats) -> Dict[str, Any]:
+    return {"grad_norm": stats["norm"], "clip_coef": stats["coef"]}
 
 
 def _ring_wire(payload: int, n: int) -> float:

@@ -33,6 +33,8 @@ __all__ = [
     "hash4",
     "crop_flip_draw",
     "image_norm_constants",
+    "GradClip",
+    "clip_grad_norm_",
 ]
 
 
@@ -280,3 +282,4 @@ def checksum(x: torch.Tensor) -> float:
 
 from .metrics import ClassificationMetrics, classification_metrics  # noqa: E402  (fused eval metrics, csrc/loss.hip)
 from .image_batch import crop_flip_draw, hash4, image_batch, image_norm_constants  # noqa: E402  (csrc/image_batch.hip)
+from .gradclip import GradClip, clip_grad_norm_  # noqa: E402  (global-norm clipping, csrc/gradclip.hip)

@@ -30,15 +30,23 @@ backward-overlapped MI355X arm.
   ``set_hyper(lr, weight_decay)`` changes the learning rate and the L2 weight decay of later
   steps, captured replays included: on a device the SGD kernel then reads both from the
   optimiser's 16-byte block (ops/hyper.py) instead of taking ``lr`` by value.
+  ``max_grad_norm > 0`` clips by the global L2 norm of the AVERAGED gradient (ops/gradclip.py):
+  the buckets all-reduce during backward as before, and immediately before the fused SGD launch,
+  on its stream, two launches measure ``norm = ||sum g|| / N`` over the arena (its 16-element
+  padding is zero and stays zero) and scale the arena by the coefficient.  The arena then holds
+  ``coef * sum g`` and the SGD forms ``(coef * sum g) / N``: torch's clip-after-average, exact
+  when N is a power of two and within one ulp per element otherwise.  Every rank sees the same
+  all-reduced arena, so the norm and the replicas stay identical across ranks.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import Any, Dict, List, Optional
 
 import numpy as np
 import torch
 
 from ..ops import SegPlan, capturing, gradarena, gradfinish, sgd_momentum_
+from ..ops.gradclip import GradClip
 from ..ops.hyper import HyperBlock
 from .comm import Communicator, all_reduce, world_size
 
@@ -66,8 +74,11 @@ def average_gradients(model: torch.nn.Module, comm: Optional[Communicator] = Non
 class BucketedDataParallel:
     def __init__(self, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                  momentum: float = 0.9, bucket_mb: Optional[float] = None, broadcast_params: bool = True,
-                 overlap: Optional[bool] = None, weight_decay: float = 0.0):
+                 overlap: Optional[bool] = None, weight_decay: float = 0.0,
+                 max_grad_norm: float = 0.0):
         assert weight_decay >= 0, "weight_decay >= 0"
+        assert max_grad_norm >= 0, "max_grad_norm >= 0 (0: off, inf: measure only)"
+        self.max_grad_norm = float(max_grad_norm)
         bucket_mb = DEFAULT_BUCKET_MB if bucket_mb is None else float(bucket_mb)
         self.model = model
         self.comm = comm if comm is not None else Communicator()
@@ -141,6 +152,16 @@ class BucketedDataParallel:
             for p in self.params:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
         self.step_count = 0
+        # global-norm clip over the flat gradient arena as ONE table entry, built before any capture
+        self.clip: Optional[GradClip] = None
+        if self.max_grad_norm > 0:
+            self.clip = GradClip(self.device, capacity=1, blocks=(self.numel + 2047) // 2048)
+            self.clip.bind([self.g])
+
+    def clip_stats(self) -> Optional[Dict[str, Any]]:
+        """``{"norm", "coef", "clipped", "steps"}`` of the gradient clip (a host sync), or None when
+        ``max_grad_norm`` is 0.  The norm is that of the averaged gradient, equal on every rank."""
+        return self.clip.read() if self.clip is not None else None
 
     @property
     def bytes_per_step(self) -> int:
@@ -228,7 +249,15 @@ class BucketedDataParallel:
         hy = self.hyper.dev if self._hyper_on else None
         if capturing() and hy is None:
             self._captured_by_value = True
-        return lambda: sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+        if self.clip is None:
+            return lambda: sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+        clip, max_norm = self.clip, self.max_grad_norm
+        clip.bind([self.g])  # a no-op unless the device tables were restored (upload_epoch)
+
+        def clip_sgd():  # norm of sum g / N, arena scaled in place, then the SGD: all on one stream
+            clip.run(max_norm, n)
+            sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+        return clip_sgd
 
     def plan_hyper(self, pairs):
         """Write the pinned source rows of the coming steps' ``(lr, weight_decay)`` ahead of time."""
@@ -307,12 +336,15 @@ class BucketedDataParallel:
         return 8 * self.bytes_per_step
 
     def snapshot(self):
-        return {"x": self.x.clone(), "buf": self.buf.clone(), "step_count": self.step_count}
+        return {"x": self.x.clone(), "buf": self.buf.clone(), "step_count": self.step_count,
+                **({"clip": self.clip.snapshot()} if self.clip is not None else {})}
 
     def restore(self, snap):
         self.x.copy_(snap["x"])
         self.buf.copy_(snap["buf"])
         self.step_count = snap["step_count"]
+        if self.clip is not None:
+            self.clip.restore(snap["clip"])
 
     def count_step(self):
         if not capturing():

@@ -35,12 +35,13 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ..ops import SegPlan, capturing, ext, gradfinish, taps, upload, upload_epoch
+from ..ops.gradclip import GradClip
 from ..ops.hyper import HyperBlock
 from .comm import Communicator, n_bits
 from ..knobs import fusion_on
@@ -526,6 +527,15 @@ class PowerSGDOptimizer:
     ``weight_decay`` is L2 on every parameter, ``d = out + wd x`` after decompression; it never
     enters the error memory, P, Q or the all-reduced bytes.  Dead taps acquire momentum under it,
     so with ``weight_decay != 0`` every matrix keeps the full layout.
+
+    **Gradient clipping** (``max_grad_norm > 0``; ops/gradclip.py, csrc/gradclip.hip): ``phase_p``
+    clips every parameter's gradient, the <=1-D group included, by their global L2 norm in two
+    launches before anything reads them, so the whole-step and the piecewise graph contain the
+    clip.  ``inf`` measures the norm and never scales.  With more than one rank, each rank clips
+    its OWN gradient by its OWN norm before it enters ``M = g + e``: the error feedback sees the
+    clipped gradient, and :meth:`clip_stats` reports a rank-local norm.  The norm needs every
+    gradient, so the per-group pipelines cannot start during backward: ``overlap=None`` resolves
+    to ``False`` and ``overlap=True`` / ``set_overlap(True)`` raise.
     """
 
     def __init__(self, params, lr: float, momentum: float = 0.9, rank: int = 4,
@@ -533,10 +543,15 @@ class PowerSGDOptimizer:
                  comm: Optional[Communicator] = None, write_grad: bool = False,
                  broadcast_params: bool = True, rng_compat: bool = False, eps: float = 1e-8,
                  native: Optional[bool] = None, overlap: Optional[bool] = None, groups: Optional[int] = None,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0, max_grad_norm: float = 0.0):
         self.params: List[torch.nn.Parameter] = [p for p in params]
         assert self.params, "no parameters"
         assert weight_decay >= 0, "weight_decay >= 0"
+        assert max_grad_norm >= 0, "max_grad_norm >= 0 (0: off, inf: measure only)"
+        self.max_grad_norm = float(max_grad_norm)
+        if self.max_grad_norm > 0 and overlap:
+            raise ValueError("PowerSGD: overlap=True cannot be combined with max_grad_norm > 0 (the global "
+                             "norm needs every gradient before the first group's pipeline may start)")
         self.lr = float(lr)
         self.weight_decay = float(weight_decay)
         self.momentum = float(momentum)
@@ -610,6 +625,13 @@ class PowerSGDOptimizer:
         self._r1_pack = SegPlan([], self.device, capacity=len(r1) + 1) if self.native else None
         self._grad_key = None
         self._r1_key = None
+        # global-norm clip of this rank's gradients (ops/gradclip.py): table, partials and the
+        # {norm, coef, clipped, steps} block exist before any capture
+        self.clip: Optional[GradClip] = None
+        if self.max_grad_norm > 0:
+            self.clip = GradClip(self.device, capacity=len(self.params),
+                                 blocks=sum((p.numel() + 2047) // 2048 for p in self.params))
+            overlap = False  # overlap=None resolves to the serial step
 
         # default: overlap when a step has wire time to hide (N > 1 or link emulation)
         want = overlap if overlap is not None else (os.environ.get("NDP_PSGD_OVERLAP", "1") != "0"
@@ -864,6 +886,11 @@ class PowerSGDOptimizer:
         self.buf.check_orth()
         self.comm.check()
 
+    def clip_stats(self) -> Optional[Dict[str, Any]]:
+        """``{"norm", "coef", "clipped", "steps"}`` of the gradient clip (a host sync), or None when
+        ``max_grad_norm`` is 0.  The norm is this rank's own."""
+        return self.clip.read() if self.clip is not None else None
+
     # -- the step --------------------------------------------------------------------------
     # Serial path: step() = phase_p -> comm_p -> phase_q -> comm_q -> phase_update.  The
     # phases are exposed separately so a piecewise hipGraph can capture the compute phases
@@ -872,7 +899,10 @@ class PowerSGDOptimizer:
     def phase_p(self):
         B = self.buf
         self._ensure_queries()
-        self._grads()
+        grads = self._grads()
+        if self.clip is not None:  # before M = g + e: the error feedback sees the clipped gradient
+            self.clip.bind(grads)
+            self.clip.run(self.max_grad_norm)
         if not self.native:
             return
         self._sync_supports()
@@ -958,6 +988,8 @@ class PowerSGDOptimizer:
                 (self.phase_update, False)]
 
     def set_overlap(self, on: bool):
+        if on and self.clip is not None:
+            raise ValueError("PowerSGD: overlap=True cannot be combined with max_grad_norm > 0")
         if on and not self.groups:
             raise ValueError("optimizer was built without overlap groups")
         if self.hyper is not None and bool(on) != bool(self.overlap):
@@ -1196,7 +1228,8 @@ class PowerSGDOptimizer:
 
     def snapshot(self):
         # e / m in the full layout: the warm-up steps between snapshot and restore may re-plan
-        return {"x": self.x.clone(), "e": self._full_arena(self._e).clone(), "p_prev": self.p_prev.clone(),
+        return {**({"clip": self.clip.snapshot()} if self.clip is not None else {}),
+                "x": self.x.clone(), "e": self._full_arena(self._e).clone(), "p_prev": self.p_prev.clone(),
                 "lazy_pending": self._lazy_pending, "m": self.m.clone(), "q": self.buf.q_warm.clone(),
                 "step_count": self.step_count, "bits": self.bits_communicated, "q_ready": self._q_ready,
                 "rng": self.rng.get_state()}
@@ -1212,6 +1245,8 @@ class PowerSGDOptimizer:
         self.bits_communicated = snap["bits"]
         self._q_ready = snap["q_ready"]
         self.rng.set_state(snap["rng"])
+        if self.clip is not None:
+            self.clip.restore(snap["clip"])
 
     # -- checkpoint / resume ---------------------------------------------------------------
     def state_dict(self):

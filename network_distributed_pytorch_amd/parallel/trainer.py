@@ -17,6 +17,11 @@ Every strategy has ``set_hyper(lr, weight_decay)``: the learning rate and the L2
 the steps from now on (the engine calls it before every step when a schedule or a decay is on).
 The native engines forward it to their optimiser's device block, the reference loops apply it
 in torch.
+
+Every strategy takes ``max_grad_norm`` (0: off; ``inf``: measure only) and has ``clip_stats()``: the
+``{"norm", "coef", "clipped", "steps"}`` block of the global-norm gradient clip (ops/gradclip.py), or
+None when clipping is off.  The PowerSGD arms clip each rank's own gradient before the error
+feedback; the dense arms and the local optimisers clip the averaged gradient before the update.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ from typing import Optional
 
 import torch
 
+from ..ops.gradclip import GradClip
 from .comm import Communicator
 from .ddp import BucketedDataParallel, average_gradients
 from .powersgd import PowerSGDOptimizer, PowerSGDReducer, powersgd_bytes_per_step
@@ -64,6 +70,9 @@ class PowerSGDSync:
     def phases(self):
         return self.opt.phases()
 
+    def clip_stats(self):
+        return self.opt.clip_stats()
+
     def count_step(self):
         self.opt.count_step()
 
@@ -89,9 +98,11 @@ class PowerSGDSync:
 class ReferencePowerSGDLoop:
     """Algorithm 2 exactly as the reference loop writes it (ddp_init.py:130-178)."""
 
-    def __init__(self, model, comm, lr, momentum, rank, seed=714, native_reducer=False):
+    def __init__(self, model, comm, lr, momentum, rank, seed=714, native_reducer=False, max_grad_norm=0.0):
         self.model = model
         self.params = list(model.parameters())
+        self.max_grad_norm = float(max_grad_norm)
+        self.clip = _make_clip(self.max_grad_norm, self.params[0].device)
         self.lr, self.lam, self.weight_decay = lr, momentum, 0.0
         self.reducer = PowerSGDReducer(seed, self.params[0].device, 0, True, rank=rank, comm=comm)
         self.native_reducer = native_reducer
@@ -120,6 +131,7 @@ class ReferencePowerSGDLoop:
     @torch.no_grad()
     def step(self):
         grads = [p.grad for p in self.params]
+        _clip(self.clip, self.max_grad_norm, grads)  # this rank's own gradient, before s = g + e
         for g, e, s in zip(grads, self.memories, self.send_buffers):
             s.data[:] = g + e
         if self.native_reducer:
@@ -140,11 +152,16 @@ class ReferencePowerSGDLoop:
             p.data.add_(g, alpha=-self.lr)
         return self.bytes_per_step * 8
 
+    def clip_stats(self):
+        return self.clip.read() if self.clip is not None else None
+
 
 class ReferenceDenseLoop:
-    def __init__(self, model, comm, lr, momentum):
+    def __init__(self, model, comm, lr, momentum, max_grad_norm=0.0):
         self.model = model
         self.comm = comm
+        self.max_grad_norm = float(max_grad_norm)
+        self.clip = _make_clip(self.max_grad_norm, next(model.parameters()).device)
         self.opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum)
         self.bytes_per_step = 4 * sum(p.numel() for p in model.parameters())
         self._payloads = [4 * p.numel() for p in model.parameters()]  # ddp_init.py:61, one per param
@@ -161,13 +178,18 @@ class ReferenceDenseLoop:
 
     def step(self):
         bits = average_gradients(self.model, self.comm)
+        _clip(self.clip, self.max_grad_norm, [p.grad for p in self.model.parameters()])
         self.opt.step()
         return bits
 
+    def clip_stats(self):
+        return self.clip.read() if self.clip is not None else None
+
 
 class _DenseSync:
-    def __init__(self, model, comm, lr, momentum, bucket_mb, overlap=None):
-        self.ddp = BucketedDataParallel(model, comm, lr=lr, momentum=momentum, bucket_mb=bucket_mb, overlap=overlap)
+    def __init__(self, model, comm, lr, momentum, bucket_mb, overlap=None, max_grad_norm=0.0):
+        self.ddp = BucketedDataParallel(model, comm, lr=lr, momentum=momentum, bucket_mb=bucket_mb, overlap=overlap,
+                                        max_grad_norm=max_grad_norm)
         self.bytes_per_step = self.ddp.bytes_per_step
 
     @property
@@ -205,6 +227,9 @@ class _DenseSync:
     def phases(self):
         return self.ddp.phases()
 
+    def clip_stats(self):
+        return self.ddp.clip_stats()
+
     def count_step(self):
         self.ddp.count_step()
 
@@ -213,6 +238,18 @@ class _DenseSync:
 
     def load_state_dict(self, sd):
         self.ddp.load_state_dict(sd)
+
+
+def _make_clip(max_grad_norm, device) -> Optional[GradClip]:
+    assert max_grad_norm >= 0, "max_grad_norm >= 0 (0: off, inf: measure only)"
+    return GradClip(device) if max_grad_norm > 0 else None
+
+
+def _clip(clip: Optional[GradClip], max_grad_norm, grads):
+    """Clip ``grads`` in place by their global norm (device kernels or the torch twin)."""
+    if clip is not None:
+        clip.bind([g for g in grads if g is not None])
+        clip.run(max_grad_norm)
 
 
 def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
@@ -224,20 +261,21 @@ def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
 
 def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                     momentum: float = 0.9, rank: int = 4, bucket_mb: Optional[float] = None, seed: int = 714,
-                    **kw):
+                    max_grad_norm: float = 0.0, **kw):
     comm = comm if comm is not None else Communicator()
+    clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
     if kind == "powersgd":
-        return PowerSGDSync(model, comm, lr, momentum, rank, seed=seed, **kw)
+        return PowerSGDSync(model, comm, lr, momentum, rank, seed=seed, **clip, **kw)
     if kind == "powersgd-ref":
-        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed)
+        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed, **clip)
     if kind == "powersgd-api":
-        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed, native_reducer=True)
+        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed, native_reducer=True, **clip)
     if kind == "dense":
-        return _DenseSync(model, comm, lr, momentum, bucket_mb, overlap=kw.get("overlap"))
+        return _DenseSync(model, comm, lr, momentum, bucket_mb, overlap=kw.get("overlap"), **clip)
     if kind == "dense-ref":
-        return ReferenceDenseLoop(model, comm, lr, momentum)
+        return ReferenceDenseLoop(model, comm, lr, momentum, **clip)
     if kind in ("local-sgd-nesterov", "local-adamw"):
-        return LocalOptimizer(model, kind, lr, momentum)
+        return LocalOptimizer(model, kind, lr, momentum, **clip)
     raise ValueError(f"unknown grad sync {kind!r}")
 
 
@@ -247,7 +285,10 @@ class LocalOptimizer:
     (ddp_powersgd_distillBERT_IMDb/IMDb_distillBERT_example.py:57);
     ``local-adamw`` = AdamW(lr) (IMDb_dataset_distributer.py:55)."""
 
-    def __init__(self, model, kind, lr, momentum):
+    def __init__(self, model, kind, lr, momentum, max_grad_norm=0.0):
+        self.model = model
+        self.max_grad_norm = float(max_grad_norm)
+        self.clip = _make_clip(self.max_grad_norm, next(model.parameters()).device)
         if kind == "local-adamw":
             self.opt = torch.optim.AdamW(model.parameters(), lr=lr)
         else:
@@ -262,8 +303,12 @@ class LocalOptimizer:
         _set_param_groups(self.opt, lr, weight_decay)
 
     def step(self):
+        _clip(self.clip, self.max_grad_norm, [p.grad for p in self.model.parameters()])
         self.opt.step()
         return 0
+
+    def clip_stats(self):
+        return self.clip.read() if self.clip is not None else None
 
     def state_dict(self):
         return self.opt.state_dict()

@@ -93,6 +93,7 @@ class TrainConfig:
     lr_milestones: str = ""  # "step": comma-separated epochs, e.g. "15,25"
     lr_gamma: float = 0.1  # "step": factor per milestone passed
     weight_decay: float = 0.0  # L2, every parameter (torch.optim.SGD's weight_decay)
+    max_grad_norm: float = 0.0  # clip by the global L2 norm (ops/gradclip.py); 0 = off, inf = measure only
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -169,6 +170,11 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError(f"augment = {c['augment']!r} needs data_root (the synthetic data is never augmented)")
     if c["weight_decay"] < 0:
         raise ConfigError("weight_decay must be >= 0")
+    if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too
+        raise ConfigError(f"max_grad_norm = {c['max_grad_norm']} must be >= 0 (0 = off, inf = measure only)")
+    if c["max_grad_norm"] > 0 and c["grad_sync"] == "powersgd" and c["overlap"]:
+        raise ConfigError("grad_sync='powersgd' with overlap=True cannot be combined with max_grad_norm > 0: the "
+                          "global norm needs every gradient before a group's pipeline may start")
     if not 0 <= c["lr_min"] <= c["learning_rate"]:
         raise ConfigError(f"lr_min {c['lr_min']} must lie in [0, learning_rate = {c['learning_rate']}]")
     if c["lr_warmup_steps"] < 0 or not c["lr_gamma"] > 0:

@@ -12,7 +12,8 @@ default).  Additions: ``-spawn`` launches all ranks locally (127.0.0.1 rendezvou
 (held-out evaluation every N epochs: loss, top-1, top-k), ``-data_root`` / ``-augment`` / ``-normalize``
 (train and evaluate on the CIFAR-10 files in a directory instead of synthetic data), ``-lr_schedule`` /
 ``-lr_warmup_steps`` / ``-lr_min`` / ``-lr_milestones`` / ``-lr_gamma`` / ``-weight_decay`` (learning-rate
-schedule and L2 weight decay, utils/schedule.py).
+schedule and L2 weight decay, utils/schedule.py), ``-max_grad_norm`` (clip the gradient by its global L2
+norm, ops/gradclip.py; ``inf`` only measures it).
 """
 from __future__ import annotations
 
@@ -73,6 +74,8 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-lr_milestones", type=str, default=None, help="step: comma-separated epochs, e.g. 15,25")
     p.add_argument("-lr_gamma", type=float, default=None, help="step: factor per milestone (default 0.1)")
     p.add_argument("-weight_decay", type=float, default=None, help="L2 weight decay, every parameter (default 0)")
+    p.add_argument("-max_grad_norm", type=float, default=None,
+                   help="clip the gradient by its global L2 norm (default 0 = off; inf = log the norm only)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -87,7 +90,8 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "log_every": "log_every", "seq_len": "seq_len", "eval_every": "eval_every", "eval_size": "eval_size",
         "eval_topk": "eval_topk", "data_root": "data_root", "augment": "augment", "normalize": "normalize",
         "lr_schedule": "lr_schedule", "lr_warmup_steps": "lr_warmup_steps", "lr_min": "lr_min",
-        "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay"}
+        "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay",
+        "max_grad_norm": "max_grad_norm"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
