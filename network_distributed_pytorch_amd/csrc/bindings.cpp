@@ -1264,6 +1264,47 @@ void ce_fwd(torch::Tensor x, torch::Tensor tgt, torch::Tensor dl, torch::Tensor 
   check_launch("launch_ce_fwd");
 }
 
+// the same with label smoothing eps and an optional second target per row: tgt_b (int64 [B]) and lam
+// (fp32 [B], the weight of tgt) come together or not at all
+void ce_soft_fwd(torch::Tensor x, torch::Tensor tgt, torch::Tensor dl, torch::Tensor scratch, torch::Tensor loss,
+                 torch::Tensor ctr, int64_t ignore_index, double eps, c10::optional<torch::Tensor> tgt_b,
+                 c10::optional<torch::Tensor> lam, c10::optional<torch::Tensor> acc) {
+  check_f32(x, "logits"); check_f32(dl, "dl"); check_f32(scratch, "scratch"); check_f32(loss, "loss");
+  float* ap = nullptr;
+  if (acc.has_value()) {
+    check_f32(*acc, "acc");
+    TORCH_CHECK(acc->numel() == 1, "ce_soft_fwd: acc must be a one-element fp32 tensor");
+    ap = acc->data_ptr<float>();
+  }
+  check_dev(tgt, "target"); check_dev(ctr, "ctr");
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && dl.sizes() == x.sizes() && dl.is_contiguous(),
+              "ce_soft_fwd: logits / dl must be contiguous [B, K]");
+  TORCH_CHECK(tgt.scalar_type() == torch::kInt64 && tgt.is_contiguous() && tgt.numel() == x.size(0),
+              "ce_soft_fwd: target must be contiguous int64 [B]");
+  TORCH_CHECK(scratch.numel() >= x.size(0) + 1 && loss.numel() == 1, "ce_soft_fwd: scratch / loss size");
+  TORCH_CHECK(ctr.scalar_type() == torch::kInt32 && ctr.numel() >= 1, "ce_soft_fwd: int32 counter");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) < (1LL << 31) && x.size(1) >= 1 && x.size(1) < (1LL << 31),
+              "ce_soft_fwd: empty batch");
+  TORCH_CHECK(eps >= 0.0 && eps < 1.0, "ce_soft_fwd: 0 <= label_smoothing < 1 required, got ", eps);
+  TORCH_CHECK(tgt_b.has_value() == lam.has_value(), "ce_soft_fwd: target_b and lam come together");
+  const int64_t* bp = nullptr;
+  const float* lp = nullptr;
+  if (tgt_b.has_value()) {
+    check_dev(*tgt_b, "target_b"); check_f32(*lam, "lam");
+    TORCH_CHECK(tgt_b->scalar_type() == torch::kInt64 && tgt_b->is_contiguous() && tgt_b->numel() == x.size(0),
+                "ce_soft_fwd: target_b must be contiguous int64 [B]");
+    TORCH_CHECK(lam->is_contiguous() && lam->numel() == x.size(0), "ce_soft_fwd: lam must be contiguous float32 [B]");
+    bp = tgt_b->data_ptr<int64_t>();
+    lp = lam->data_ptr<float>();
+  }
+  const int B = (int)x.size(0);
+  float* sp = scratch.data_ptr<float>();
+  ndp::launch_ce_soft_fwd(x.data_ptr<float>(), tgt.data_ptr<int64_t>(), bp, lp, (float)eps, B, (int)x.size(1),
+                          ignore_index, dl.data_ptr<float>(), sp, loss.data_ptr<float>(), sp + B,
+                          reinterpret_cast<unsigned*>(ctr.data_ptr<int32_t>()), cur_stream(), ap);
+  check_launch("launch_ce_soft_fwd");
+}
+
 void ce_bwd(torch::Tensor dl, torch::Tensor g, torch::Tensor scratch, torch::Tensor dx) {
   check_f32(dl, "dl"); check_f32(g, "grad"); check_f32(scratch, "scratch"); check_f32(dx, "dx");
   TORCH_CHECK(dl.is_contiguous() && dx.is_contiguous() && dx.sizes() == dl.sizes() && dl.dim() == 2, "ce_bwd: shapes");
@@ -1386,6 +1427,60 @@ void image_batch(torch::Tensor src, torch::Tensor labels, torch::Tensor idx, tor
                           (int)pad, flip_on ? 1 : 0, (uint32_t)(uint64_t)seed, (uint32_t)(uint64_t)epoch, pad_target,
                           err.data_ptr<int32_t>(), cur_stream());
   check_launch("launch_image_batch");
+}
+
+// the same batch with mixup / CutMix against the reversed batch (image_batch.hip): also writes
+// out_target_b (int64 [>= B]) and out_lam (fp32 [>= B]).  mode 1 mixup, 2 CutMix, 3 either;
+// thr = int(mix_prob * 2^24) in [1, 2^24].  No allocation, no sync: capture-safe.
+void image_mix_batch(torch::Tensor src, torch::Tensor labels, torch::Tensor idx, torch::Tensor out,
+                     torch::Tensor out_target, torch::Tensor out_target_b, torch::Tensor out_lam, int64_t m, int64_t B,
+                     std::vector<double> scale, std::vector<double> shift, int64_t pad, bool flip_on, int64_t seed,
+                     int64_t epoch, int64_t pad_target, torch::Tensor err, int64_t mode, int64_t thr) {
+  TORCH_CHECK(src.scalar_type() == torch::kUInt8 && src.dim() == 4 && src.is_contiguous(),
+              "image_mix_batch: src must be contiguous uint8 [N, C, 32, 32]");
+  TORCH_CHECK(src.size(2) == 32 && src.size(3) == 32, "image_mix_batch: H == W == 32 required, got ", src.size(2),
+              " x ", src.size(3));
+  const int64_t N = src.size(0), C = src.size(1);
+  TORCH_CHECK(N >= 1 && N < (1LL << 31), "image_mix_batch: 1 <= N < 2^31 required");
+  TORCH_CHECK(C >= 1 && C <= ndp::kImageMaxC, "image_mix_batch: 1 <= C <= ", ndp::kImageMaxC, " required");
+  TORCH_CHECK((int64_t)scale.size() == C && (int64_t)shift.size() == C,
+              "image_mix_batch: scale / shift need C entries");
+  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.dim() == 1 && labels.is_contiguous() &&
+                  labels.numel() == N, "image_mix_batch: labels must be contiguous int64 [N]");
+  TORCH_CHECK(B >= 1 && B * C < (1LL << 31), "image_mix_batch: 1 <= B, B * C < 2^31 required");
+  TORCH_CHECK(m >= 1 && m <= B, "image_mix_batch: 1 <= m <= B required (m = ", m, ", B = ", B, ")");
+  TORCH_CHECK(idx.scalar_type() == torch::kInt64 && idx.dim() == 1 && idx.is_contiguous() && idx.numel() >= m,
+              "image_mix_batch: idx must be contiguous int64 with >= m elements");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat32 && out.dim() == 4 && out.is_contiguous() && out.size(0) >= B &&
+                  out.size(1) == C && out.size(2) == 32 && out.size(3) == 32,
+              "image_mix_batch: out must be contiguous float32 [>= B, C, 32, 32]");
+  TORCH_CHECK(out_target.scalar_type() == torch::kInt64 && out_target.dim() == 1 && out_target.is_contiguous() &&
+                  out_target.numel() >= B, "image_mix_batch: out_target must be contiguous int64 [>= B]");
+  TORCH_CHECK(out_target_b.scalar_type() == torch::kInt64 && out_target_b.dim() == 1 &&
+                  out_target_b.is_contiguous() && out_target_b.numel() >= B,
+              "image_mix_batch: out_target_b must be contiguous int64 [>= B]");
+  TORCH_CHECK(out_lam.scalar_type() == torch::kFloat32 && out_lam.dim() == 1 && out_lam.is_contiguous() &&
+                  out_lam.numel() >= B, "image_mix_batch: out_lam must be contiguous float32 [>= B]");
+  TORCH_CHECK(pad >= 0 && pad <= 8, "image_mix_batch: 0 <= pad <= 8 required");
+  TORCH_CHECK(mode >= 1 && mode <= 3, "image_mix_batch: mode must be 1 (mixup), 2 (cutmix) or 3 (mixup_cutmix)");
+  TORCH_CHECK(thr >= 1 && thr <= (1LL << 24), "image_mix_batch: 1 <= thr <= 2^24 required");
+  TORCH_CHECK(err.scalar_type() == torch::kInt32 && err.numel() >= 1, "image_mix_batch: err must be int32");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, "image_mix_batch: out must be 16-byte aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 4 == 0, "image_mix_batch: src must be 4-byte aligned");
+  check_dev(src, "src"); check_dev(labels, "labels"); check_dev(idx, "idx"); check_dev(out, "out");
+  check_dev(out_target, "out_target"); check_dev(out_target_b, "out_target_b"); check_dev(out_lam, "out_lam");
+  check_dev(err, "err");
+  ndp::ImageNorm norm{};
+  for (int64_t c = 0; c < C; ++c) {
+    norm.scale[c] = (float)scale[c];
+    norm.shift[c] = (float)shift[c];
+  }
+  ndp::launch_image_mix_batch(src.data_ptr<uint8_t>(), labels.data_ptr<int64_t>(), idx.data_ptr<int64_t>(),
+                              out.data_ptr<float>(), out_target.data_ptr<int64_t>(),
+                              out_target_b.data_ptr<int64_t>(), out_lam.data_ptr<float>(), (int)m, (int)B, N, (int)C,
+                              norm, (int)pad, flip_on ? 1 : 0, (uint32_t)(uint64_t)seed, (uint32_t)(uint64_t)epoch,
+                              pad_target, err.data_ptr<int32_t>(), (int)mode, (uint32_t)thr, cur_stream());
+  check_launch("launch_image_mix_batch");
 }
 
 // fused residual add + LayerNorm (last dim D): y, s (= a + b), mean, rstd are outputs
@@ -1747,6 +1842,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));
+  m.def("image_mix_batch", &image_mix_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
+        py::arg("out_target"), py::arg("out_target_b"), py::arg("out_lam"), py::arg("m"), py::arg("B"),
+        py::arg("scale"), py::arg("shift"), py::arg("pad"), py::arg("flip_on"), py::arg("seed"), py::arg("epoch"),
+        py::arg("pad_target"), py::arg("err"), py::arg("mode"), py::arg("thr"));
+  m.def("ce_soft_fwd", &ce_soft_fwd, py::arg("x"), py::arg("tgt"), py::arg("dl"), py::arg("scratch"),
+        py::arg("loss"), py::arg("ctr"), py::arg("ignore_index"), py::arg("eps"), py::arg("tgt_b") = py::none(),
+        py::arg("lam") = py::none(), py::arg("acc") = py::none());
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   register_comm(m);

@@ -13,6 +13,8 @@
 //        idiom as orth.hip) adds them in row order and writes loss = sum / n_valid and
 //        inv = 1 / n_valid, then re-arms the counter (hipGraph-replay safe).
 //   bwd: dx = dl * (dloss * inv) — one float4 launch.
+//   ce_soft_fwd_kernel: the forward with label smoothing and a second, weighted target per row
+//        (mixup / CutMix); ce_fwd_kernel is the default path and is left as it is.
 // Fixed summation order everywhere: bitwise reproducible.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -114,6 +116,124 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ x
     const float cnt = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
     loss[0] = tot / cnt;  // 0 / 0 = NaN when every row is ignored, like PyTorch
     if (acc != nullptr) acc[0] += tot / cnt;  // running loss sum (logging): no separate add launch
+    inv[0] = 1.f / cnt;
+    __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---- label smoothing and two targets per row (mixup / CutMix) --------------------------------
+// torch.nn.CrossEntropyLoss(label_smoothing=eps) on a row whose target is `ta` with weight lam
+// and `tb` with weight 1 - lam (tgt_b == nullptr: lam = 1, one target):
+//   la = lse - x[ta], lb = lse - x[tb], hard = lam * la + (1 - lam) * lb   (hard = la with one target)
+//   rowloss = (1 - eps) * hard + eps * (lse - sx / K),  sx = sum_k x[k]  (lane order, then the
+//             wave butterfly: a fixed order)
+//   dl[k]   = softmax_k - (1 - eps) * (lam * [k == ta] + (1 - lam) * [k == tb]) - eps / K
+//             (ta == tb: both weights land on k)
+// A row is valid iff ta != ignore; ignored rows give 0 loss and a 0 dl row; a valid row with ta
+// or tb outside [0, K) gets a NaN loss.  The shape, the sc1 row-loss stores, the ticket, the
+// fixed-order mean, inv, acc and the re-arm are ce_fwd_kernel's, and so is the scratch layout:
+// ce_bwd_kernel serves both.  eps arrives by value: a captured graph freezes it.
+__global__ __launch_bounds__(256) void ce_soft_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ tgt,
+                                                          const int64_t* __restrict__ tgt_b,
+                                                          const float* __restrict__ lam, float eps, int B, int K,
+                                                          int64_t ignore, float* __restrict__ dl,
+                                                          float* __restrict__ rowloss, float* __restrict__ loss,
+                                                          float* __restrict__ inv, unsigned* __restrict__ ctr,
+                                                          float* __restrict__ acc) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x * kCeRowsPerWg + wave;
+  if (b < B) {
+    const float* xr = x + (int64_t)b * K;
+    float* dr = dl + (int64_t)b * K;
+    const int64_t ta = tgt[b];
+    const int64_t tb = tgt_b != nullptr ? tgt_b[b] : ta;
+    const float l = tgt_b != nullptr ? lam[b] : 1.f;
+    const bool valid = ta != ignore;
+    const bool in_range = ta >= 0 && ta < K && tb >= 0 && tb < K;
+    const float wa = (1.f - eps) * l, wb = (1.f - eps) * (1.f - l);  // wb = 0 with one target
+    const float uni = eps / (float)K;
+    float m = -INFINITY, s = 0.f, sx = 0.f, lse;
+    if (K <= 64 * kCeRegs) {  // the row in registers: one load pass
+      float v[kCeRegs];
+#pragma unroll
+      for (int i = 0; i < kCeRegs; ++i) {
+        const int k = lane + 64 * i;
+        v[i] = k < K ? xr[k] : -INFINITY;
+        m = fmaxf(m, v[i]);
+        sx += k < K ? v[i] : 0.f;
+      }
+      m = wave_max_f(m);
+#pragma unroll
+      for (int i = 0; i < kCeRegs; ++i) s += lane + 64 * i < K ? expf(v[i] - m) : 0.f;
+      s = wave_sum_f(s);
+      lse = m + logf(s);
+#pragma unroll
+      for (int i = 0; i < kCeRegs; ++i) {
+        const int k = lane + 64 * i;
+        if (k < K) {
+          const float hard = (k == ta ? wa : 0.f) + (k == tb ? wb : 0.f);
+          dr[k] = valid ? (expf(v[i] - lse) - hard) - uni : 0.f;
+        }
+      }
+    } else {
+      for (int k = lane; k < K; k += 64) {
+        const float xv = xr[k];
+        m = fmaxf(m, xv);
+        sx += xv;
+      }
+      m = wave_max_f(m);
+      for (int k = lane; k < K; k += 64) s += expf(xr[k] - m);
+      s = wave_sum_f(s);
+      lse = m + logf(s);
+      for (int k = lane; k < K; k += 64) {
+        const float hard = (k == ta ? wa : 0.f) + (k == tb ? wb : 0.f);
+        dr[k] = valid ? (expf(xr[k] - lse) - hard) - uni : 0.f;
+      }
+    }
+    sx = wave_sum_f(sx);
+    if (lane == 0) {  // sc1 (write-through) store: read back by the last workgroup below
+      float rl = 0.f;
+      if (valid) {
+        rl = __builtin_nanf("");
+        if (in_range) {
+          const float la = lse - xr[ta];
+          const float hard = tgt_b != nullptr ? l * la + (1.f - l) * (lse - xr[tb]) : la;
+          rl = (1.f - eps) * hard + eps * (lse - sx / (float)K);
+        }
+      }
+      __hip_atomic_store(rowloss + b, rl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  // last-arriving workgroup: ce_fwd_kernel's ticket and fixed-order mean (sc1 stores drained
+  // before the ticket, agent-scope loads after it, no release / acquire fence)
+  __shared__ int last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned prev = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = prev == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler order only: the loads below are sc1
+  __shared__ float red[2][4];
+  float a = 0.f, n = 0.f;
+  for (int r = threadIdx.x; r < B; r += 256) {
+    a += __hip_atomic_load(rowloss + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    n += tgt[r] != ignore ? 1.f : 0.f;
+  }
+  a = wave_sum_f(a);
+  n = wave_sum_f(n);
+  if (lane == 0) {
+    red[0][wave] = a;
+    red[1][wave] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float tot = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    const float cnt = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    loss[0] = tot / cnt;  // 0 / 0 = NaN when every row is ignored, like PyTorch
+    if (acc != nullptr) acc[0] += tot / cnt;
     inv[0] = 1.f / cnt;
     __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -296,6 +416,14 @@ void launch_ce_fwd(const float* x, const int64_t* tgt, int B, int K, int64_t ign
   const unsigned wgs = (unsigned)((B + kCeRowsPerWg - 1) / kCeRowsPerWg);
   hipLaunchKernelGGL(ce_fwd_kernel, dim3(wgs), dim3(256), 0, s, x, tgt, B, K, ignore, dl, rowloss, loss, inv, ctr,
                      acc);
+}
+
+void launch_ce_soft_fwd(const float* x, const int64_t* tgt, const int64_t* tgt_b, const float* lam, float eps, int B,
+                        int K, int64_t ignore, float* dl, float* rowloss, float* loss, float* inv, unsigned* ctr,
+                        hipStream_t s, float* acc) {
+  const unsigned wgs = (unsigned)((B + kCeRowsPerWg - 1) / kCeRowsPerWg);
+  hipLaunchKernelGGL(ce_soft_fwd_kernel, dim3(wgs), dim3(256), 0, s, x, tgt, tgt_b, lam, eps, B, K, ignore, dl,
+                     rowloss, loss, inv, ctr, acc);
 }
 
 void launch_ce_bwd(const float* dl, const float* g, const float* inv, float* dx, int64_t n, hipStream_t s) {

@@ -309,6 +309,12 @@ namespace ndp {
 // acc (nullable): acc[0] += loss (a running loss sum)
 void launch_ce_fwd(const float* x, const int64_t* tgt, int B, int K, int64_t ignore, float* dl, float* rowloss,
                    float* loss, float* inv, unsigned* ctr, hipStream_t s, float* acc = nullptr);
+// the same with label smoothing eps and an optional second target per row (mixup / CutMix):
+// row loss = (1 - eps) * (lam * nll(tgt) + (1 - lam) * nll(tgt_b)) + eps * (lse - mean_k x[k]);
+// tgt_b / lam nullable together (then lam = 1); same scratch layout, launch_ce_bwd serves it
+void launch_ce_soft_fwd(const float* x, const int64_t* tgt, const int64_t* tgt_b, const float* lam, float eps, int B,
+                        int K, int64_t ignore, float* dl, float* rowloss, float* loss, float* inv, unsigned* ctr,
+                        hipStream_t s, float* acc = nullptr);
 // dx = dl * (g[0] * inv[0])
 void launch_ce_bwd(const float* dl, const float* g, const float* inv, float* dx, int64_t n, hipStream_t s);
 // fused evaluation metrics: state[4] (fp64) += [loss sum, valid rows, top-1 correct, top-k correct]
@@ -355,6 +361,14 @@ struct ImageNorm {
 void launch_image_batch(const uint8_t* src, const int64_t* labels, const int64_t* idx, float* out,
                         int64_t* out_target, int m, int B, int64_t N, int C, const ImageNorm& norm, int pad,
                         int flip_on, uint32_t seed, uint32_t epoch, int64_t pad_target, int* err, hipStream_t s);
+// the same batch with mixup / CutMix against the reversed batch (row b with row m - 1 - b): also
+// writes out_target_b [B] (the partner's label, the own one when unmixed) and out_lam [B] (the own
+// label's weight, 1 when unmixed).  mode: 1 mixup, 2 CutMix, 3 either by a hash bit; thr =
+// int(mix_prob * 2^24): a row is mixed when its 24-bit hash draw is below thr.
+void launch_image_mix_batch(const uint8_t* src, const int64_t* labels, const int64_t* idx, float* out,
+                            int64_t* out_target, int64_t* out_target_b, float* out_lam, int m, int B, int64_t N,
+                            int C, const ImageNorm& norm, int pad, int flip_on, uint32_t seed, uint32_t epoch,
+                            int64_t pad_target, int* err, int mode, uint32_t thr, hipStream_t s);
 }  // namespace ndp
 
 // ---- fused residual add + LayerNorm over the last dim (layernorm.hip) --------------------

@@ -74,6 +74,8 @@ def default_config(**over) -> Dict[str, Any]:
         lr_schedule="constant", lr_warmup_steps=0, lr_min=0.0, lr_milestones="", lr_gamma=0.1, weight_decay=0.0,
         # clip the gradient by its global L2 norm (ops/gradclip.py): 0 = off, inf = measure only
         max_grad_norm=0.0,
+        # label smoothing (ops/loss.py) and mixup / CutMix of the byte-image batches (ops/image_batch.py)
+        label_smoothing=0.0, mix="none", mix_prob=1.0,
     )
     cfg.update(over)
     return cfg
@@ -170,9 +172,10 @@ def _build_data(config, device, world, rank):
         crop = config.get("augment", "none") == "crop_flip"
         images, labels = load_cifar10(config["data_root"], train=True)
         n = min(config["dataset_size"] or len(images), len(images))
-        ds = Uint8ImageDataset(images[:n], labels[:n], mean, std, pad=4 if crop else 0, flip=crop).to(device)
+        ds = Uint8ImageDataset(images[:n], labels[:n], mean, std, pad=4 if crop else 0, flip=crop,
+                               mix=config.get("mix", "none"), mix_prob=config.get("mix_prob", 1.0)).to(device)
         val = None
-        if want_val:  # the test split, never augmented
+        if want_val:  # the test split, never augmented or mixed
             vi, vl = load_cifar10(config["data_root"], train=False)
             nv = min(eval_size or len(vi), len(vi))
             val = Uint8ImageDataset(vi[:nv], vl[:nv], mean, std).to(device)
@@ -221,9 +224,9 @@ def _loss_fn(config, model, crit):
             out = model(batch["input_ids"], attention_mask=batch["attention_mask"], labels=batch["labels"])
             return out[0]
     else:
-        def f(batch):
-            data, target = batch
-            return crit(model(data), target)
+        def f(batch):  # (data, target), or (data, target, target_b, lam) from a dataset that mixes samples
+            data, target, *mixed = batch
+            return crit(model(data), target, *mixed)
     return f
 
 
@@ -377,7 +380,12 @@ def run_task(config) -> Dict[str, Any]:
     if config["task"] == "mlp":
         model_name = "mlp"
     model = build_model(model_name, config["num_classes"] if config["task"] != "imdb" else 2).to(device)
-    crit = CrossEntropyLoss().to(device)  # fused gfx950 kernel on device (ops/loss.py)
+    label_smoothing = float(config.get("label_smoothing") or 0.0)
+    mix = config.get("mix", "none")
+    # fused gfx950 kernels on device (ops/loss.py)
+    crit = CrossEntropyLoss(label_smoothing=label_smoothing).to(device)
+    if config["task"] == "imdb" and label_smoothing:
+        model.config.label_smoothing = label_smoothing  # DistilBERT computes its own loss
     link = None if config.get("link", "none") == "none" else LINK_PRESETS[config["link"]]
     comm = Communicator(link=link, emulate_world=config.get("emulate_world"),
                         device=device if device.type == "cuda" else None)
@@ -494,7 +502,7 @@ def run_task(config) -> Dict[str, Any]:
                 if "batch" not in static:
                     static["batch"] = _clone_batch(batch)
                     if not isinstance(batch, dict):  # later full batches: written in place, one launch
-                        loader.deliver_into(*static["batch"])
+                        loader.deliver_into(static["batch"][0], static["batch"][1], extra=static["batch"][2:])
                 elif not _delivered(static["batch"], batch):
                     _copy_batch(static["batch"], batch)
                 runner()
@@ -559,16 +567,20 @@ def run_task(config) -> Dict[str, Any]:
         if hasattr(loader.ds, "check_errors"):
             loader.ds.check_errors()
         losses.append(mean)
-        clip_rec = {}
+        epoch_rec = {}
         if clip_on:
-            clip_rec = {"clipped_steps": clip_read()["clipped"] - clipped_base, "max_grad_norm": max_grad_norm}
+            epoch_rec = {"clipped_steps": clip_read()["clipped"] - clipped_base, "max_grad_norm": max_grad_norm}
+        if label_smoothing:
+            epoch_rec["label_smoothing"] = label_smoothing
+        if mix != "none":
+            epoch_rec.update(mix=mix, mix_prob=float(config["mix_prob"]))
         if config.get("verbose", True):
             print_epoch(rank, epoch, mean)
             print(">>>>> Rank ", rank, ", epoch ", epoch, " Finished...\n", flush=True)
         logger.log(kind="epoch", epoch=epoch, mean_loss=mean, steps=i, num_batches=num_batches,
                    bytes_per_step=getattr(sync, "bytes_per_step", None), comm=comm.stats.as_dict(),
                    phase_ms=timer.summary() if timer is not None else None, **({"lr": lr_now} if hyper_on else {}),
-                   **clip_rec)
+                   **epoch_rec)
         if config.get("checkpoint_dir"):
             save_checkpoint(os.path.join(config["checkpoint_dir"], "last.pt"), model, sync, epoch=epoch, step=step,
                             rank=rank, world=world)
@@ -602,6 +614,11 @@ def run_task(config) -> Dict[str, Any]:
     if hyper_on:
         summary["lr_schedule"] = schedule.schedule
         summary["weight_decay"] = weight_decay
+    if label_smoothing:
+        summary["label_smoothing"] = label_smoothing
+    if mix != "none":
+        summary["mix"] = mix
+        summary["mix_prob"] = float(config["mix_prob"])
     if clip_on:
         summary["clipped_steps"] = sync.clip_stats()["clipped"] - clipped_base
         summary["max_grad_norm"] = max_grad_norm

@@ -56,6 +56,7 @@ class DistilBertConfig:
     initializer_range: float = 0.02
     layer_norm_eps: float = 1e-12
     fused_attention: bool = True   # not an HF field: selects csrc/attention.hip on the GPU
+    label_smoothing: float = 0.0   # not an HF field: eps of the classification loss (ops/loss.py)
 
 
 class Embeddings(nn.Module):
@@ -254,7 +255,9 @@ class DistilBertForSequenceClassification(nn.Module):
         if labels is not None:
             lg, lb = logits.view(-1, self.config.num_labels), labels.view(-1)
             # native kernels on: the fused gfx950 cross-entropy (ops/loss.py), same math
-            loss = native_ce(lg, lb) if self.config.fused_attention else F.cross_entropy(lg, lb)
+            eps = self.config.label_smoothing
+            loss = (native_ce(lg, lb, label_smoothing=eps) if self.config.fused_attention
+                    else F.cross_entropy(lg, lb, label_smoothing=eps))
             return SequenceClassifierOutput((loss, logits))
         return SequenceClassifierOutput((logits,))
 

@@ -30,6 +30,8 @@ __all__ = [
     "classification_metrics",
     "ClassificationMetrics",
     "image_batch",
+    "image_mix_batch",
+    "mix_draw",
     "hash4",
     "crop_flip_draw",
     "image_norm_constants",
@@ -281,5 +283,6 @@ def checksum(x: torch.Tensor) -> float:
 
 
 from .metrics import ClassificationMetrics, classification_metrics  # noqa: E402  (fused eval metrics, csrc/loss.hip)
-from .image_batch import crop_flip_draw, hash4, image_batch, image_norm_constants  # noqa: E402  (csrc/image_batch.hip)
+from .image_batch import (crop_flip_draw, hash4, image_batch, image_mix_batch, image_norm_constants,  # noqa: E402
+                          mix_draw)  # (csrc/image_batch.hip)
 from .gradclip import GradClip, clip_grad_norm_  # noqa: E402  (global-norm clipping, csrc/gradclip.hip)

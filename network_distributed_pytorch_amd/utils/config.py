@@ -28,6 +28,7 @@ LINKS = ("none", "1g", "10g", "100g")
 BACKENDS = ("nccl", "gloo")
 AUGMENTS = ("none", "crop_flip")
 NORMALIZES = ("half", "cifar")
+MIXES = ("none", "mixup", "cutmix", "mixup_cutmix")  # ops/image_batch.py: image_mix_batch
 LR_SCHEDULES = ("constant", "step", "cosine")  # utils/schedule.py
 
 
@@ -94,6 +95,11 @@ class TrainConfig:
     lr_gamma: float = 0.1  # "step": factor per milestone passed
     weight_decay: float = 0.0  # L2, every parameter (torch.optim.SGD's weight_decay)
     max_grad_norm: float = 0.0  # clip by the global L2 norm (ops/gradclip.py); 0 = off, inf = measure only
+    # regularisers of the training loss: label smoothing (ops/loss.py, every task) and mixup / CutMix of the
+    # byte-image batches (ops/image_batch.py), lambda ~ Beta(1, 1); both reach a captured step
+    label_smoothing: float = 0.0  # eps of CrossEntropyLoss(label_smoothing=eps), 0 <= eps < 1
+    mix: str = "none"  # "mixup", "cutmix", "mixup_cutmix" (either, per row); training only, needs data_root
+    mix_prob: float = 1.0  # probability that a row is mixed at all, 0 < p <= 1
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -141,7 +147,7 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
     c = config
     for key, allowed in (("grad_sync", GRAD_SYNCS), ("task", TASKS), ("graph_mode", GRAPH_MODES), ("link", LINKS),
                          ("distributed_backend", BACKENDS), ("augment", AUGMENTS), ("normalize", NORMALIZES),
-                         ("lr_schedule", LR_SCHEDULES)):
+                         ("lr_schedule", LR_SCHEDULES), ("mix", MIXES)):
         if c[key] not in allowed:
             raise ConfigError(f"config[{key!r}] = {c[key]!r}; allowed: {list(allowed)}")
     if c["n_workers"] < 1 or not 0 <= c["rank"] < c["n_workers"]:
@@ -168,6 +174,12 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError(f"data_root is for task='cifar' only (task = {c['task']!r})")
     if c["augment"] != "none" and c["data_root"] is None:
         raise ConfigError(f"augment = {c['augment']!r} needs data_root (the synthetic data is never augmented)")
+    if c["mix"] != "none" and c["data_root"] is None:
+        raise ConfigError(f"mix = {c['mix']!r} needs data_root (the synthetic data is never mixed)")
+    if not 0 <= c["label_smoothing"] < 1:  # NaN fails the comparison too
+        raise ConfigError(f"label_smoothing = {c['label_smoothing']} must lie in [0, 1)")
+    if not 0 < c["mix_prob"] <= 1 or c["mix_prob"] * (1 << 24) < 1:
+        raise ConfigError(f"mix_prob = {c['mix_prob']} must lie in (0, 1] (resolution 2^-24)")
     if c["weight_decay"] < 0:
         raise ConfigError("weight_decay must be >= 0")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too

@@ -77,9 +77,15 @@ class Uint8ImageDataset:
     ``Evaluator`` take it as they take any dataset.  ``pad`` / ``flip`` are the augmentation
     ``gather`` applies (and ``gather_into`` with ``augment=True``); which crop and flip a sample
     gets depends on ``(seed, epoch, dataset index)`` only.  ``err`` is the int32 error word an
-    out-of-range index sets; :meth:`check_errors` reads it (one host sync)."""
+    out-of-range index sets; :meth:`check_errors` reads it (one host sync).
 
-    def __init__(self, images_u8: torch.Tensor, labels: torch.Tensor, mean, std, pad: int = 0, flip: bool = False):
+    ``mix`` (``"mixup"`` / ``"cutmix"`` / ``"mixup_cutmix"``) with ``mix_prob`` turns on
+    :func:`ops.image_mix_batch` for the augmented batches: ``gather`` then returns ``(data, target,
+    target_b, lam)`` and ``gather_into(augment=True)`` writes the two extra tensors as well.
+    ``gather_rows`` and ``gather_into(augment=False)``, hence evaluation, never mix."""
+
+    def __init__(self, images_u8: torch.Tensor, labels: torch.Tensor, mean, std, pad: int = 0, flip: bool = False,
+                 mix: str = "none", mix_prob: float = 1.0):
         if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or tuple(images_u8.shape[2:]) != (32, 32):
             raise ValueError(f"Uint8ImageDataset: uint8 [N, C, 32, 32] images expected, got {images_u8.dtype} "
                              f"{tuple(images_u8.shape)}")
@@ -93,6 +99,10 @@ class Uint8ImageDataset:
         if not 0 <= int(pad) <= 8:
             raise ValueError("Uint8ImageDataset: 0 <= pad <= 8 required")
         self.pad, self.flip = int(pad), bool(flip)
+        if mix != "none":
+            from ..ops.image_batch import _mix_mode
+            _mix_mode(mix, mix_prob)  # ValueError on an unknown mode or a probability outside (0, 1]
+        self.mix, self.mix_prob = str(mix), float(mix_prob)
         self.columns = {"data": images_u8.contiguous(), "target": labels.long().contiguous()}
         self.as_tuple = ["data", "target"]
         self.err = torch.zeros(1, dtype=torch.int32, device=images_u8.device)
@@ -107,7 +117,15 @@ class Uint8ImageDataset:
 
     def to(self, device):
         return Uint8ImageDataset(self.columns["data"].to(device), self.columns["target"].to(device), self.mean,
-                                 self.std, self.pad, self.flip)
+                                 self.std, self.pad, self.flip, self.mix, self.mix_prob)
+
+    def _run_mix(self, idx, out, out_target, out_target_b, out_lam, rows, pad_target, epoch, seed):
+        from ..ops.image_batch import image_mix_batch
+
+        return image_mix_batch(self.columns["data"], self.columns["target"], idx, mode=self.mix,
+                               mix_prob=self.mix_prob, out=out, out_target=out_target, out_target_b=out_target_b,
+                               out_lam=out_lam, rows=rows, mean=self.mean, std=self.std, pad=self.pad, flip=self.flip,
+                               seed=seed, epoch=epoch, pad_target=pad_target, err=self.err)
 
     def _run(self, idx, out, out_target, rows, pad_target, epoch, seed, augment):
         from ..ops.image_batch import image_batch
@@ -121,13 +139,24 @@ class Uint8ImageDataset:
         return self._run(idx, None, None, None, -100, 0, 0, False)
 
     def gather(self, idx: torch.Tensor, epoch: int = 0, seed: int = 0):
-        """Fresh ``(fp32 batch, targets)`` of ``idx``, augmented as the dataset was built."""
+        """Fresh ``(fp32 batch, targets)`` of ``idx``, augmented as the dataset was built; with
+        mixing on, ``(fp32 batch, targets, partner targets, lam)``."""
+        if self.mix != "none":
+            return self._run_mix(idx, None, None, None, None, None, -100, epoch, seed)
         return self._run(idx, None, None, None, -100, epoch, seed, True)
 
-    def gather_into(self, idx: torch.Tensor, data_out: torch.Tensor, target_out: torch.Tensor, *, pad_target: int,
-                    epoch: int = 0, seed: int = 0, augment: bool = False) -> None:
+    def gather_into(self, idx: torch.Tensor, data_out: torch.Tensor, target_out: torch.Tensor,
+                    target_b_out: Optional[torch.Tensor] = None, lam_out: Optional[torch.Tensor] = None, *,
+                    pad_target: int, epoch: int = 0, seed: int = 0, augment: bool = False) -> None:
         """Write the batch of ``idx`` into ``data_out`` / ``target_out`` in place; the rows past
-        ``len(idx)`` become zero images with ``target = pad_target``."""
+        ``len(idx)`` become zero images with ``target = pad_target``.  With mixing on and
+        ``augment=True`` the partner targets and ``lam`` go to ``target_b_out`` / ``lam_out``."""
+        if self.mix != "none" and augment:
+            if target_b_out is None or lam_out is None:
+                raise ValueError("Uint8ImageDataset.gather_into: mixing is on, target_b_out and lam_out are needed")
+            self._run_mix(idx, data_out, target_out, target_b_out, lam_out, int(data_out.shape[0]), pad_target,
+                          epoch, seed)
+            return
         self._run(idx, data_out, target_out, int(data_out.shape[0]), pad_target, epoch, seed, augment)
 
     def check_errors(self) -> None:
@@ -249,16 +278,18 @@ class DeviceLoader:
         self._static = None
 
     def deliver_into(self, data: Optional[torch.Tensor], target: Optional[torch.Tensor] = None,
-                     pad_target: int = -100) -> bool:
+                     pad_target: int = -100, extra: Sequence[torch.Tensor] = ()) -> bool:
         """Have every batch of ``data``'s row count written straight into the caller's
         ``(data, target)`` tensors (e.g. a captured step's static inputs): the loader then yields
         those two tensors themselves instead of fresh ones.  Batches of another size (the ragged
         last one) are still yielded fresh.  Only datasets with ``gather_into`` can do this;
-        returns whether delivery is on.  ``deliver_into(None)`` turns it off."""
+        returns whether delivery is on.  ``deliver_into(None)`` turns it off.  ``extra``: the
+        further static tensors of a dataset that mixes samples, ``(target_b, lam)``; they are
+        passed on to ``gather_into`` and yielded after ``data`` and ``target``."""
         if data is None or not hasattr(self.ds, "gather_into"):
             self._static = None
             return False
-        self._static = (data, target, int(pad_target))
+        self._static = (data, target, int(pad_target), tuple(extra))
         return True
 
     def __len__(self):
@@ -286,9 +317,9 @@ class DeviceLoader:
             if not keyed:
                 yield self.ds.gather(idx)
             elif self._static is not None and len(idx) == self._static[0].shape[0]:
-                data, target, pad_target = self._static
-                self.ds.gather_into(idx, data, target, pad_target=pad_target, epoch=epoch, seed=self.seed,
+                data, target, pad_target, extra = self._static
+                self.ds.gather_into(idx, data, target, *extra, pad_target=pad_target, epoch=epoch, seed=self.seed,
                                     augment=True)
-                yield data, target
+                yield (data, target) + extra
             else:
                 yield self.ds.gather(idx, epoch=epoch, seed=self.seed)

@@ -13,7 +13,8 @@ default).  Additions: ``-spawn`` launches all ranks locally (127.0.0.1 rendezvou
 (train and evaluate on the CIFAR-10 files in a directory instead of synthetic data), ``-lr_schedule`` /
 ``-lr_warmup_steps`` / ``-lr_min`` / ``-lr_milestones`` / ``-lr_gamma`` / ``-weight_decay`` (learning-rate
 schedule and L2 weight decay, utils/schedule.py), ``-max_grad_norm`` (clip the gradient by its global L2
-norm, ops/gradclip.py; ``inf`` only measures it).
+norm, ops/gradclip.py; ``inf`` only measures it), ``-label_smoothing`` (ops/loss.py) and ``-mix`` /
+``-mix_prob`` (mixup / CutMix of the byte-image batches, ops/image_batch.py; needs ``-data_root``).
 """
 from __future__ import annotations
 
@@ -76,6 +77,11 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-weight_decay", type=float, default=None, help="L2 weight decay, every parameter (default 0)")
     p.add_argument("-max_grad_norm", type=float, default=None,
                    help="clip the gradient by its global L2 norm (default 0 = off; inf = log the norm only)")
+    p.add_argument("-label_smoothing", type=float, default=None,
+                   help="eps of CrossEntropyLoss(label_smoothing=eps), 0 <= eps < 1 (default 0)")
+    p.add_argument("-mix", type=str, default=None, choices=[None, "none", "mixup", "cutmix", "mixup_cutmix"],
+                   help="mix each training row with the reversed batch's row, lambda ~ Beta(1, 1) (needs -data_root)")
+    p.add_argument("-mix_prob", type=float, default=None, help="probability that a row is mixed (default 1)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -91,7 +97,8 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "eval_topk": "eval_topk", "data_root": "data_root", "augment": "augment", "normalize": "normalize",
         "lr_schedule": "lr_schedule", "lr_warmup_steps": "lr_warmup_steps", "lr_min": "lr_min",
         "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay",
-        "max_grad_norm": "max_grad_norm"}
+        "max_grad_norm": "max_grad_norm", "label_smoothing": "label_smoothing", "mix": "mix",
+        "mix_prob": "mix_prob"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
