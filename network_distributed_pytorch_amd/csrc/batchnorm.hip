@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const float* __restri
     });
   } else {
     for_slice<1>(sl.n0, sl.n1, C, c, HW, [&](int64_t o) {
-      const float dz = (!relu || y[o] > 0.f) ? dy[o] : 0.f;
+      const float dz = (!relu || (mbet ? fmaf(x[o], msc, msh) : y[o]) > 0.f) ? dy[o] : 0.f;  // (mbet: y is null)
       sdz += (double)dz;
       sdzx += (double)dz * (double)((x[o] - mean) * invstd);
     });
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
   } else {
     coefficients();
     for_slice<1>(sl.n0, sl.n1, C, c, HW, [&](int64_t o) {
-      const float dz = (!relu || y[o] > 0.f) ? dy[o] : 0.f;
+      const float dz = (!relu || (mbet ? fmaf(x[o], msc, msh) : y[o]) > 0.f) ? dy[o] : 0.f;  // (mbet: y is null)
       const float xh = (x[o] - mean) * invstd;
       dx[o] = k1 * (dz - mdz - xh * mdzx);
       if (dres) dres[o] = dz;
@@ -1523,7 +1523,8 @@ BnRoute bn_make_route(const BnQuery& q) {
   else if (r.training && q.single && fused_ok) r.path = HW == 64 ? kBnFused64 : kBnFused;
   else if (r.training && (HW == 1 || HW == 2 || HW == 4) && in_range) r.path = kBnThreeKernel;
   else r.path = kBnTwoKernel;
-  // the mask recomputed from x: the float4 two-kernel backward only
+  // the mask recomputed from x: the two-kernel backward on maps of whole float4s only (its scalar
+  // kernels recompute it too, for operands off a 16-byte boundary)
   if (q.mbeta && !(q.bwd && q.relu && HW % 4 == 0 && r.path == kBnTwoKernel)) r.path = kBnNone;
   if (r.path == kBnNone) return r;
 
@@ -1754,11 +1755,11 @@ void launch_bn_bwd(const BnOps& o, const BnRoute& r, hipStream_t s) {
     hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(r.Sa, C), dim3(256), 0, s, o.dy, o.yin, o.x, o.gamma,
                        o.save_mean, o.save_invstd, o.out, o.dres, o.dgamma, o.dbeta, r.Sp > 0 ? o.stats : o.part, N, C, HW,
                        r.Sa, o.relu, o.mbeta, r.Sp);
-  } else {
+  } else {  // (an operand off a 16-byte boundary: the mask recomputed from x takes these kernels too)
     hipLaunchKernelGGL(bn_bwd_stats_kernel<false>, grid, dim3(256), 0, s, o.dy, o.yin, o.x, o.save_mean, o.save_invstd,
-                       o.part, N, C, HW, r.S, o.relu);
+                       o.part, N, C, HW, r.S, o.relu, nullptr, 0, nullptr, o.gamma, o.mbeta);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(256), 0, s, o.dy, o.yin, o.x, o.gamma, o.save_mean,
-                       o.save_invstd, o.out, o.dres, o.dgamma, o.dbeta, o.part, N, C, HW, r.S, o.relu);
+                       o.save_invstd, o.out, o.dres, o.dgamma, o.dbeta, o.part, N, C, HW, r.S, o.relu, o.mbeta, 0);
   }
 }
 

@@ -1,12 +1,17 @@
-"""Run every BatchNorm launch route once, through the bindings, on seeded inputs.
+"""Run BatchNorm launch routes once, through the bindings, on seeded inputs, for a byte comparison
+of two builds.
 
     python tools/bn_route_sweep.py [--dump DIR]
 
-About forty shapes that between them reach every route of tools/bn_route_table.py: each single-launch
-column-block width in its float4 and scalar form, the 8x8 maps with 1 / 2 / 4 row splits, the
-three-kernel and two-kernel paths, evaluation mode, slabs summed inside the launch and by a sum
-launch first (with and without the grad-x addend), statistics from a conv epilogue, misaligned
-operands, the float4 switch off, the BN pair and the stem tail.  Every shape runs one forward and
+About fifty shapes at the sizes the models use, over the kinds of route of tools/bn_route_table.py:
+each single-launch column-block width in its float4 and scalar form, the 8x8 maps with 1 / 2 / 4
+row splits, the three-kernel and two-kernel paths, evaluation mode, slabs summed inside the launch
+and by a sum launch first (with and without the grad-x addend), statistics from a conv epilogue,
+misaligned operands, the float4 switch off, the BN pair and the stem tail.  It compares with
+nothing and does not claim to be complete: the complete list of route variants (one call per
+binding, mode, map size and route row of the recorded table) is tests/bn_route_cases.py, which
+tests/test_bn_route_cases_cpu.py pins and tests/test_bn_routes_gpu.py runs against fp64.  Every
+shape here runs one forward and
 one backward per (residual, relu) case.  Inputs are made on the CPU from a seed and copied over, so
 two builds see the same bits: with --dump every output is written as DIR/<case>.<name>.npy for a
 byte comparison, and under a kernel trace the launches of two builds can be compared in order.
