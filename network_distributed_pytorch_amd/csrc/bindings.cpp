@@ -1753,6 +1753,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TORCH_CHECK(ndp::conv_set_wgrad_stage(n), "conv_set_wgrad_stage: 0 (auto), 1 or 4 images per stage; ", n,
                 " is not built");
   });
+  m.def("conv_set_ds_stream", &ndp::conv_set_ds_stream);
   m.def("conv_pair_launches", &ndp::conv_pair_launches);
   m.def("wino_set_wgrad_prefetch", &ndp::wino_set_wgrad_prefetch);
   m.def("bn_slices", &ndp::bn_slices);

@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "ndp_kernels.h"
+#include "ds_stream.h"
 #include "wino_dpp.h"
 
 namespace ndp {
@@ -1331,6 +1332,9 @@ struct NoTile { static constexpr int IMGS = 0, UPS = 1, IUPS = 1, PQ = 0; };  //
 using WgradStem = WgTile<7, 7, 2, 3, 32, 32, 3, 32, 5, 1, 4>;
 // grad-x of a 1x1 stride-2 conv: the transposed 1x1 product on the DH x DW output map, written to the
 // even pixels of the (2 DH) x (2 DW) plane (UPS = 2 epilogue, odd pixels zero)
+// (These six tiles describe the two 1x1 stride-2 classes to the plan — class_info reads their images per
+// workgroup — and run only where the streamed bodies of ds_stream.h do not: NDP_FUSION_OFF=ds_stream and
+// the 8x8 forward.)
 template <int DH, int DW, int DBM, int DIMGS>
 using DsDgradTile = FwdTile<1, 1, 1, 0, DH, DW, 8, DBM, DIMGS, 2, 2, 4, true, true, 2>;
 using Fwd1x1S2Map8 = FwdTile<1, 1, 2, 0, 8, 8, 8, 64, 4, 2, 2, 4, false, true>;
@@ -1351,26 +1355,41 @@ struct DirectDgradArgs {
   int Cin, Kout, cps;
   int64_t slab;
   const float* addend;
+  DsArgs ds;     // STREAM: the arguments of ds_stream_body
+  DsWgArgs dsw;  //         and of ds_wgrad_body
 };
-template <int DH, int DW, int DBM, int DIMGS, int R, int S, int ST, int PD, int H, int W, int CB, int BM, int NW,
-          int NBPW, int KB>
+// STREAM: both halves are the streamed bodies of ds_stream.h (no LDS, every wave on its own) instead of
+// conv_fwd_body / conv_wgrad_body
+template <bool STREAM, int DH, int DW, int DBM, int DIMGS, int R, int S, int ST, int PD, int H, int W, int CB, int BM,
+          int NW, int NBPW, int KB>
 __global__ __launch_bounds__(256) void direct_pair_kernel(DirectDgradArgs A, uint3 ga, const float* __restrict__ x,
                                                           const float* __restrict__ dy, float* __restrict__ part,
                                                           int Cin, int Kout, int imgs, uint3 gw) {
   static_assert(NW <= 4, "grad-W workgroup within the pair's 256 threads");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
   const unsigned na = ga.x * ga.y * ga.z;
   unsigned b = blockIdx.x;
-  if (b < na) {
-    conv_fwd_body<DsDgradTile<DH, DW, DBM, DIMGS>>(A.dy, A.w, A.dx, A.part, A.Cin, A.Kout, A.cps, A.slab, A.addend,
-                                                   ConvBnStats{},
-                                                   make_uint3(b % ga.x, (b / ga.x) % ga.y, b / (ga.x * ga.y)), ga, smem);
+  if constexpr (STREAM) {
+    if (b < na) ds_stream_body<2 * DH, true>(A.ds, make_uint3(b % ga.x, 0, b / ga.x), ga);
+    else ds_wgrad_body<H>(A.dsw, make_uint3(b - na, 0, 0));
   } else {
-    if (threadIdx.x >= 64 * NW) return;
-    b -= na;
-    conv_wgrad_body<WgTile<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>>(
-        x, dy, part, Cin, Kout, imgs, make_uint3(b % gw.x, (b / gw.x) % gw.y, b / (gw.x * gw.y)), smem);
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (b < na) {
+      conv_fwd_body<DsDgradTile<DH, DW, DBM, DIMGS>>(A.dy, A.w, A.dx, A.part, A.Cin, A.Kout, A.cps, A.slab, A.addend,
+                                                     ConvBnStats{},
+                                                     make_uint3(b % ga.x, (b / ga.x) % ga.y, b / (ga.x * ga.y)), ga, smem);
+    } else {
+      if (threadIdx.x >= 64 * NW) return;
+      b -= na;
+      conv_wgrad_body<WgTile<R, S, ST, PD, H, W, CB, BM, NW, NBPW, KB>>(
+          x, dy, part, Cin, Kout, imgs, make_uint3(b % gw.x, (b / gw.x) % gw.y, b / (gw.x * gw.y)), smem);
+    }
   }
+}
+
+// The streamed 1x1 stride-2 grad-W on its own
+template <int MAP>
+__global__ __launch_bounds__(256) void ds_wgrad_kernel(DsWgArgs A) {
+  ds_wgrad_body<MAP>(A, make_uint3(blockIdx.x, 0, 0));
 }
 
 // ---- the downsample block's two forward convs in ONE launch --------------------------------
@@ -1395,6 +1414,12 @@ __global__ __launch_bounds__(256) void ds_fwd_pair_kernel(FwdPart a, uint3 ga, F
     conv_fwd_body<Fwd1x1S2Map8>(b.x, b.w, b.y, b.part, b.Cin, b.Kout, b.cps, b.slab, nullptr, ConvBnStats{},
                                        make_uint3(k % gb.x, (k / gb.x) % gb.y, k / (gb.x * gb.y)), gb, smem);
   }
+}
+
+// The streamed 1x1 stride-2 forward (DGRAD false) / grad-x (true) on its own
+template <int MAP, bool DGRAD>
+__global__ __launch_bounds__(256) void ds_stream_kernel(DsArgs A) {
+  ds_stream_body<MAP, DGRAD>(A, make_uint3(blockIdx.x, 0, blockIdx.z), make_uint3(gridDim.x, 1, gridDim.z));
 }
 
 // ---- launch helpers -------------------------------------------------------------------------
@@ -1444,8 +1469,83 @@ static FwdPart fwd_part(const FwdArgs& a, uint3& grid) {
 template <typename P>
 static P take(P& slot) { return std::exchange(slot, P{}); }
 
+// ---- the streamed 1x1 stride-2 bodies (ds_stream.h) ----
+// On unless NDP_FUSION_OFF=ds_stream (A/B arm) or conv_set_ds_stream(0): off runs conv_fwd_body on the
+// Fwd1x1S2* / DsDgradTile tiles, which stay for that arm (and for the plan's ClassInfo) only.
+static int g_ds_stream = -1;  // -1: by the switch
+void conv_set_ds_stream(int on) { g_ds_stream = on < 0 ? -1 : (on ? 1 : 0); }
+static bool ds_stream_on() {
+  static const bool env_off = [] {
+    const char* e = getenv("NDP_FUSION_OFF");
+    const std::string s = std::string(",") + (e ? e : "") + ",";
+    return s.find(",ds_stream,") != std::string::npos || s.find(",all,") != std::string::npos;
+  }();
+  return g_ds_stream < 0 ? !env_off : g_ds_stream == 1;
+}
+// FwdTile T -> the streamed body that replaces it (MAP 0: none).  Not the 8x8 forward: in the
+// flagship it runs inside ds_fwd_pair_kernel, whose time is conv1's and did not move with a streamed
+// 1x1 half (profiles/r11/README.md).
+template <typename T>
+struct DsOf {
+  static constexpr bool DGRAD = T::UPS == 2;
+  static constexpr int MAP = (T::R == 1 && T::S == 1 && T::PD == 0 && T::CK == 8 && (DGRAD ? T::ST == 1 : T::ST == 2) &&
+                              (DGRAD || T::H == 4))
+                                 ? (DGRAD ? 2 * T::H : T::H)
+                                 : 0;
+};
+static_assert(DsOf<Fwd1x1S2Map8>::MAP == 0 && DsOf<Dgrad1x1S2Map8>::MAP == 8 && DsOf<Fwd1x1S2Map4>::MAP == 4 &&
+                  DsOf<Dgrad1x1S2Map4>::MAP == 4 && DsOf<Fwd3x3S2>::MAP == 0 && DsOf<Dgrad3x3Map4>::MAP == 0,
+              "the 1x1 stride-2 tiles but the 8x8 forward, and no other");
+// live waves per workgroup of the streamed bodies for `tiles` independent wave tiles: as few as
+// still give every CU a workgroup (a wave alone on its SIMD keeps its MFMA chain and its loads
+// to itself; the pair kernels launch 256 threads, the surplus waves leave at once)
+static int ds_wpw(int64_t tiles) { return tiles >= 4 * 256 ? 4 : tiles >= 2 * 256 ? 2 : 1; }
+// Arguments and grid of the streamed body for launch `a`, with the split-K normalisation of fwd_part
+// (the same grid z, channel ranges and slabs: the plan's ksplit decides, the consumers do not change).
+// The grid's x is this launcher's: the 32-pixel x 32-channel wave tiles, ds_wpw of them per
+// workgroup.  false: switched off.
+template <int MAP, bool DGRAD>
+static bool ds_part(const FwdArgs& a, DsArgs& d, uint3& grid) {
+  using G = DsGeom<MAP>;
+  if (!ds_stream_on() || a.Cin % 8 != 0 || a.Kout % 32 != 0) return false;
+  const int nchunks = a.Cin / 8;
+  const int ksplit = (a.ksplit < 1 || a.part == nullptr) ? 1 : a.ksplit;
+  const int cps = (nchunks + ksplit - 1) / ksplit;
+  if (nchunks % cps != 0) return false;
+  const int gz = nchunks / cps;
+  const int tiles = (int)(((int64_t)a.B * G::PQ + 31) / 32) * (a.Kout / 32);
+  const int wpw = ds_wpw((int64_t)tiles * gz);
+  d = DsArgs{a.x, a.w, a.y, a.part, gz > 1 ? nullptr : a.addend, a.Cin, a.Kout, a.B, cps * 8, wpw, tiles,
+             (int64_t)a.B * a.Kout * G::PQ};
+  grid = make_uint3((unsigned)((tiles + wpw - 1) / wpw), 1u, (unsigned)gz);
+  return true;
+}
+// run_fwd on the streamed body: the same slab sums and return value
+template <typename T>
+static bool run_ds(const FwdArgs& a, int& ret) {
+  constexpr int MAP = DsOf<T>::MAP;
+  constexpr bool DGRAD = DsOf<T>::DGRAD;
+  DsArgs d;
+  uint3 grid;
+  if (!ds_part<MAP, DGRAD>(a, d, grid)) return false;
+  hipLaunchKernelGGL((ds_stream_kernel<MAP, DGRAD>), dim3(grid.x, 1, grid.z), dim3(256), 0, a.s, d);
+  const int ksplit = (int)grid.z;
+  ret = 1;
+  if (ksplit > 1 && a.defer && !DGRAD) {
+    ret = ksplit;
+  } else if (ksplit > 1) {
+    if constexpr (!DGRAD) launch_slab_sum(a.part, a.y, d.slab, ksplit, a.s, a.addend);
+    else launch_slab_sum_ups<T>(a.part, a.y, d.slab, ksplit, a.s, a.addend);
+  }
+  return true;
+}
+
 template <typename T>
 static int run_fwd(const FwdArgs& a) {
+  if constexpr (DsOf<T>::MAP != 0) {
+    int ret;
+    if (run_ds<T>(a, ret)) return ret;
+  }
   auto k = conv_fwd_kernel<T::R, T::S, T::ST, T::PD, T::H, T::W, T::CK, T::BM, T::IMGS, T::WM, T::NBUF, T::KB,
                            T::TRANSW, T::VEC, T::UPS, T::SCH, T::IUPS, T::PSPLIT>;
   static bool attr = false;  // once per instantiation (> 64 KiB of LDS needs the opt-in)
@@ -1497,8 +1597,32 @@ template <typename T>
 static uint3 wgrad_grid(const WgArgs& a) {
   return make_uint3((unsigned)(a.B / a.imgs), (unsigned)(a.Kout / T::BM), (unsigned)((a.Cin + T::CB - 1) / T::CB));
 }
+// Arguments and grid of the streamed 1x1 stride-2 grad-W (ds_wgrad_body) for launch `a`: one wave tile per
+// slice and 32 x 32 block, ds_wpw of them per workgroup; the slices and the slab layout are the plan's.
+// false: switched off.
+static bool ds_wg_part(const WgArgs& a, DsWgArgs& d, uint3& grid) {
+  if (!ds_stream_on() || a.Cin % 32 != 0 || a.Kout % 32 != 0) return false;
+  const int tiles = (a.B / a.imgs) * (a.Kout / 32) * (a.Cin / 32);
+  const int wpw = ds_wpw(tiles);
+  d = DsWgArgs{a.x, a.dy, a.part, a.Cin, a.Kout, a.imgs, wpw, tiles};
+  grid = make_uint3((unsigned)((tiles + wpw - 1) / wpw), 1u, 1u);
+  return true;
+}
+template <int MAP>
+static bool run_ds_wgrad(const WgArgs& a) {
+  DsWgArgs d;
+  uint3 g;
+  if (!ds_wg_part(a, d, g)) return false;
+  hipLaunchKernelGGL((ds_wgrad_kernel<MAP>), dim3(g.x), dim3(256), 0, a.s, d);
+  if (a.dw != nullptr) launch_slab_sum(a.part, a.dw, (int64_t)a.Kout * a.Cin, a.B / a.imgs, a.s);
+  return true;
+}
+
 template <typename T>
 static void run_wgrad(const WgArgs& a) {
+  if constexpr (T::R == 1 && T::S == 1 && T::ST == 2 && T::PD == 0) {
+    if (run_ds_wgrad<T::H>(a)) return;
+  }
   auto k = conv_wgrad_kernel<T::R, T::S, T::ST, T::PD, T::H, T::W, T::CB, T::BM, T::NW, T::NBPW, T::KB, T::IPS>;
   static bool attr = false;
   if (!attr) { set_lds(k, T::LDS_BYTES); attr = true; }
@@ -1816,17 +1940,27 @@ void run_pair(const float* dy, const float* u, float* dx, int B, int inC, int ou
 template <typename F, typename Wg>
 int run_direct_pair(const FwdArgs& a, const WgArgs& p) {
   static_assert(std::is_same<F, DsDgradTile<F::H, F::W, F::BM, F::IMGS>>::value, "the tile direct_pair_kernel runs");
-  auto k = direct_pair_kernel<F::H, F::W, F::BM, F::IMGS, Wg::R, Wg::S, Wg::ST, Wg::PD, Wg::H, Wg::W, Wg::CB, Wg::BM,
-                              Wg::NW, Wg::NBPW, Wg::KB>;
-  constexpr size_t lds = std::max(F::LDS_BYTES, Wg::LDS_BYTES);
-  static bool attr = false;
-  if (!attr) { set_lds(k, lds); attr = true; }
   uint3 ga;
   const FwdPart f = fwd_part<F>(a, ga);
-  const DirectDgradArgs d{f.x, f.w, f.y, f.part, f.Cin, f.Kout, f.cps, f.slab, ga.z > 1 ? nullptr : a.addend};
-  const uint3 gw = wgrad_grid<Wg>(p);
-  const unsigned n = ga.x * ga.y * ga.z + gw.x * gw.y * gw.z;
-  hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, a.s, d, ga, p.x, p.dy, p.part, p.Cin, p.Kout, p.imgs, gw);
+  DirectDgradArgs d{f.x, f.w, f.y, f.part, f.Cin, f.Kout, f.cps, f.slab, ga.z > 1 ? nullptr : a.addend, DsArgs{}, DsWgArgs{}};
+  uint3 gw = wgrad_grid<Wg>(p);
+  // the streamed halves (ds_stream.h): their own grids, the same slabs; off: the old pair
+  const auto launch = [&](auto k, size_t lds, const uint3& gx) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const unsigned n = gx.x * gx.y * gx.z + gw.x * gw.y * gw.z;
+    hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, a.s, d, gx, p.x, p.dy, p.part, p.Cin, p.Kout, p.imgs, gw);
+  };
+#define NDP_DIRECT_PAIR(STREAM)                                                                              \
+  direct_pair_kernel<STREAM, F::H, F::W, F::BM, F::IMGS, Wg::R, Wg::S, Wg::ST, Wg::PD, Wg::H, Wg::W, Wg::CB, \
+                     Wg::BM, Wg::NW, Wg::NBPW, Wg::KB>
+  uint3 gs, gsw;
+  if (ds_part<DsOf<F>::MAP, true>(a, d.ds, gs) && ds_wg_part(p, d.dsw, gsw)) {
+    gw = gsw;
+    launch(NDP_DIRECT_PAIR(true), 0, gs);
+  } else {
+    launch(NDP_DIRECT_PAIR(false), std::max(F::LDS_BYTES, Wg::LDS_BYTES), ga);
+  }
+#undef NDP_DIRECT_PAIR
   ++g_pair_launches;
   if (ga.z > 1) launch_slab_sum_ups<F>(a.part, a.y, f.slab, (int)ga.z, a.s, a.addend);
   return 1;

@@ -513,6 +513,9 @@ bool wgrad_pipe_off();  // NDP_FUSION_OFF=wgrad_pipe
 void wino_set_wgrad_prefetch(bool on);
 bool conv_set_wgrad_stage(int n);  // false: a value that is not built (nothing changed)
 int64_t conv_pair_launches();
+// the streamed forward / grad-x bodies of the 1x1 stride-2 classes (fusion `ds_stream`, ds_stream.h):
+// 1 = on, 0 = off (conv_fwd_body on the 8-channel chunk tiles), -1 = by NDP_FUSION_OFF (the default)
+void conv_set_ds_stream(int on);
 // several layers' transforms in one launch (ops/conv.py WinoBank)
 constexpr int kMaxWino = 16;
 struct WinoBatch {

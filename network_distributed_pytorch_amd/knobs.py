@@ -29,6 +29,8 @@ FUSIONS = {
     "wgrad_pipe": "grad-W operand pipelining: LDS prefetch of the next image in the layer1 Winograd grad-W, several "
                   "images per stage in the layer2 direct grad-W (csrc/winograd.hip, csrc/conv.hip)",
     "ds_fwd_pair": "a downsample block's conv1 and 1x1 downsample forward in one launch (csrc/conv.hip)",
+    "ds_stream": "1x1 stride-2 downsample forward / grad-x / grad-W as streamed GEMMs: operands from registers, no LDS, "
+                 "no barrier, the same sums bit for bit (csrc/ds_stream.h; off: conv_fwd_body / conv_wgrad_body)",
     "stem_pool": "stem BN -> ReLU -> max-pool in one pass (ops/batchnorm.py)",
     "stem_bwd": "stem max-pool backward + BN backward apply from the pooled gradient in one pass (ops/batchnorm.py)",
     "bn_pair": "downsample block's bn2 + downsample BN + ReLU in one launch per direction (ops/batchnorm.py)",
