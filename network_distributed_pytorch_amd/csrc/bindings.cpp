@@ -1386,6 +1386,36 @@ void grad_scale(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, 
   check_launch("launch_grad_scale");
 }
 
+// exponential moving average of the weights (ema.hip) over a SegPlan table with src = live
+// tensor, dst = shadow: ctr: grad_clip_ctr_words(n_blocks) zeroed int32 (re-armed), block: the
+// EmaBlock {decay, weight, updates, pad} as 4 int32 words.  No allocation, no sync: capture-safe.
+void ema_update(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
+                torch::Tensor ctr, torch::Tensor block, double decay, bool warmup) {
+  check_dev(entries, "entries"); check_dev(prefix, "prefix"); check_dev(ctr, "ctr"); check_dev(block, "block");
+  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "ema_update: table too large");
+  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
+              "seg table size mismatch");
+  TORCH_CHECK(ctr.scalar_type() == torch::kInt32 && ctr.numel() >= ndp::grad_clip_ctr_words(n_blocks),
+              "ema_update: ctr must be int32 of >= grad_clip_ctr_words(n_blocks) elements");
+  TORCH_CHECK(block.scalar_type() == torch::kInt32 && block.numel() == 4, "ema_update: the block is 4 int32 words");
+  TORCH_CHECK((float)decay > 0.0f && (float)decay < 1.0f, "ema_update: decay must be in (0, 1)");
+  ndp::launch_ema_update(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
+                         (int)n_entries, n_blocks, reinterpret_cast<unsigned*>(ctr.data_ptr<int32_t>()),
+                         reinterpret_cast<ndp::EmaBlock*>(block.data_ptr<int32_t>()), (float)decay, warmup ? 1 : 0,
+                         cur_stream());
+  check_launch("launch_ema_update");
+}
+
+void ema_swap(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks) {
+  check_dev(entries, "entries"); check_dev(prefix, "prefix");
+  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "ema_swap: table too large");
+  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
+              "seg table size mismatch");
+  ndp::launch_ema_swap(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
+                       (int)n_entries, n_blocks, cur_stream());
+  check_launch("launch_ema_swap");
+}
+
 // batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
 // [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
 // shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
@@ -1840,6 +1870,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_clip_ctr_words", &ndp::grad_clip_ctr_words);
   m.def("grad_scale", &grad_scale, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
         py::arg("clip"));
+  m.def("ema_update", &ema_update, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
+        py::arg("ctr"), py::arg("block"), py::arg("decay"), py::arg("warmup"));
+  m.def("ema_swap", &ema_swap, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"));
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));

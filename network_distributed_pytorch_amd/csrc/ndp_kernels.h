@@ -345,6 +345,23 @@ void launch_grad_sqnorm(const SegEntry* entries, const int64_t* block_prefix, in
 // v *= clip->coef over the table; every workgroup returns at once when coef == 1
 void launch_grad_scale(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
                        const ClipBlock* clip, hipStream_t s);
+
+// ---- exponential moving average of the weights (ema.hip) ----------------------------------
+// A SegEntry table with src = live tensor, dst = shadow (chunks = 1; vec: both 16-byte aligned);
+// ctr: grad_clip_ctr_words(n_blocks) zeroed uint32 (the two-level tickets, re-armed by the
+// kernel), block: the 16-byte EmaBlock.
+struct EmaBlock {
+  float decay;       // d of the last run
+  float weight;      // w = 1 - d of the last run
+  uint32_t updates;  // runs so far
+  uint32_t pad;
+};
+// s += w * (x - s) over the table with the decay of run block->updates (decay, warmup by value)
+void launch_ema_update(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
+                       unsigned* ctr, EmaBlock* block, float decay, int warmup, hipStream_t s);
+// x <-> s over the table, bitwise
+void launch_ema_swap(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
+                     hipStream_t s);
 }  // namespace ndp
 
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------

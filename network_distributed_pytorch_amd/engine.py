@@ -34,12 +34,13 @@ import torch
 import torch.distributed as dist
 
 from .ops import gemm_tuning
+from .ops.ema import WeightEma
 from .ops.loss import CrossEntropyLoss
 from .ops.metrics import ClassificationMetrics
 from .models import build_model
 from .parallel.comm import LINK_PRESETS, Communicator
 from .parallel.trainer import build_grad_sync
-from .utils.checkpoint import load_checkpoint, save_checkpoint
+from .utils.checkpoint import load_checkpoint, restore_ema, save_checkpoint
 from .utils.config import ConfigError, validate_config
 from .utils.cifar import load_cifar10
 from .utils.data import (NORMALIZE, DeviceLoader, SyntheticCIFAR10, SyntheticIMDb, SyntheticMLPData,
@@ -49,7 +50,7 @@ from .utils.metrics import JsonlLogger, PhaseTimer, print_epoch, print_eval
 from .utils.partition_helper import DataPartitioner
 from .utils.schedule import LrSchedule
 
-__all__ = ["setup", "run_task", "cleanup", "device_for", "default_config", "evaluate", "Evaluator"]
+__all__ = ["setup", "run_task", "cleanup", "device_for", "default_config", "evaluate", "Evaluator", "ema_targets"]
 
 
 def default_config(**over) -> Dict[str, Any]:
@@ -76,6 +77,8 @@ def default_config(**over) -> Dict[str, Any]:
         max_grad_norm=0.0,
         # label smoothing (ops/loss.py) and mixup / CutMix of the byte-image batches (ops/image_batch.py)
         label_smoothing=0.0, mix="none", mix_prob=1.0,
+        # exponential moving average of the weights (ops/ema.py): 0 = off
+        ema_decay=0.0, ema_warmup=True,
     )
     cfg.update(over)
     return cfg
@@ -405,10 +408,21 @@ def run_task(config) -> Dict[str, Any]:
                            bucket_mb=config.get("bucket_mb"), seed=config["seed"], **extra)
     start_epoch = 0
     step = 0
+    info = None
     if config.get("resume"):
         info = load_checkpoint(config["resume"], model, sync)
         start_epoch = info["epoch"] + 1
         step = info["step"]
+    # weight EMA (ops/ema.py): built over the (resumed) weights, then updated by the sync behind every
+    # step's last update launch.  Off: nothing is allocated, launched, logged or uploaded.
+    ema = None
+    ema_decay = float(config.get("ema_decay") or 0.0)
+    if ema_decay > 0:
+        ema_names, ema_tensors = ema_targets(model)
+        ema = WeightEma(ema_tensors, ema_decay, warmup=bool(config.get("ema_warmup", True)))
+        if info is not None:
+            restore_ema(ema, info.get("ema"), config["resume"])
+        sync.attach_ema(ema)
     log_path = config.get("log_file")
     if log_path and "{rank}" in log_path:  # one file per rank
         logger = JsonlLogger(log_path.format(rank=rank), rank, all_ranks=True)
@@ -469,6 +483,12 @@ def run_task(config) -> Dict[str, Any]:
     losses = []
     clip_on = max_grad_norm > 0
     clipped_base = None  # the block's counter when this run began (a resume restarts clipped_steps)
+
+    def ema_record():
+        # host read of the EMA block; after a replay its last write may sit on the side stream
+        if runner is not None:
+            runner.join()
+        return {"ema_decay": ema_decay, "ema_warmup": ema.warmup, "ema_updates": ema.read()["updates"]}
 
     def clip_read():
         # host read of the clip block; after a replay the block's last write may sit on the side stream
@@ -574,6 +594,8 @@ def run_task(config) -> Dict[str, Any]:
             epoch_rec["label_smoothing"] = label_smoothing
         if mix != "none":
             epoch_rec.update(mix=mix, mix_prob=float(config["mix_prob"]))
+        if ema is not None:
+            epoch_rec.update(ema_record())
         if config.get("verbose", True):
             print_epoch(rank, epoch, mean)
             print(">>>>> Rank ", rank, ", epoch ", epoch, " Finished...\n", flush=True)
@@ -583,12 +605,24 @@ def run_task(config) -> Dict[str, Any]:
                    **epoch_rec)
         if config.get("checkpoint_dir"):
             save_checkpoint(os.path.join(config["checkpoint_dir"], "last.pt"), model, sync, epoch=epoch, step=step,
-                            rank=rank, world=world)
+                            rank=rank, world=world,
+                            **({"ema": ema.state_dict(ema_names) if rank == 0 else None} if ema is not None else {}))
         if evaluator is not None and (epoch + 1) % eval_every == 0:
             # after runner.join() above: the pass reads the parameters of the last update.  Its
             # all-reduce is accounted in the record, not in comm.stats / bytes_per_step, and its
             # time is kept out of the training throughput
             rec = dict(evaluator(), epoch=epoch)
+            if ema is not None:
+                # the same evaluator (same captured graph) on the averaged weights: exchanged in place,
+                # no second model.  Every weight-derived tensor (Winograd / Toeplitz banks) is rebuilt
+                # by each forward pass from the weights it finds, so nothing stale crosses a swap.
+                ema.swap()
+                try:
+                    avg = evaluator()
+                finally:
+                    ema.swap()
+                rec.update(ema_loss=avg["loss"], ema_top1=avg["top1"], ema_topk=avg["topk"],
+                           eval_s=rec["eval_s"] + avg["eval_s"], comm_bytes=rec["comm_bytes"] + avg["comm_bytes"])
             if device.type == "cuda":
                 torch.cuda.synchronize()
             eval_s += rec["eval_s"]
@@ -625,11 +659,30 @@ def run_task(config) -> Dict[str, Any]:
     if eval_every:
         summary["eval"] = evals
         summary["eval_s"] = eval_s
+    if ema is not None:
+        summary.update(ema_record())
     logger.log(kind="summary", **{k: v for k, v in summary.items()})
     logger.close()
+    if ema is not None:
+        summary["ema"] = ema
     summary["model"] = model
     summary["sync"] = sync
     return summary
+
+
+def ema_targets(model: torch.nn.Module):
+    """``(names, tensors)`` a weight EMA of ``model`` covers: every parameter, then every persistent
+    fp32 buffer (BatchNorm running statistics), under their ``state_dict`` names.  Integer buffers
+    (``num_batches_tracked``) and non-persistent scratch are left out."""
+    live = model.state_dict(keep_vars=True)  # persistent tensors only, the objects themselves
+    params = {id(p) for p in model.parameters()}
+    seen, names = set(), []
+    for want_param in (True, False):
+        for k, v in live.items():
+            if (id(v) in params) == want_param and id(v) not in seen and (want_param or v.dtype == torch.float32):
+                seen.add(id(v))  # a tied tensor is averaged once, under its first name
+                names.append(k)
+    return names, [live[k].detach() for k in names]
 
 
 def _clip_step_record(stats) -> Dict[str, Any]:

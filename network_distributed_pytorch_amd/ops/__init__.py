@@ -37,6 +37,8 @@ __all__ = [
     "image_norm_constants",
     "GradClip",
     "clip_grad_norm_",
+    "WeightEma",
+    "ema_decay_at",
 ]
 
 
@@ -286,3 +288,4 @@ from .metrics import ClassificationMetrics, classification_metrics  # noqa: E402
 from .image_batch import (crop_flip_draw, hash4, image_batch, image_mix_batch, image_norm_constants,  # noqa: E402
                           mix_draw)  # (csrc/image_batch.hip)
 from .gradclip import GradClip, clip_grad_norm_  # noqa: E402  (global-norm clipping, csrc/gradclip.hip)
+from .ema import WeightEma, ema_decay_at  # noqa: E402  (weight EMA, csrc/ema.hip)

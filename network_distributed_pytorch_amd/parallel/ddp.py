@@ -157,6 +157,14 @@ class BucketedDataParallel:
         if self.max_grad_norm > 0:
             self.clip = GradClip(self.device, capacity=1, blocks=(self.numel + 2047) // 2048)
             self.clip.bind([self.g])
+        self.ema = None  # ops.WeightEma updated behind the SGD launch (attach_ema)
+
+    def attach_ema(self, ema):
+        """Keep ``ema`` (ops/ema.py) of the weights: one launch behind every step's SGD launch, on
+        its stream (the side stream in stream mode), inside the captured step; part of
+        :meth:`snapshot`.  None detaches."""
+        assert not capturing(), "attach_ema() inside a graph capture"
+        self.ema = ema
 
     def clip_stats(self) -> Optional[Dict[str, Any]]:
         """``{"norm", "coef", "clipped", "steps"}`` of the gradient clip (a host sync), or None when
@@ -249,14 +257,23 @@ class BucketedDataParallel:
         hy = self.hyper.dev if self._hyper_on else None
         if capturing() and hy is None:
             self._captured_by_value = True
+        ema = self.ema
         if self.clip is None:
-            return lambda: sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+            if ema is None:
+                return lambda: sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+
+            def sgd_ema():  # the EMA reads the weights the SGD launch wrote: same stream, behind it
+                sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+                ema.update()
+            return sgd_ema
         clip, max_norm = self.clip, self.max_grad_norm
         clip.bind([self.g])  # a no-op unless the device tables were restored (upload_epoch)
 
         def clip_sgd():  # norm of sum g / N, arena scaled in place, then the SGD: all on one stream
             clip.run(max_norm, n)
             sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+            if ema is not None:
+                ema.update()
         return clip_sgd
 
     def plan_hyper(self, pairs):
@@ -337,7 +354,8 @@ class BucketedDataParallel:
 
     def snapshot(self):
         return {"x": self.x.clone(), "buf": self.buf.clone(), "step_count": self.step_count,
-                **({"clip": self.clip.snapshot()} if self.clip is not None else {})}
+                **({"clip": self.clip.snapshot()} if self.clip is not None else {}),
+                **({"ema": self.ema.snapshot()} if self.ema is not None else {})}
 
     def restore(self, snap):
         self.x.copy_(snap["x"])
@@ -345,6 +363,8 @@ class BucketedDataParallel:
         self.step_count = snap["step_count"]
         if self.clip is not None:
             self.clip.restore(snap["clip"])
+        if self.ema is not None and "ema" in snap:
+            self.ema.restore(snap["ema"])
 
     def count_step(self):
         if not capturing():

@@ -627,6 +627,7 @@ class PowerSGDOptimizer:
         self._r1_key = None
         # global-norm clip of this rank's gradients (ops/gradclip.py): table, partials and the
         # {norm, coef, clipped, steps} block exist before any capture
+        self.ema = None  # ops.WeightEma updated behind the last update launch (attach_ema)
         self.clip: Optional[GradClip] = None
         if self.max_grad_norm > 0:
             self.clip = GradClip(self.device, capacity=len(self.params),
@@ -768,6 +769,7 @@ class PowerSGDOptimizer:
                 self._r1_key = key
             r1 = slice(self.r1_start, self.arena_numel)
             lr, mom, hy = self.lr, self.momentum, self._hyper()
+            ema = self.ema
 
             def rank1():
                 self._r1_pack.run()
@@ -776,7 +778,11 @@ class PowerSGDOptimizer:
                                  self.r1_upd if self.write_grad else None, lr, mom, hyper=hy)
                 if self.write_grad:
                     self._r1_out.run()
+                if ema is not None:  # behind the step's last update launch, same side item
+                    ema.update()
             self.comm.side_launch(rank1)
+        elif self.ema is not None:
+            self.comm.side_launch(self.ema.update)
         self.comm.side_join()
 
     # -- helpers -------------------------------------------------------------------------
@@ -891,6 +897,16 @@ class PowerSGDOptimizer:
         ``max_grad_norm`` is 0.  The norm is this rank's own."""
         return self.clip.read() if self.clip is not None else None
 
+    def attach_ema(self, ema):
+        """Keep ``ema`` (ops/ema.py) of the weights: one launch per step behind the step's last
+        update launch, on its stream.  Serial step and :meth:`phases`: the tail of
+        :meth:`phase_update`, inside the captured segment.  Overlap groups: the last side-stream
+        item, ahead of the release of the next compute graph (the table may hold BatchNorm
+        running statistics, which the next forward rewrites).  Part of :meth:`snapshot`.  None
+        detaches."""
+        assert not capturing(), "attach_ema() inside a graph capture"
+        self.ema = ema
+
     # -- the step --------------------------------------------------------------------------
     # Serial path: step() = phase_p -> comm_p -> phase_q -> comm_q -> phase_update.  The
     # phases are exposed separately so a piecewise hipGraph can capture the compute phases
@@ -954,6 +970,8 @@ class PowerSGDOptimizer:
                     self._r1_out.run()
         else:
             self._step_torch(N, [p.grad for p in self.params])
+        if self.ema is not None:
+            self.ema.update()
         self.count_step()
 
     def count_step(self):
@@ -1229,6 +1247,7 @@ class PowerSGDOptimizer:
     def snapshot(self):
         # e / m in the full layout: the warm-up steps between snapshot and restore may re-plan
         return {**({"clip": self.clip.snapshot()} if self.clip is not None else {}),
+                **({"ema": self.ema.snapshot()} if self.ema is not None else {}),
                 "x": self.x.clone(), "e": self._full_arena(self._e).clone(), "p_prev": self.p_prev.clone(),
                 "lazy_pending": self._lazy_pending, "m": self.m.clone(), "q": self.buf.q_warm.clone(),
                 "step_count": self.step_count, "bits": self.bits_communicated, "q_ready": self._q_ready,
@@ -1247,6 +1266,8 @@ class PowerSGDOptimizer:
         self.rng.set_state(snap["rng"])
         if self.clip is not None:
             self.clip.restore(snap["clip"])
+        if self.ema is not None and "ema" in snap:
+            self.ema.restore(snap["ema"])
 
     # -- checkpoint / resume ---------------------------------------------------------------
     def state_dict(self):

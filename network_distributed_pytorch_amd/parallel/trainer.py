@@ -22,6 +22,11 @@ Every strategy takes ``max_grad_norm`` (0: off; ``inf``: measure only) and has `
 ``{"norm", "coef", "clipped", "steps"}`` block of the global-norm gradient clip (ops/gradclip.py), or
 None when clipping is off.  The PowerSGD arms clip each rank's own gradient before the error
 feedback; the dense arms and the local optimisers clip the averaged gradient before the update.
+
+Every strategy has ``attach_ema(ema)``: an ``ops.WeightEma`` (ops/ema.py) whose ``update()`` then
+runs once per step, behind the step's last update launch and on its stream (inside a captured
+step); the native engines' ``snapshot()`` / ``restore()`` include it.  Nothing attached: every
+launch, snapshot and state dict is what it is without.
 """
 from __future__ import annotations
 
@@ -73,6 +78,9 @@ class PowerSGDSync:
     def clip_stats(self):
         return self.opt.clip_stats()
 
+    def attach_ema(self, ema):
+        self.opt.attach_ema(ema)
+
     def count_step(self):
         self.opt.count_step()
 
@@ -115,9 +123,13 @@ class ReferencePowerSGDLoop:
         self.bytes_per_step = b["total"]
         self._payloads = [b["p"], b["rank1"], b["q"]]  # reducer.py:126, :132, :145
         self.collectives_per_step = 3 if comm.active else 0
+        self.ema = None
 
     def collective_payloads(self):
         return list(self._payloads)
+
+    def attach_ema(self, ema):
+        self.ema = ema
 
     def zero_grad(self):
         for p in self.params:
@@ -150,6 +162,8 @@ class ReferencePowerSGDLoop:
         self.first = False
         for p, g in zip(self.params, grads):
             p.data.add_(g, alpha=-self.lr)
+        if self.ema is not None:
+            self.ema.update()
         return self.bytes_per_step * 8
 
     def clip_stats(self):
@@ -166,9 +180,13 @@ class ReferenceDenseLoop:
         self.bytes_per_step = 4 * sum(p.numel() for p in model.parameters())
         self._payloads = [4 * p.numel() for p in model.parameters()]  # ddp_init.py:61, one per param
         self.collectives_per_step = len(list(model.parameters())) if comm.active else 0
+        self.ema = None
 
     def collective_payloads(self):
         return list(self._payloads)
+
+    def attach_ema(self, ema):
+        self.ema = ema
 
     def zero_grad(self):
         self.opt.zero_grad()
@@ -180,6 +198,8 @@ class ReferenceDenseLoop:
         bits = average_gradients(self.model, self.comm)
         _clip(self.clip, self.max_grad_norm, [p.grad for p in self.model.parameters()])
         self.opt.step()
+        if self.ema is not None:
+            self.ema.update()
         return bits
 
     def clip_stats(self):
@@ -229,6 +249,9 @@ class _DenseSync:
 
     def clip_stats(self):
         return self.ddp.clip_stats()
+
+    def attach_ema(self, ema):
+        self.ddp.attach_ema(ema)
 
     def count_step(self):
         self.ddp.count_step()
@@ -295,6 +318,10 @@ class LocalOptimizer:
             self.opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, nesterov=True)
         self.bytes_per_step = 0
         self.collectives_per_step = 0
+        self.ema = None
+
+    def attach_ema(self, ema):
+        self.ema = ema
 
     def zero_grad(self):
         self.opt.zero_grad()
@@ -305,6 +332,8 @@ class LocalOptimizer:
     def step(self):
         _clip(self.clip, self.max_grad_norm, [p.grad for p in self.model.parameters()])
         self.opt.step()
+        if self.ema is not None:
+            self.ema.update()
         return 0
 
     def clip_stats(self):

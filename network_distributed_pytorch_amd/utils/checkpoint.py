@@ -4,7 +4,10 @@ Layout of a checkpoint ``<path>``:
 
 * ``<path>`` — written by rank 0: the model ``state_dict`` with torchvision / HF key names
   (compatible with the reference's model definitions), rank 0's gradient-sync state, the
-  epoch / step counters, the world size and rank 0's torch RNG.
+  epoch / step counters, the world size and rank 0's torch RNG.  With a weight EMA (ops/ema.py)
+  also ``"ema"``: ``{"shadow": {state_dict name: tensor}, "updates", "decay", "weight"}``; the
+  replicas' shadows are identical, so one copy serves every rank, and ``state["ema"]["shadow"]``
+  loads into a model with ``load_state_dict(strict=False)``.
 * ``<path>.rank<r>`` — written by EVERY rank r: that rank's gradient-sync state and RNG
   streams.  PowerSGD's error memory ``e = (g + e) - P Q^T`` is rank-local (M is the local
   gradient), and ranks are seeded ``seed + rank``, so a resume at N > 1 must give each
@@ -29,7 +32,7 @@ import torch
 
 from ..parallel.comm import get_rank, world_size
 
-__all__ = ["save_checkpoint", "load_checkpoint", "rank_file", "CheckpointMismatch"]
+__all__ = ["save_checkpoint", "load_checkpoint", "restore_ema", "rank_file", "CheckpointMismatch"]
 
 
 class CheckpointMismatch(RuntimeError):
@@ -65,7 +68,8 @@ def _set_rng(state: Dict[str, Any]):
 
 def save_checkpoint(path: str, model: torch.nn.Module, sync=None, epoch: int = 0, step: int = 0,
                     extra: Optional[Dict[str, Any]] = None, rank: Optional[int] = None,
-                    world: Optional[int] = None) -> Optional[str]:
+                    world: Optional[int] = None, ema: Optional[Dict[str, Any]] = None) -> Optional[str]:
+    """``ema``: ``WeightEma.state_dict(names)``, stored under ``"ema"`` in the rank-0 file."""
     rank = get_rank() if rank is None else rank
     world = world_size() if world is None else world
     sync_state = sync.state_dict() if sync is not None and hasattr(sync, "state_dict") else None
@@ -83,12 +87,17 @@ def save_checkpoint(path: str, model: torch.nn.Module, sync=None, epoch: int = 0
         "extra": extra or {},
         **_rng_state(),
     }
+    if ema is not None:
+        state["ema"] = ema
     _atomic_save(state, path)
     return path
 
 
 def load_checkpoint(path: str, model: torch.nn.Module, sync=None, strict: bool = True,
-                    rank: Optional[int] = None, world: Optional[int] = None) -> Dict[str, Any]:
+                    rank: Optional[int] = None, world: Optional[int] = None, ema=None) -> Dict[str, Any]:
+    """``ema``: a ``WeightEma`` over ``model``'s tensors; it gets the checkpoint's shadow and update
+    count back, or, from a checkpoint without one, a warning and the loaded weights as its shadow.
+    The returned dict carries the stored state under ``"ema"`` (None when absent)."""
     rank = get_rank() if rank is None else rank
     world = world_size() if world is None else world
     state = torch.load(path, map_location="cpu", weights_only=True)
@@ -114,4 +123,15 @@ def load_checkpoint(path: str, model: torch.nn.Module, sync=None, strict: bool =
     if sync is not None and local.get("sync") is not None and hasattr(sync, "load_state_dict"):
         sync.load_state_dict(local["sync"])
     _set_rng(local)
-    return {"epoch": state["epoch"], "step": state["step"], "extra": state.get("extra", {})}
+    if ema is not None:
+        restore_ema(ema, state.get("ema"), path)
+    return {"epoch": state["epoch"], "step": state["step"], "extra": state.get("extra", {}), "ema": state.get("ema")}
+
+
+def restore_ema(ema, saved: Optional[Dict[str, Any]], path: str = "checkpoint") -> None:
+    """Give ``ema`` the ``saved`` state, or (None) warn and start its shadow from the live tensors."""
+    if saved is not None:
+        ema.load_state_dict(saved)
+        return
+    warnings.warn(f"{path} holds no weight EMA: the shadow starts from the loaded weights")
+    ema.reset()

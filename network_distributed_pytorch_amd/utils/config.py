@@ -14,6 +14,8 @@ import dataclasses
 import typing
 from typing import Any, Dict, Optional
 
+import numpy as np
+
 __all__ = ["TrainConfig", "validate_config", "ConfigError"]
 
 
@@ -100,6 +102,9 @@ class TrainConfig:
     label_smoothing: float = 0.0  # eps of CrossEntropyLoss(label_smoothing=eps), 0 <= eps < 1
     mix: str = "none"  # "mixup", "cutmix", "mixup_cutmix" (either, per row); training only, needs data_root
     mix_prob: float = 1.0  # probability that a row is mixed at all, 0 < p <= 1
+    # exponential moving average of the weights (ops/ema.py), evaluated and checkpointed next to them
+    ema_decay: float = 0.0  # 0 = off; 0 < decay < 1: shadow += (1 - d) * (weights - shadow) after every step
+    ema_warmup: bool = True  # d = min(decay, (n + 1) / (n + 10)) for update n (the TF / timm warm-up)
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -182,6 +187,9 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError(f"mix_prob = {c['mix_prob']} must lie in (0, 1] (resolution 2^-24)")
     if c["weight_decay"] < 0:
         raise ConfigError("weight_decay must be >= 0")
+    if not 0 <= c["ema_decay"] < 1 or (c["ema_decay"] > 0 and not 0 < np.float32(c["ema_decay"]) < 1):
+        # NaN fails the comparison too; a decay that rounds to 0 or 1 in fp32 is no average
+        raise ConfigError(f"ema_decay = {c['ema_decay']} must lie in [0, 1) (0 = off)")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too
         raise ConfigError(f"max_grad_norm = {c['max_grad_norm']} must be >= 0 (0 = off, inf = measure only)")
     if c["max_grad_norm"] > 0 and c["grad_sync"] == "powersgd" and c["overlap"]:

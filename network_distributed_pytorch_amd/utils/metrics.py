@@ -100,3 +100,7 @@ def print_eval(rank: int, epoch: int, rec: dict):
     topk = "" if rec.get("topk") is None else ", top-{} {:.4f}".format(rec["k"], rec["topk"])
     print("     Rank ", rank, ", epoch ", epoch, " eval: loss {:.6f}, top-1 {:.4f}{} over {} samples ({:.3f} s)".format(
         rec["loss"], rec["top1"], topk, rec["n"], rec.get("eval_s", 0.0)), flush=True)
+    if "ema_loss" in rec:  # the same pass on the averaged weights (ops/ema.py)
+        topk = "" if rec.get("ema_topk") is None else ", top-{} {:.4f}".format(rec["k"], rec["ema_topk"])
+        print("     Rank ", rank, ", epoch ", epoch, " eval (EMA weights): loss {:.6f}, top-1 {:.4f}{}".format(
+            rec["ema_loss"], rec["ema_top1"], topk), flush=True)

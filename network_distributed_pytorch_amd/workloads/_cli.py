@@ -14,7 +14,8 @@ default).  Additions: ``-spawn`` launches all ranks locally (127.0.0.1 rendezvou
 ``-lr_warmup_steps`` / ``-lr_min`` / ``-lr_milestones`` / ``-lr_gamma`` / ``-weight_decay`` (learning-rate
 schedule and L2 weight decay, utils/schedule.py), ``-max_grad_norm`` (clip the gradient by its global L2
 norm, ops/gradclip.py; ``inf`` only measures it), ``-label_smoothing`` (ops/loss.py) and ``-mix`` /
-``-mix_prob`` (mixup / CutMix of the byte-image batches, ops/image_batch.py; needs ``-data_root``).
+``-mix_prob`` (mixup / CutMix of the byte-image batches, ops/image_batch.py; needs ``-data_root``),
+``-ema_decay`` / ``-ema_warmup`` (exponential moving average of the weights, ops/ema.py).
 """
 from __future__ import annotations
 
@@ -82,6 +83,10 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-mix", type=str, default=None, choices=[None, "none", "mixup", "cutmix", "mixup_cutmix"],
                    help="mix each training row with the reversed batch's row, lambda ~ Beta(1, 1) (needs -data_root)")
     p.add_argument("-mix_prob", type=float, default=None, help="probability that a row is mixed (default 1)")
+    p.add_argument("-ema_decay", type=float, default=None,
+                   help="keep an exponential moving average of the weights with this decay (default 0 = off)")
+    p.add_argument("-ema_warmup", type=int, default=None, choices=[None, 0, 1],
+                   help="EMA decay warm-up min(decay, (n + 1) / (n + 10)) (default 1)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -98,7 +103,7 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "lr_schedule": "lr_schedule", "lr_warmup_steps": "lr_warmup_steps", "lr_min": "lr_min",
         "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay",
         "max_grad_norm": "max_grad_norm", "label_smoothing": "label_smoothing", "mix": "mix",
-        "mix_prob": "mix_prob"}
+        "mix_prob": "mix_prob", "ema_decay": "ema_decay"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
@@ -118,6 +123,8 @@ def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional
         c["reuse_query"] = bool(args.reuse_query)
     if args.overlap is not None:
         c["overlap"] = bool(args.overlap)
+    if args.ema_warmup is not None:
+        c["ema_warmup"] = bool(args.ema_warmup)
     if args.quiet:
         c["verbose"] = False
     if args.trace:
