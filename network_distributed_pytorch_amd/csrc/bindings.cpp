@@ -9,6 +9,7 @@
 
 #include <cstring>
 
+#include "arrival.h"
 #include "ndp_kernels.h"
 #include "plan.h"
 
@@ -183,6 +184,22 @@ unsigned long long* ctr_ptr(const torch::Tensor& c, int64_t need, const char* wh
   return reinterpret_cast<unsigned long long*>(c.data_ptr());
 }
 
+// A SegPlan table as the table kernels take it (one workgroup per block: n_blocks is their grid)
+struct SegArgs {
+  const SegEntry* entries;
+  const int64_t* prefix;
+  int n_entries;
+  int64_t n_blocks;
+};
+SegArgs seg_args(const torch::Tensor& entries, const torch::Tensor& prefix, int64_t n_entries, int64_t n_blocks,
+                 const char* who) {
+  check_dev(entries, "entries"); check_dev(prefix, "prefix");
+  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), who, ": table too large");
+  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
+              "seg table size mismatch");
+  return {reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(), (int)n_entries, n_blocks};
+}
+
 // p_out + p_ctr: in-kernel split-K finish (P written into p_out, wide plans only); seg_*: the
 // rank-1 pack run by the same launch's extra blocks
 void psgd_p(torch::Tensor geom, torch::Tensor ptrs, torch::Tensor items, torch::Tensor q_warm,
@@ -214,13 +231,11 @@ void psgd_p(torch::Tensor geom, torch::Tensor ptrs, torch::Tensor items, torch::
   if (seg_entries.has_value() && seg_n > 0 && seg_blocks > 0) {
     TORCH_CHECK(max_rank <= ndp::kUWideMaxRank, "psgd_p: fused rank-1 pack needs rank <= 16");
     TORCH_CHECK(seg_prefix.has_value(), "psgd_p: seg table needs its prefix");
-    check_dev(*seg_entries, "seg_entries"); check_dev(*seg_prefix, "seg_prefix");
-    TORCH_CHECK(seg_entries->numel() >= seg_n * (int64_t)sizeof(SegEntry) && seg_prefix->numel() >= seg_n,
-                "seg table size mismatch");
-    fin.seg = reinterpret_cast<const SegEntry*>(seg_entries->data_ptr());
-    fin.seg_prefix = seg_prefix->data_ptr<int64_t>();
-    fin.n_seg = (int)seg_n;
-    nsb = seg_blocks;
+    const SegArgs t = seg_args(*seg_entries, *seg_prefix, seg_n, seg_blocks, "psgd_p");
+    fin.seg = t.entries;
+    fin.seg_prefix = t.prefix;
+    fin.n_seg = t.n_entries;
+    nsb = t.n_blocks;
   }
   ndp::launch_psgd_p(reinterpret_cast<const MatGeom*>(geom.data_ptr()),
                      reinterpret_cast<const MatPtrs*>(ptrs.data_ptr()),
@@ -339,12 +354,25 @@ void rank1_step(torch::Tensor buf, double div, torch::Tensor mom, torch::Tensor 
   check_launch("launch_rank1_step");
 }
 
+// the two-level arrival tickets (arrival.h) of a table launch: zeroed by the caller, re-armed by the kernel
+unsigned* ticket_ptr(const torch::Tensor& ctr, int64_t n_blocks, const char* who) {
+  check_dev(ctr, "ctr");
+  TORCH_CHECK(ctr.scalar_type() == torch::kInt32 && ctr.numel() >= ndp::arrive_ctr_words(n_blocks), who,
+              ": ctr must be int32 of >= arrive_ctr_words(n_blocks) elements");
+  return reinterpret_cast<unsigned*>(ctr.data_ptr<int32_t>());
+}
+// a 16-byte device block (ClipBlock, EmaBlock) held as 4 int32 words
+template <typename T>
+T* block4_ptr(const torch::Tensor& t, const char* who) {
+  static_assert(sizeof(T) == 16, "a 4-word block");
+  check_dev(t, "block");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.numel() == 4, who, ": the block is 4 int32 words");
+  return reinterpret_cast<T*>(t.data_ptr<int32_t>());
+}
+
 void seg_reduce(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks) {
-  check_dev(entries, "entries"); check_dev(prefix, "prefix");
-  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
-              "seg table size mismatch");
-  ndp::launch_seg_reduce(reinterpret_cast<const SegEntry*>(entries.data_ptr()),
-                         prefix.data_ptr<int64_t>(), (int)n_entries, n_blocks, cur_stream());
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "seg_reduce");
+  ndp::launch_seg_reduce(t.entries, t.prefix, t.n_entries, t.n_blocks, cur_stream());
   check_launch("launch_seg_reduce");
 }
 
@@ -1349,70 +1377,45 @@ void cls_metrics(torch::Tensor x, torch::Tensor tgt, torch::Tensor state, torch:
 }
 
 // global-norm gradient clipping (gradclip.hip) over a SegPlan table of the gradients: partial
-// [>= n_blocks] fp64 scratch, ctr: grad_clip_ctr_words(n_blocks) zeroed int32 (re-armed), clip: the ClipBlock
+// [>= n_blocks] fp64 scratch, ctr: arrive_ctr_words(n_blocks) zeroed int32 (re-armed), clip: the ClipBlock
 // {norm, coef, clipped, steps} as 4 int32 words.  No allocation, no sync: capture-safe.
 void grad_sqnorm(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
                  torch::Tensor partial, torch::Tensor ctr, torch::Tensor clip, double max_norm, double div) {
-  check_dev(entries, "entries"); check_dev(prefix, "prefix"); check_dev(partial, "partial");
-  check_dev(ctr, "ctr"); check_dev(clip, "clip");
-  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "grad_sqnorm: table too large");
-  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
-              "seg table size mismatch");
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "grad_sqnorm");
+  check_dev(partial, "partial");
   TORCH_CHECK(partial.scalar_type() == torch::kFloat64 && partial.numel() >= n_blocks,
               "grad_sqnorm: partial must be float64 of >= n_blocks elements");
-  TORCH_CHECK(ctr.scalar_type() == torch::kInt32 && ctr.numel() >= ndp::grad_clip_ctr_words(n_blocks),
-              "grad_sqnorm: ctr must be int32 of >= grad_clip_ctr_words(n_blocks) elements");
-  TORCH_CHECK(clip.scalar_type() == torch::kInt32 && clip.numel() == 4, "grad_sqnorm: clip block is 4 int32 words");
   TORCH_CHECK(max_norm > 0.0, "grad_sqnorm: max_norm must be > 0 (inf: measure only)");
   TORCH_CHECK(div >= 1.0, "grad_sqnorm: div must be >= 1");
-  ndp::launch_grad_sqnorm(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
-                          (int)n_entries, n_blocks, partial.data_ptr<double>(),
-                          reinterpret_cast<unsigned*>(ctr.data_ptr<int32_t>()),
-                          reinterpret_cast<ndp::ClipBlock*>(clip.data_ptr<int32_t>()), (float)max_norm, (float)div,
-                          cur_stream());
+  ndp::launch_grad_sqnorm(t.entries, t.prefix, t.n_entries, t.n_blocks, partial.data_ptr<double>(),
+                          ticket_ptr(ctr, n_blocks, "grad_sqnorm"), block4_ptr<ndp::ClipBlock>(clip, "grad_sqnorm"),
+                          (float)max_norm, (float)div, cur_stream());
   check_launch("launch_grad_sqnorm");
 }
 
 void grad_scale(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
                 torch::Tensor clip) {
-  check_dev(entries, "entries"); check_dev(prefix, "prefix"); check_dev(clip, "clip");
-  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "grad_scale: table too large");
-  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
-              "seg table size mismatch");
-  TORCH_CHECK(clip.scalar_type() == torch::kInt32 && clip.numel() == 4, "grad_scale: clip block is 4 int32 words");
-  ndp::launch_grad_scale(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
-                         (int)n_entries, n_blocks, reinterpret_cast<const ndp::ClipBlock*>(clip.data_ptr<int32_t>()),
-                         cur_stream());
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "grad_scale");
+  ndp::launch_grad_scale(t.entries, t.prefix, t.n_entries, t.n_blocks,
+                         block4_ptr<const ndp::ClipBlock>(clip, "grad_scale"), cur_stream());
   check_launch("launch_grad_scale");
 }
 
 // exponential moving average of the weights (ema.hip) over a SegPlan table with src = live
-// tensor, dst = shadow: ctr: grad_clip_ctr_words(n_blocks) zeroed int32 (re-armed), block: the
+// tensor, dst = shadow: ctr: arrive_ctr_words(n_blocks) zeroed int32 (re-armed), block: the
 // EmaBlock {decay, weight, updates, pad} as 4 int32 words.  No allocation, no sync: capture-safe.
 void ema_update(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
                 torch::Tensor ctr, torch::Tensor block, double decay, bool warmup) {
-  check_dev(entries, "entries"); check_dev(prefix, "prefix"); check_dev(ctr, "ctr"); check_dev(block, "block");
-  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "ema_update: table too large");
-  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
-              "seg table size mismatch");
-  TORCH_CHECK(ctr.scalar_type() == torch::kInt32 && ctr.numel() >= ndp::grad_clip_ctr_words(n_blocks),
-              "ema_update: ctr must be int32 of >= grad_clip_ctr_words(n_blocks) elements");
-  TORCH_CHECK(block.scalar_type() == torch::kInt32 && block.numel() == 4, "ema_update: the block is 4 int32 words");
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "ema_update");
   TORCH_CHECK((float)decay > 0.0f && (float)decay < 1.0f, "ema_update: decay must be in (0, 1)");
-  ndp::launch_ema_update(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
-                         (int)n_entries, n_blocks, reinterpret_cast<unsigned*>(ctr.data_ptr<int32_t>()),
-                         reinterpret_cast<ndp::EmaBlock*>(block.data_ptr<int32_t>()), (float)decay, warmup ? 1 : 0,
-                         cur_stream());
+  ndp::launch_ema_update(t.entries, t.prefix, t.n_entries, t.n_blocks, ticket_ptr(ctr, n_blocks, "ema_update"),
+                         block4_ptr<ndp::EmaBlock>(block, "ema_update"), (float)decay, warmup ? 1 : 0, cur_stream());
   check_launch("launch_ema_update");
 }
 
 void ema_swap(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks) {
-  check_dev(entries, "entries"); check_dev(prefix, "prefix");
-  TORCH_CHECK(n_entries >= 0 && n_blocks >= 0 && n_blocks < (1LL << 31), "ema_swap: table too large");
-  TORCH_CHECK(entries.numel() >= n_entries * (int64_t)sizeof(SegEntry) && prefix.numel() >= n_entries,
-              "seg table size mismatch");
-  ndp::launch_ema_swap(reinterpret_cast<const SegEntry*>(entries.data_ptr()), prefix.data_ptr<int64_t>(),
-                       (int)n_entries, n_blocks, cur_stream());
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "ema_swap");
+  ndp::launch_ema_swap(t.entries, t.prefix, t.n_entries, t.n_blocks, cur_stream());
   check_launch("launch_ema_swap");
 }
 
@@ -1726,6 +1729,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("SIZEOF_MATGEOM") = (int)sizeof(MatGeom);
   m.attr("SIZEOF_MATPTRS") = (int)sizeof(MatPtrs);
   m.attr("SIZEOF_SEGENTRY") = (int)sizeof(SegEntry);
+  m.attr("SEG_BLOCK_ELEMS") = (int)ndp::kSegBlockElems;
   m.attr("MAX_RANK") = ndp::kMaxRank;
   m.def("build_plan", &build_plan, "Build the PowerSGD execution plan (host)", py::arg("shapes"), py::arg("rank"),
         py::arg("supports") = std::vector<std::pair<int64_t, int64_t>>{});
@@ -1867,7 +1871,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ctr"), py::arg("ignore_index"), py::arg("k"), py::arg("pred") = py::none());
   m.def("grad_sqnorm", &grad_sqnorm, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
         py::arg("partial"), py::arg("ctr"), py::arg("clip"), py::arg("max_norm"), py::arg("div"));
-  m.def("grad_clip_ctr_words", &ndp::grad_clip_ctr_words);
+  m.def("arrive_ctr_words", &ndp::arrive_ctr_words);
+  m.def("grad_clip_ctr_words", &ndp::arrive_ctr_words);  // the earlier name, kept for its callers
   m.def("grad_scale", &grad_scale, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
         py::arg("clip"));
   m.def("ema_update", &ema_update, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),

@@ -1,24 +1,18 @@
 // Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False) over a
-// SegEntry table of fp32 gradients, in two launches of one workgroup per table block
-// (kSegBlockElems = 2048 elements, the block -> entry search of seg_block.h):
+// SegEntry table of fp32 gradients, in two launches of one workgroup per table block (the table
+// walk of seg_block.h):
 //
 //   grad_sqnorm: S = sum v^2 with every square formed and accumulated in fp64 by an explicit
 //        fma((double)v, (double)v, acc) (no fp32 overflow: 1e25 has a finite norm; independent of
 //        -ffp-contract).  The block partial goes out as an sc1 (write-through) store, the
-//        workgroup drains it and draws an arrival ticket; the LAST arriver (the loss.hip idiom:
-//        no fence, no workgroup ever waits for another, no floating-point atomic) sums the
-//        partials and writes the ClipBlock
+//        workgroup drains it and draws its two-level arrival ticket (arrival.h); the LAST arriver
+//        sums the partials and writes the ClipBlock
 //            norm = (float)(sqrt(S) / (double)div)
 //            q    = max_norm / (norm + 1e-6f)           (fp32, IEEE division)
 //            coef = (q < 1 || q != q) ? q : 1           (a NaN norm gives a NaN coefficient)
 //            steps += 1;  clipped += coef != 1
 //        and re-arms the ticket (hipGraph-replay safe).  max_norm / div go by value: a captured
 //        graph freezes them.
-//        The ticket has two levels: kClipGroup consecutive workgroups share a first-level
-//        counter, and the last of a group draws the top-level one.  Agent-scope atomics on ONE
-//        address retire at about 13 ns each (measured with a single counter: 78 us for
-//        ResNet-18's 5708 workgroups, 423 us for DistilBERT's 32693, whatever the bytes), several
-//        times the read itself; the groups' counters lie 256 B apart and proceed in parallel.
 //   grad_scale:  one scalar load of coef per workgroup; coef == 1: return at once, nothing is
 //        written (the gradients stay bitwise as they were, -0 and NaN payloads included);
 //        otherwise v = v * coef, one fp32 multiply per element.
@@ -26,10 +20,9 @@
 // Two launches because the scale needs the global norm: one launch would need a grid-wide wait.
 //
 // Summation order (fixed: bitwise reproducible from run to run and under graph replay).
-//   thread:    a vector entry (src 16-byte aligned): for q = 0, 1 the float4 at element
-//              base + (q*256 + tid)*4, components 0..3 in order (a float4 that crosses the
-//              entry's end: its in-range components, in order);  a scalar entry: for q = 0..7 the
-//              element base + q*256 + tid.  base = (blk - first block of the entry) * 2048.
+//   thread:    its kSegElems = 8 elements in the order of seg_block.h (a vector entry: the float4
+//              q = 0, 1, components 0..3; a scalar entry: q = 0..7); an element past the entry's
+//              end counts as 0.
 //   wave:      xor butterfly, offsets 32, 16, 8, 4, 2, 1.
 //   workgroup: ((w0 + w1) + w2) + w3.
 //   grid:      thread t of the last workgroup adds partial[t], partial[t + 256], ... in
@@ -38,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "arrival.h"
 #include "ndp_kernels.h"
 #include "seg_block.h"
 
@@ -57,73 +51,33 @@ __device__ __forceinline__ double clip_block_sum(double v, double* red) {
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-__device__ __forceinline__ int clip_find_entry(const int64_t* __restrict__ prefix, int n_ent, int64_t blk) {
-  int lo = 0, hi = n_ent - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (prefix[mid] <= blk) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const SegEntry* __restrict__ ents,
                                                           const int64_t* __restrict__ prefix, int n_ent,
                                                           double* __restrict__ partial, unsigned* __restrict__ ctr,
                                                           ClipBlock* __restrict__ clip, float max_norm, float div) {
-  const int64_t blk = blockIdx.x;
-  const int lo = clip_find_entry(prefix, n_ent, blk);
-  const SegEntry E = ents[lo];
-  const float NDP_SEG_GLOBAL* const src = (const float NDP_SEG_GLOBAL*)E.src;
-  const int64_t base = (blk - prefix[lo]) * kSegBlockElems;
+  const SegPos p = seg_find(ents, prefix, n_ent, blockIdx.x);
+  const SegEntry& E = p.E;
+  const float NDP_SEG_GLOBAL* const src = seg_global(E.src);
+  float v[kSegElems] = {};  // every load in flight before the first fma
+  seg_walk(
+      E, p.base,
+      [&](int q, int64_t k) __attribute__((always_inline)) {
+        const seg_f32x4 t = seg_ld4(src + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[4 * q + j] = t[j];
+      },
+      [&](int i, int64_t k, bool) __attribute__((always_inline)) { v[i] = src[k]; });
   double acc = 0.0;
-  if (E.vec) {
-    constexpr int QN = kSegBlockElems / 1024;
-    seg_f32x4 v[QN];
 #pragma unroll
-    for (int q = 0; q < QN; ++q) {  // both loads in flight before the first fma
-      const int64_t k = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-      if (k + 3 < E.numel) {
-        v[q] = seg_ld4(src + k);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[q][j] = k + j < E.numel ? src[k + j] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < QN; ++q)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc = fma((double)v[q][j], (double)v[q][j], acc);
-  } else {
-    constexpr int QS = kSegBlockElems / 256;
-    float v[QS];
-#pragma unroll
-    for (int q = 0; q < QS; ++q) {
-      const int64_t k = base + q * 256 + threadIdx.x;
-      v[q] = k < E.numel ? src[k] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < QS; ++q) acc = fma((double)v[q], (double)v[q], acc);
-  }
+  for (int i = 0; i < kSegElems; ++i) acc = fma((double)v[i], (double)v[i], acc);
   __shared__ double red[4];
   __shared__ int last;
   const double bsum = clip_block_sum(acc, red);
   if (threadIdx.x == 0) {
     // sc1 (write-through) store, drained before the ticket: read back by the last workgroup
-    __hip_atomic_store(partial + blk, bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(partial + blockIdx.x, bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // first-level ticket of this group of kClipGroup workgroups; its last arriver re-arms it
-    // (every member has arrived) and draws the top-level ticket.  Causality runs through the
-    // atomics: a partial is in memory before its workgroup's ticket, that before the group's last.
-    const unsigned n = gridDim.x, g = blockIdx.x / kClipGroup;
-    const unsigned members = min((unsigned)kClipGroup, n - g * kClipGroup);
-    unsigned* const gctr = ctr + (size_t)(1 + g) * kClipCtrStride;
-    int l = 0;
-    if (__hip_atomic_fetch_add(gctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1) {
-      __hip_atomic_store(gctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned groups = (n + kClipGroup - 1) / kClipGroup;
-      l = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1;
-    }
-    last = l;
+    last = arrive_last_grouped(ctr);
   }
   __syncthreads();
   if (!last) return;
@@ -149,7 +103,7 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const SegEntry* __rest
     clip->coef = coef;
     clip->steps += 1u;
     if (coef != 1.0f) clip->clipped += 1u;
-    __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    arrive_rearm(ctr);
   }
 }
 
@@ -158,33 +112,19 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const SegEntry* __restr
                                                          const ClipBlock* __restrict__ clip) {
   const float coef = clip->coef;  // uniform address: one scalar load
   if (coef == 1.0f) return;
-  const int64_t blk = blockIdx.x;
-  const int lo = clip_find_entry(prefix, n_ent, blk);
-  const SegEntry E = ents[lo];
-  const float NDP_SEG_GLOBAL* const src = (const float NDP_SEG_GLOBAL*)E.src;
-  float NDP_SEG_GLOBAL* const dst = (float NDP_SEG_GLOBAL*)E.dst;
-  const int64_t base = (blk - prefix[lo]) * kSegBlockElems;
-  if (E.vec) {
-    constexpr int QN = kSegBlockElems / 1024;
-#pragma unroll
-    for (int q = 0; q < QN; ++q) {
-      const int64_t k = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-      if (k + 3 < E.numel) {
+  const SegPos p = seg_find(ents, prefix, n_ent, blockIdx.x);
+  const SegEntry& E = p.E;
+  const float NDP_SEG_GLOBAL* const src = seg_global(E.src);
+  float NDP_SEG_GLOBAL* const dst = seg_global(E.dst);
+  seg_walk(
+      E, p.base,
+      [&](int, int64_t k) __attribute__((always_inline)) {
         seg_f32x4 v = seg_ld4(src + k);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = __fmul_rn(v[j], coef);
         seg_st4(dst + k, v);
-      } else {
-        for (int j = 0; j < 4 && k + j < E.numel; ++j) dst[k + j] = __fmul_rn(src[k + j], coef);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < kSegBlockElems / 256; ++q) {
-      const int64_t k = base + q * 256 + threadIdx.x;
-      if (k < E.numel) dst[k] = __fmul_rn(src[k], coef);
-    }
-  }
+      },
+      [&](int, int64_t k, bool) __attribute__((always_inline)) { dst[k] = __fmul_rn(src[k], coef); });
 }
 
 void launch_grad_sqnorm(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,

@@ -8,9 +8,8 @@
 //        lse = max + log(sum) (fp32, butterfly order: the same value on every lane),
 //        loss_b = lse - x[t], and the row of the saved gradient dl[b, k] = softmax_k - [k == t]
 //        (unscaled).  Rows whose target is ignore_index contribute nothing (0 loss, 0 grad).
-//        Row losses go to rowloss[b]; the LAST workgroup to finish (agent-scope counter:
-//        plain stores -> release fence -> relaxed add; the last one: acquire fence, same
-//        idiom as orth.hip) adds them in row order and writes loss = sum / n_valid and
+//        Row losses go to rowloss[b] as sc1 stores; the LAST workgroup to finish (the one-level
+//        arrival ticket of arrival.h) adds them in row order and writes loss = sum / n_valid and
 //        inv = 1 / n_valid, then re-arms the counter (hipGraph-replay safe).
 //   bwd: dx = dl * (dloss * inv) — one float4 launch.
 //   ce_soft_fwd_kernel: the forward with label smoothing and a second, weighted target per row
@@ -19,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "arrival.h"
 #include "ndp_kernels.h"
 
 namespace ndp {
@@ -85,19 +85,9 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ x
       __hip_atomic_store(rowloss + b, !valid ? 0.f : (in_range ? lse - xr[t] : __builtin_nanf("")), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
   }
-  // last-arriving workgroup: fixed-order mean over the rows.  The row losses cross workgroups
-  // through sc1 stores (drained before the ticket) and agent-scope loads — no release / acquire
-  // fence: an agent-scope release writes the XCD's whole L2 back (11.2 -> 10.0 µs at batch 512)
-  __shared__ int last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler order only: the loads below are sc1
+  // last-arriving workgroup: fixed-order mean over the rows, which cross workgroups through sc1
+  // stores (drained by the ticket) and agent-scope loads
+  if (!arrive_last(ctr, gridDim.x)) return;
   __shared__ float red[2][4];
   float a = 0.f, n = 0.f;
   for (int r = threadIdx.x; r < B; r += 256) {
@@ -117,7 +107,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ x
     loss[0] = tot / cnt;  // 0 / 0 = NaN when every row is ignored, like PyTorch
     if (acc != nullptr) acc[0] += tot / cnt;  // running loss sum (logging): no separate add launch
     inv[0] = 1.f / cnt;
-    __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    arrive_rearm(ctr);
   }
 }
 
@@ -204,18 +194,8 @@ __global__ __launch_bounds__(256) void ce_soft_fwd_kernel(const float* __restric
       __hip_atomic_store(rowloss + b, rl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  // last-arriving workgroup: ce_fwd_kernel's ticket and fixed-order mean (sc1 stores drained
-  // before the ticket, agent-scope loads after it, no release / acquire fence)
-  __shared__ int last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler order only: the loads below are sc1
+  // last-arriving workgroup: ce_fwd_kernel's ticket and fixed-order mean
+  if (!arrive_last(ctr, gridDim.x)) return;
   __shared__ float red[2][4];
   float a = 0.f, n = 0.f;
   for (int r = threadIdx.x; r < B; r += 256) {
@@ -235,7 +215,7 @@ __global__ __launch_bounds__(256) void ce_soft_fwd_kernel(const float* __restric
     loss[0] = tot / cnt;  // 0 / 0 = NaN when every row is ignored, like PyTorch
     if (acc != nullptr) acc[0] += tot / cnt;
     inv[0] = 1.f / cnt;
-    __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    arrive_rearm(ctr);
   }
 }
 
@@ -365,18 +345,8 @@ __global__ __launch_bounds__(256) void cls_metrics_kernel(const float* __restric
       __hip_atomic_store(rowrank + b, rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  // last-arriving workgroup: the ce_fwd ticket (sc1 stores drained before it, no release /
-  // acquire fence), then a fixed-order sum over the rows, the loss in fp64
-  __shared__ int last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler order only: the loads below are sc1
+  // last-arriving workgroup: the ce_fwd ticket, then a fixed-order sum over the rows, the loss in fp64
+  if (!arrive_last(ctr, gridDim.x)) return;
   __shared__ double redl[4];
   __shared__ int redc[3][4];
   double a = 0.0;
@@ -407,7 +377,7 @@ __global__ __launch_bounds__(256) void cls_metrics_kernel(const float* __restric
     state[1] += (double)(redc[0][0] + redc[0][1] + redc[0][2] + redc[0][3]);
     state[2] += (double)(redc[1][0] + redc[1][1] + redc[1][2] + redc[1][3]);
     state[3] += (double)(redc[2][0] + redc[2][1] + redc[2][2] + redc[2][3]);
-    __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    arrive_rearm(ctr);
   }
 }
 

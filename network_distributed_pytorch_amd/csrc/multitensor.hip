@@ -20,15 +20,11 @@
 
 namespace ndp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
+// the flat-arena kernels' float4 (kernel arguments: already global accesses); the table kernels'
+// set is seg_block.h's
+typedef seg_f32x4 f32x4;
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-// the entry table's pointers, re-typed as global (address space 1): read through the table they
-// would compile to FLAT accesses, which also wait on the scalar-cache counter
-#define NDP_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ f32x4 ld4(const float NDP_GLOBAL* p) { return *reinterpret_cast<const f32x4 NDP_GLOBAL*>(p); }
-__device__ __forceinline__ void st4(float NDP_GLOBAL* p, f32x4 v) { *reinterpret_cast<f32x4 NDP_GLOBAL*>(p) = v; }
 
 __global__ __launch_bounds__(256) void seg_reduce_kernel(const SegEntry* __restrict__ ents,
                                                          const int64_t* __restrict__ prefix,

@@ -86,7 +86,7 @@ constexpr int kUWideRows = 16;
 constexpr int kUWideCols = 256;
 constexpr int kUWideMaxRank = 16;
 constexpr int kMaxRank = 64;
-constexpr int kSegBlockElems = 2048;  // elements per workgroup in seg_reduce
+constexpr int kSegBlockElems = 2048;  // elements per workgroup of a SegEntry table (seg_block.h)
 
 // ---- launchers (powersgd.hip) --------------------------------------------------
 // p_prev (rank <= kUWideMaxRank only): lazy error feedback, e = M_prev - P_prev Qs^T formed here
@@ -326,14 +326,9 @@ void launch_cls_metrics(const float* x, const int64_t* tgt, int B, int K, int64_
 
 // ---- global-norm gradient clipping (gradclip.hip) -----------------------------------------
 // A SegEntry table over the gradients (src read, dst written, chunks = 1); partial [n_blocks]
-// fp64 scratch, ctr: grad_clip_ctr_words(n_blocks) zeroed uint32 (the two-level arrival tickets,
-// re-armed by the kernel), clip: the 16-byte ClipBlock.
+// fp64 scratch, ctr: arrive_ctr_words(n_blocks) zeroed uint32 (the two-level arrival tickets of
+// arrival.h, re-armed by the kernel), clip: the 16-byte ClipBlock.
 namespace ndp {
-constexpr int kClipGroup = 64;      // workgroups that share one first-level ticket
-constexpr int kClipCtrStride = 64;  // uint32 between two tickets: 256 B apart, never one cache line
-inline int64_t grad_clip_ctr_words(int64_t n_blocks) {
-  return (int64_t)kClipCtrStride * (1 + (n_blocks + kClipGroup - 1) / kClipGroup);
-}
 struct ClipBlock {
   float norm;        // (float)(sqrt(sum v^2) / div) of the last run
   float coef;        // q = max_norm / (norm + 1e-6f);  q < 1 or NaN ? q : 1
@@ -348,8 +343,8 @@ void launch_grad_scale(const SegEntry* entries, const int64_t* block_prefix, int
 
 // ---- exponential moving average of the weights (ema.hip) ----------------------------------
 // A SegEntry table with src = live tensor, dst = shadow (chunks = 1; vec: both 16-byte aligned);
-// ctr: grad_clip_ctr_words(n_blocks) zeroed uint32 (the two-level tickets, re-armed by the
-// kernel), block: the 16-byte EmaBlock.
+// ctr: arrive_ctr_words(n_blocks) zeroed uint32 (the two-level tickets of arrival.h, re-armed by
+// the kernel), block: the 16-byte EmaBlock.
 struct EmaBlock {
   float decay;       // d of the last run
   float weight;      // w = 1 - d of the last run

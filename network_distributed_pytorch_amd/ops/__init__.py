@@ -26,6 +26,8 @@ __all__ = [
     "capturing",
     "upload",
     "SegPlan",
+    "read_block4",
+    "write_block4",
     "upload_epoch",
     "classification_metrics",
     "ClassificationMetrics",
@@ -252,12 +254,24 @@ class SegPlan:
             return None
         return self._ent, self._prefix, self._n_ent, self._n_blocks
 
+    @property
+    def n_blocks(self) -> int:
+        """Blocks of ``SEG_BLOCK_ELEMS`` elements (the grid of a table kernel); 0: nothing to run."""
+        return self._n_blocks if self.table() is not None else 0
+
+    def launch(self, fn, *extra) -> bool:
+        """``fn(entries, prefix, n_entries, n_blocks, *extra)`` over the device table; False (and
+        no call) when the table is empty."""
+        if not self.n_blocks:
+            return False
+        fn(self._ent, self._prefix, self._n_ent, self._n_blocks, *extra)
+        return True
+
     def run(self) -> None:
         if not self.specs:
             return
         if self.device.type == "cuda":
-            if self._n_ent:
-                ext().seg_reduce(self._ent, self._prefix, self._n_ent, self._n_blocks)
+            self.launch(ext().seg_reduce)
             return
         for src, dst, chunks, stride, div in self.specs:
             n = dst.numel()
@@ -267,6 +281,24 @@ class SegPlan:
             if div != 1.0:
                 acc /= div
             dst.copy_(acc.view_as(dst))
+
+
+def read_block4(block: torch.Tensor):
+    """A 16-byte device block (4 int32 words: ``ClipBlock``, ``EmaBlock``) as
+    ``(float, float, uint32, uint32)``: a host sync on a device."""
+    w = block.cpu()
+    f = w[:2].view(torch.float32)
+    return float(f[0]), float(f[1]), int(w[2]) & 0xffffffff, int(w[3]) & 0xffffffff
+
+
+def write_block4(block: torch.Tensor, f0: float, f1: float, u0: int = 0, u1: int = 0) -> None:
+    """The inverse of :func:`read_block4`."""
+    host = torch.zeros(4, dtype=torch.int32)
+    host[:2].view(torch.float32).copy_(torch.tensor([f0, f1], dtype=torch.float32))
+    for i, u in ((2, u0), (3, u1)):
+        u &= 0xffffffff
+        host[i] = u - (1 << 32) if u >= (1 << 31) else u
+    block.copy_(host)
 
 
 def delay_ns(ns: int) -> None:

@@ -25,6 +25,7 @@ from typing import Any, Dict, List, Sequence
 import numpy as np
 import torch
 
+from . import SegPlan, read_block4, write_block4
 from ._ext import ext
 
 __all__ = ["WeightEma", "ema_decay_at"]
@@ -64,8 +65,6 @@ class WeightEma:
     """
 
     def __init__(self, tensors: Sequence[torch.Tensor], decay: float, warmup: bool = True):
-        from . import SegPlan
-
         self.decay = _check_decay(decay)
         self.warmup = bool(warmup)
         self.tensors: List[torch.Tensor] = [t.detach() for t in tensors]
@@ -110,7 +109,6 @@ class WeightEma:
                 s.copy_(t)
         self._state = {"decay": 0.0, "weight": 0.0, "updates": 0}  # the twin's block
         if cuda:
-            X = ext()
             specs = []
             for r, (i0, n, _, _) in enumerate(runs):
                 if n == 0:
@@ -119,20 +117,15 @@ class WeightEma:
                 live = first.reshape(-1) if n == first.numel() else torch.as_strided(first, (n,), (1,))
                 specs.append((live, self.arena[offs[r]: offs[r] + n], 1, 0, 1.0))
             self.plan = SegPlan(specs, self.device)
-            tab = self.plan.table()
-            blocks = tab[3] if tab is not None else 0
-            self.ctr = torch.zeros(X.grad_clip_ctr_words(blocks), dtype=torch.int32, device=self.device)
+            self.ctr = torch.zeros(ext().arrive_ctr_words(self.plan.n_blocks), dtype=torch.int32, device=self.device)
             self.block = torch.zeros(4, dtype=torch.int32, device=self.device)
 
     # ---- the rule ---------------------------------------------------------------------------
     def update(self) -> None:
         """One run of the rule: one launch on a device (current stream), the twin on CPU."""
         if self.device.type == "cuda":
-            tab = self.plan.table()
-            if tab is None or tab[3] == 0:
+            if not self.plan.launch(ext().ema_update, self.ctr, self.block, self.decay, self.warmup):
                 raise RuntimeError("WeightEma.update: empty table")
-            ent, prefix, n_ent, n_blocks = tab
-            ext().ema_update(ent, prefix, n_ent, n_blocks, self.ctr, self.block, self.decay, self.warmup)
             return
         st = self._state
         d, w = ema_decay_at(self.decay, st["updates"], self.warmup)
@@ -146,11 +139,7 @@ class WeightEma:
     def swap(self) -> None:
         """Exchange live tensors and shadows bitwise (twice: the identity)."""
         if self.device.type == "cuda":
-            tab = self.plan.table()
-            if tab is None or tab[3] == 0:
-                return
-            ent, prefix, n_ent, n_blocks = tab
-            ext().ema_swap(ent, prefix, n_ent, n_blocks)
+            self.plan.launch(ext().ema_swap)
             return
         with torch.no_grad():
             for s, x in zip(self.shadow, self.tensors):
@@ -163,20 +152,13 @@ class WeightEma:
     def read(self) -> Dict[str, Any]:
         """``{"decay", "weight", "updates"}`` of the block: a host sync on a device."""
         if self.device.type == "cuda":
-            w = self.block.cpu()
-            f = w[:2].view(torch.float32)
-            return {"decay": float(f[0]), "weight": float(f[1]), "updates": int(w[2]) & 0xffffffff}
+            return dict(zip(("decay", "weight", "updates"), read_block4(self.block)))
         return dict(self._state)
 
     def _write_block(self, st: Dict[str, Any]) -> None:
         self._state = {"decay": float(st["decay"]), "weight": float(st["weight"]), "updates": int(st["updates"])}
         if self.device.type == "cuda":
-            host = torch.zeros(4, dtype=torch.int32)
-            host[:2].view(torch.float32).copy_(torch.tensor([self._state["decay"], self._state["weight"]],
-                                                            dtype=torch.float32))
-            u = self._state["updates"] & 0xffffffff
-            host[2] = u - (1 << 32) if u >= (1 << 31) else u
-            self.block.copy_(host)
+            write_block4(self.block, self._state["decay"], self._state["weight"], self._state["updates"])
 
     def reset(self) -> None:
         """The state after construction: the shadow a copy of the live tensors, ``updates = 0``."""

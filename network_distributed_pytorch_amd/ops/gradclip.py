@@ -28,11 +28,10 @@ from typing import Any, Dict, List, Sequence
 import numpy as np
 import torch
 
+from . import SegPlan, read_block4
 from ._ext import ext
 
 __all__ = ["GradClip", "clip_grad_norm_"]
-
-_BLOCK_ELEMS = 2048  # kSegBlockElems: elements per workgroup of the table
 
 
 def _check_args(max_norm: float, div: float):
@@ -70,8 +69,6 @@ class GradClip:
     """
 
     def __init__(self, device, capacity: int = 0, blocks: int = 0):
-        from . import SegPlan
-
         self.device = torch.device(device)
         self.tensors: List[torch.Tensor] = []
         self._retired: list = []  # outgrown partials: a captured graph may still hold the address
@@ -82,7 +79,7 @@ class GradClip:
             self.plan = SegPlan((), self.device, capacity=max(int(capacity), 1))
             self.partial = torch.empty(max(int(blocks), 1), dtype=torch.float64, device=self.device)
             # the two-level arrival tickets of the table's workgroups: zero, re-armed by every launch
-            self.ctr = torch.zeros(ext().grad_clip_ctr_words(self.partial.numel()), dtype=torch.int32,
+            self.ctr = torch.zeros(ext().arrive_ctr_words(self.partial.numel()), dtype=torch.int32,
                                    device=self.device)
             self.clip = torch.zeros(4, dtype=torch.int32, device=self.device)
             self.clip[1:2].view(torch.float32).fill_(1.0)
@@ -100,26 +97,21 @@ class GradClip:
                                      f"(got {t.dtype}, contiguous={t.is_contiguous()})")
             flat = [t.detach().reshape(-1) for t in tensors]
             self.plan.set([(f, f, 1, 0, 1.0) for f in flat])
-            tab = self.plan.table()
-            blocks = tab[3] if tab is not None else 0
+            blocks = self.plan.n_blocks
             if blocks > self.partial.numel():
                 assert not torch.cuda.is_current_stream_capturing(), "GradClip must be sized before graph capture"
                 self._retired += [self.partial, self.ctr]
                 self.partial = torch.empty(blocks, dtype=torch.float64, device=self.device)
-                self.ctr = torch.zeros(ext().grad_clip_ctr_words(blocks), dtype=torch.int32, device=self.device)
+                self.ctr = torch.zeros(ext().arrive_ctr_words(blocks), dtype=torch.int32, device=self.device)
         self.tensors = tensors
 
     def run(self, max_norm: float, div: float = 1.0) -> None:
         max_norm, div = _check_args(max_norm, div)
         if self.device.type == "cuda":
-            tab = self.plan.table()
-            self._empty = tab is None or tab[3] == 0
-            if self._empty:
-                return
-            ent, prefix, n_ent, n_blocks = tab
             X = ext()
-            X.grad_sqnorm(ent, prefix, n_ent, n_blocks, self.partial, self.ctr, self.clip, max_norm, div)
-            X.grad_scale(ent, prefix, n_ent, n_blocks, self.clip)
+            self._empty = not self.plan.launch(X.grad_sqnorm, self.partial, self.ctr, self.clip, max_norm, div)
+            if not self._empty:
+                self.plan.launch(X.grad_scale, self.clip)
             return
         self._empty = not any(t.numel() for t in self.tensors)
         if self._empty:
@@ -151,10 +143,7 @@ class GradClip:
     def read(self) -> Dict[str, Any]:
         """``{"norm", "coef", "clipped", "steps"}`` of the block: a host sync on a device."""
         if self.device.type == "cuda":
-            w = self.clip.cpu()
-            f = w[:2].view(torch.float32)
-            out = {"norm": float(f[0]), "coef": float(f[1]), "clipped": int(w[2]) & 0xffffffff,
-                   "steps": int(w[3]) & 0xffffffff}
+            out = dict(zip(("norm", "coef", "clipped", "steps"), read_block4(self.clip)))
         else:
             out = dict(self._state)
         if self._empty:
@@ -166,7 +155,10 @@ def clip_grad_norm_(tensors: Sequence[torch.Tensor], max_norm: float, div: float
     """One-shot :class:`GradClip` over ``tensors`` (scaled in place); returns the fp32 norm."""
     tensors = [tensors] if isinstance(tensors, torch.Tensor) else list(tensors)
     device = tensors[0].device if tensors else torch.device("cpu")
-    blocks = sum((t.numel() + _BLOCK_ELEMS - 1) // _BLOCK_ELEMS for t in tensors)
+    blocks = 0
+    if device.type == "cuda":  # size the partials once; the twin that CPU tensors run has none
+        per = ext().SEG_BLOCK_ELEMS
+        blocks = sum((t.numel() + per - 1) // per for t in tensors)
     clip = GradClip(device, capacity=len(tensors), blocks=blocks)
     clip.bind(tensors)
     clip.run(max_norm, div)

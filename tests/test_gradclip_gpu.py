@@ -17,6 +17,8 @@ from network_distributed_pytorch_amd.parallel.ddp import BucketedDataParallel
 from network_distributed_pytorch_amd.parallel.powersgd import PowerSGDOptimizer
 from network_distributed_pytorch_amd.utils.graph import StepRunner
 
+from .ema_cases import BIG
+
 pytestmark = pytest.mark.gpu
 
 INF = float("inf")
@@ -102,6 +104,29 @@ def test_norm_and_scale_kernels(device, name, div):
     want = torch.where(guard, before, before * st2["coef"])  # the product formed in torch fp32
     assert torch.equal(_bits(buf), _bits(want))
     assert torch.equal(buf[guard], torch.full_like(buf[guard], GUARD))
+
+
+@pytest.mark.parametrize("n", [64 * 2048, 64 * 2048 + 1, BIG])
+def test_ticket_group_boundaries(device, n):
+    """One-entry tables of 64, 65 and 133 blocks (ticket groups of 64; 64 + 1; 64 + 64 + 5), three
+    runs in a row on one GradClip: a first- or top-level counter that was not re-armed loses the
+    second run's last arriver (stale block, steps short) or leaves a nonzero word behind."""
+    v = torch.randn(n, generator=torch.Generator().manual_seed(n)).to(device)
+    ref = _ref_norm([v], 1.0)
+    clip = GradClip(device, capacity=1)
+    clip.bind([v])
+    assert clip.plan.n_blocks == (n + 2047) // 2048
+    norms = []
+    for run in range(3):
+        clip.run(INF)
+        norms.append(clip.clip[0:1].clone())
+        st = clip.read()
+        print(f"n={n} run {run}: norm {st['norm']!r} ref {ref!r} ulp {_ulp(ref)!r}")
+        assert abs(st["norm"] - ref) <= _ulp(ref)
+        assert st["steps"] == run + 1 and st["coef"] == 1.0 and st["clipped"] == 0
+    assert torch.equal(norms[0], norms[1]) and torch.equal(norms[0], norms[2])  # int32 words: bitwise
+    assert clip.read()["steps"] == 3
+    assert not clip.ctr.any().item(), "a ticket word was left nonzero"
 
 
 def test_one_shot_front_end(device):

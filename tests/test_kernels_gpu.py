@@ -6,6 +6,7 @@ tall / wide matrices, 1..4 MFMA column groups (R up to 40), 4-D conv weights, em
 high-rank / rank-1 groups, split-K slabs.  Determinism (bitwise repeatability) is checked
 for every stage, because replica consistency across ranks depends on it.
 """
+import numpy as np
 import pytest
 import torch
 
@@ -14,6 +15,7 @@ from network_distributed_pytorch_amd.parallel.powersgd import (PowerSGDOptimizer
                                                                 orthogonalize)
 from network_distributed_pytorch_amd.parallel.tensor_buffer import TensorBuffer
 
+from . import seg_cases as S
 from .oracle import mgs, powersgd_round, reference_bits
 
 pytestmark = pytest.mark.gpu
@@ -176,6 +178,24 @@ def test_seg_reduce_chunks(device):
     dst2 = torch.empty(4099, device=device)
     ops.SegPlan([(src[1:], dst2, 1, 0, 1.0)], device).run()
     assert torch.equal(dst2, src[1:4100])
+
+
+def test_seg_reduce_boundaries(device):
+    """Every entry of tests/seg_cases.py in one launch: bitwise the numpy fp32 loop in chunk order,
+    and the sentinel bands around every dst untouched."""
+    _native_loaded()
+    cases, src, dst = S.buffers()
+    want = S.reference(cases, src, dst)
+    s, d = torch.from_numpy(src).to(device), torch.from_numpy(dst).to(device)
+    plan = ops.SegPlan(S.specs(cases, s, d), device)
+    assert plan.n_blocks == sum((c["n"] + 2047) // 2048 for c in cases)
+    plan.run()
+    got = d.cpu().numpy()
+    bad = np.flatnonzero(got.view(np.int32) != want.view(np.int32))
+    for c in cases:  # name the first failing entry
+        lo, hi = c["dst"] - S.BAND, c["dst"] + c["n"] + S.BAND
+        assert not ((bad >= lo) & (bad < hi)).any(), f"{c}: first differing element {bad[bad >= lo][0] - c['dst']}"
+    assert bad.size == 0
 
 
 @pytest.mark.parametrize("n", [1, 4, 1023, 1 << 20])
