@@ -1419,6 +1419,48 @@ void ema_swap(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, in
   check_launch("launch_ema_swap");
 }
 
+// the AdamW kernel's table (plan.cpp build_adamw_table): rows of (g_addr, x_addr, numel, moment
+// offset, decays) against moment arenas of arena_numel floats at m_addr / v_addr
+py::tuple make_adamw_table(const std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, bool>>& rows,
+                           int64_t m_addr, int64_t v_addr, int64_t arena_numel) {
+  std::vector<ndp::AdamSpec> s;
+  s.reserve(rows.size());
+  for (const auto& t : rows)
+    s.push_back(ndp::AdamSpec{(uintptr_t)std::get<0>(t), (uintptr_t)std::get<1>(t), std::get<2>(t), std::get<3>(t),
+                              std::get<4>(t)});
+  ndp::SegTable tab;
+  try {
+    tab = ndp::build_adamw_table(s, (uintptr_t)m_addr, (uintptr_t)v_addr, arena_numel);
+  } catch (const std::invalid_argument& e) {
+    TORCH_CHECK(false, e.what());
+  }
+  auto prefix = torch::empty({(int64_t)tab.prefix.size()}, torch::dtype(torch::kInt64));
+  if (!tab.prefix.empty())
+    std::memcpy(prefix.data_ptr(), tab.prefix.data(), tab.prefix.size() * sizeof(int64_t));
+  return py::make_tuple(to_bytes(tab.entries), prefix, (int64_t)tab.entries.size(), tab.n_blocks);
+}
+
+// AdamW (adamw.hip) over a make_adamw_table table built against exactly these m / v arenas: ctr:
+// arrive_ctr_words(n_blocks) zeroed int32 (re-armed), block: the AdamBlock {b1pow, b2pow, steps,
+// pad} as 4 int32 words, hyper: the device block [lr, weight_decay, 0, 0].  No allocation, no
+// sync: capture-safe.
+void adamw_step(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
+                torch::Tensor ctr, torch::Tensor block, torch::Tensor hyper, torch::Tensor m, torch::Tensor v,
+                double beta1, double beta2, double eps, double div) {
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "adamw_step");
+  check_f32(m, "m"); check_f32(v, "v");
+  TORCH_CHECK(m.numel() == v.numel(), "adamw_step: the moment arenas differ in size");
+  TORCH_CHECK((float)beta1 >= 0.0f && (float)beta1 < 1.0f && (float)beta2 >= 0.0f && (float)beta2 < 1.0f,
+              "adamw_step: betas must be in [0, 1)");
+  TORCH_CHECK((float)eps > 0.0f, "adamw_step: eps must be > 0 as fp32");
+  TORCH_CHECK((float)div >= 1.0f, "adamw_step: div must be >= 1");
+  const float* hp = hyper_ptr(c10::optional<torch::Tensor>(hyper));
+  ndp::launch_adamw_step(t.entries, t.prefix, t.n_entries, t.n_blocks, ticket_ptr(ctr, n_blocks, "adamw_step"),
+                         block4_ptr<ndp::AdamBlock>(block, "adamw_step"), hp, m.data_ptr<float>(),
+                         v.data_ptr<float>(), (float)beta1, (float)beta2, (float)eps, (float)div, cur_stream());
+  check_launch("launch_adamw_step");
+}
+
 // batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
 // [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
 // shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
@@ -1878,6 +1920,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ema_update", &ema_update, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
         py::arg("ctr"), py::arg("block"), py::arg("decay"), py::arg("warmup"));
   m.def("ema_swap", &ema_swap, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"));
+  m.def("make_adamw_table", &make_adamw_table, py::arg("rows"), py::arg("m_addr"), py::arg("v_addr"),
+        py::arg("arena_numel"));
+  m.def("adamw_step", &adamw_step, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
+        py::arg("ctr"), py::arg("block"), py::arg("hyper"), py::arg("m"), py::arg("v"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("div"));
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));

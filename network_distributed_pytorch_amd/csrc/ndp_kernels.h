@@ -357,6 +357,22 @@ void launch_ema_update(const SegEntry* entries, const int64_t* block_prefix, int
 // x <-> s over the table, bitwise
 void launch_ema_swap(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
                      hipStream_t s);
+
+// ---- AdamW (adamw.hip) ----------------------------------------------------------------------
+// A SegEntry table from build_adamw_table (plan.h) with src = gradient, dst = parameter, stride =
+// the entry's element offset into the moment arenas m / v, pad bit 0 = no decay, vec: all four
+// streams 16-byte aligned; ctr: arrive_ctr_words(n_blocks) zeroed uint32 (re-armed by the kernel),
+// block: the 16-byte AdamBlock, hyper: the device block [lr, weight_decay, 0, 0] (never null).
+struct AdamBlock {
+  float b1pow;     // beta1^steps as a running fp32 product
+  float b2pow;     // beta2^steps
+  uint32_t steps;  // launches so far
+  uint32_t pad;
+};
+constexpr int kAdamNoDecay = 1;  // SegEntry.pad bit: the entry takes no weight decay
+void launch_adamw_step(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
+                       unsigned* ctr, AdamBlock* block, const float* hyper, float* m, float* v, float beta1,
+                       float beta2, float eps, float div, hipStream_t s);
 }  // namespace ndp
 
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------

@@ -200,4 +200,32 @@ SegTable build_seg_table(const std::vector<SegSpec>& specs) {
   return t;
 }
 
+SegTable build_adamw_table(const std::vector<AdamSpec>& specs, uintptr_t m_base, uintptr_t v_base,
+                           int64_t arena_numel) {
+  SegTable t;
+  int64_t blocks = 0;
+  for (const AdamSpec& s : specs) {
+    if (s.numel <= 0) continue;
+    if (s.off < 0 || s.off > arena_numel || s.numel > arena_numel - s.off)
+      throw std::invalid_argument("adamw table: an entry's moments lie outside the moment arenas");
+    if (((s.g | s.x | m_base | v_base) & 3) != 0)
+      throw std::invalid_argument("adamw table: a pointer is not 4-byte aligned");
+    SegEntry e{};
+    e.src = reinterpret_cast<const float*>(s.g);
+    e.dst = reinterpret_cast<float*>(s.x);
+    e.numel = s.numel;
+    e.stride = s.off;
+    e.chunks = 1;
+    e.div = 1.0f;
+    const uintptr_t mo = m_base + 4 * (uintptr_t)s.off, vo = v_base + 4 * (uintptr_t)s.off;
+    e.vec = (((s.g | s.x | mo | vo) & 15) == 0) ? 1 : 0;
+    e.pad = s.decay ? 0 : kAdamNoDecay;
+    t.entries.push_back(e);
+    t.prefix.push_back(blocks);
+    blocks += cdiv(s.numel, kSegBlockElems);
+  }
+  t.n_blocks = blocks;
+  return t;
+}
+
 }  // namespace ndp

@@ -63,4 +63,16 @@ struct SegTable {
 
 SegTable build_seg_table(const std::vector<SegSpec>& specs);
 
+// The AdamW kernel's table (adamw.hip): src = gradient, dst = parameter, stride = `off`, the
+// entry's element offset into the two moment arenas at m_base / v_base (arena_numel floats each),
+// pad bit 0 (kAdamNoDecay) = no weight decay, vec = gradient, parameter and both moments 16-byte
+// aligned.  Throws std::invalid_argument for a moment range outside the arenas.
+struct AdamSpec {
+  uintptr_t g, x;
+  int64_t numel, off;
+  bool decay;
+};
+SegTable build_adamw_table(const std::vector<AdamSpec>& specs, uintptr_t m_base, uintptr_t v_base,
+                           int64_t arena_numel);
+
 }  // namespace ndp

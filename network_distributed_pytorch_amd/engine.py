@@ -79,6 +79,8 @@ def default_config(**over) -> Dict[str, Any]:
         label_smoothing=0.0, mix="none", mix_prob=1.0,
         # exponential moving average of the weights (ops/ema.py): 0 = off
         ema_decay=0.0, ema_warmup=True,
+        # the optimiser behind the gradient sync: "sgd" or "adamw" (ops/adamw.py; weight_decay is then decoupled)
+        optimizer="sgd", adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, decay_1d=True,
     )
     cfg.update(over)
     return cfg
@@ -403,6 +405,10 @@ def run_task(config) -> Dict[str, Any]:
     max_grad_norm = float(config.get("max_grad_norm") or 0.0)
     if max_grad_norm > 0:  # off: build_grad_sync is called exactly as before
         extra["max_grad_norm"] = max_grad_norm
+    optimizer = config.get("optimizer") or "sgd"
+    if optimizer != "sgd":  # sgd: build_grad_sync is called exactly as before
+        extra.update(optimizer=optimizer, betas=(float(config["adam_beta1"]), float(config["adam_beta2"])),
+                     eps=float(config["adam_eps"]), decay_1d=bool(config.get("decay_1d", True)))
     sync = build_grad_sync(config["grad_sync"], model, comm, lr=config["learning_rate"],
                            momentum=config["momentum"], rank=config["reducer_rank"],
                            bucket_mb=config.get("bucket_mb"), seed=config["seed"], **extra)
@@ -497,6 +503,12 @@ def run_task(config) -> Dict[str, Any]:
         return sync.clip_stats()
     if clip_on:
         clipped_base = clip_read()["clipped"]
+
+    def adam_record():
+        # host read of the AdamW block; after a replay its last write may sit on the side stream
+        if runner is not None:
+            runner.join()
+        return {"optimizer": optimizer, "adam_steps": sync.adam_stats()["steps"]}
     t_start = time.perf_counter()
     samples = 0
     last_log = (time.perf_counter(), comm.stats.payload_bytes, comm.stats.wire_bytes, step)
@@ -596,6 +608,8 @@ def run_task(config) -> Dict[str, Any]:
             epoch_rec.update(mix=mix, mix_prob=float(config["mix_prob"]))
         if ema is not None:
             epoch_rec.update(ema_record())
+        if optimizer != "sgd":
+            epoch_rec.update(adam_record())
         if config.get("verbose", True):
             print_epoch(rank, epoch, mean)
             print(">>>>> Rank ", rank, ", epoch ", epoch, " Finished...\n", flush=True)
@@ -661,6 +675,8 @@ def run_task(config) -> Dict[str, Any]:
         summary["eval_s"] = eval_s
     if ema is not None:
         summary.update(ema_record())
+    if optimizer != "sgd":
+        summary.update(adam_record())
     logger.log(kind="summary", **{k: v for k, v in summary.items()})
     logger.close()
     if ema is not None:

@@ -41,6 +41,8 @@ __all__ = [
     "clip_grad_norm_",
     "WeightEma",
     "ema_decay_at",
+    "FusedAdamW",
+    "adamw_scalars",
 ]
 
 
@@ -321,3 +323,4 @@ from .image_batch import (crop_flip_draw, hash4, image_batch, image_mix_batch, i
                           mix_draw)  # (csrc/image_batch.hip)
 from .gradclip import GradClip, clip_grad_norm_  # noqa: E402  (global-norm clipping, csrc/gradclip.hip)
 from .ema import WeightEma, ema_decay_at  # noqa: E402  (weight EMA, csrc/ema.hip)
+from .adamw import FusedAdamW, adamw_scalars  # noqa: E402  (fused AdamW, csrc/adamw.hip)

@@ -37,6 +37,13 @@ backward-overlapped MI355X arm.
   ``coef * sum g`` and the SGD forms ``(coef * sum g) / N``: torch's clip-after-average, exact
   when N is a power of two and within one ulp per element otherwise.  Every rank sees the same
   all-reduced arena, so the norm and the replicas stay identical across ranks.
+  ``optimizer="adamw"`` replaces the step's fused SGD launch by the fused AdamW launch
+  (ops/adamw.py, csrc/adamw.hip) over the same arenas with ``div = world_size``: ``buf`` is the
+  first moment, one more arena ``v`` the second, the table has one entry per run of parameters
+  with the same decay flag (``decay_1d=False`` exempts tensors of at most one dimension), and the
+  bias corrections live in the kernel's device block, so the captured step serves every step.
+  The kernel always reads ``lr`` / ``weight_decay`` from the hyper block; ``momentum`` is ignored.
+  Bucketing, overlap, stream mode and the order clip -> update -> EMA are the SGD arm's.
 """
 from __future__ import annotations
 
@@ -46,6 +53,7 @@ import numpy as np
 import torch
 
 from ..ops import SegPlan, capturing, gradarena, gradfinish, sgd_momentum_
+from ..ops.adamw import AdamWCore, check_adam_args
 from ..ops.gradclip import GradClip
 from ..ops.hyper import HyperBlock
 from .comm import Communicator, all_reduce, world_size
@@ -75,8 +83,15 @@ class BucketedDataParallel:
     def __init__(self, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                  momentum: float = 0.9, bucket_mb: Optional[float] = None, broadcast_params: bool = True,
                  overlap: Optional[bool] = None, weight_decay: float = 0.0,
-                 max_grad_norm: float = 0.0):
+                 max_grad_norm: float = 0.0, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                 decay_1d: bool = True):
         assert weight_decay >= 0, "weight_decay >= 0"
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"dense arm: unknown optimizer {optimizer!r} (sgd, adamw)")
+        self.optimizer = optimizer
+        self.decay_1d = bool(decay_1d)
+        if optimizer == "adamw":
+            self.beta1, self.beta2, self.eps = check_adam_args(betas, eps)
         assert max_grad_norm >= 0, "max_grad_norm >= 0 (0: off, inf: measure only)"
         self.max_grad_norm = float(max_grad_norm)
         bucket_mb = DEFAULT_BUCKET_MB if bucket_mb is None else float(bucket_mb)
@@ -158,6 +173,32 @@ class BucketedDataParallel:
             self.clip = GradClip(self.device, capacity=1, blocks=(self.numel + 2047) // 2048)
             self.clip.bind([self.g])
         self.ema = None  # ops.WeightEma updated behind the SGD launch (attach_ema)
+        # AdamW: second-moment arena, and the table over (g, x, buf, v): one entry per run of
+        # parameters (arena order, padding included: zero g / m / v keep it zero) that decay alike
+        self.adam: Optional[AdamWCore] = None
+        if optimizer == "adamw":
+            self.v = torch.zeros(o, **f32)
+            runs: List[list] = []  # [start, end, decays]
+            for p in order:
+                s = offs[id(p)]
+                e = s + (p.numel() + 15) // 16 * 16
+                dec = self.decay_1d or p.dim() > 1
+                if runs and runs[-1][2] == dec and runs[-1][1] == s:
+                    runs[-1][1] = e
+                elif e > s:
+                    runs.append([s, e, dec])
+            self.adam_runs = [tuple(r) for r in runs]
+            self.adam = AdamWCore(self.device, self.buf, self.v, len(runs),
+                                  sum((e - s + 2047) // 2048 for s, e, _ in runs))
+            self._bind_adam()
+            self._hyper_on = self.hyper is not None  # the kernel has no by-value lr
+
+    def _bind_adam(self):
+        self.adam.bind([(self.g[s:e], self.x[s:e], s, dec) for s, e, dec in self.adam_runs])
+
+    def adam_stats(self) -> Optional[Dict[str, Any]]:
+        """``{"b1pow", "b2pow", "steps"}`` of the AdamW block (a host sync), or None with SGD."""
+        return self.adam.read() if self.adam is not None else None
 
     def attach_ema(self, ema):
         """Keep ``ema`` (ops/ema.py) of the weights: one launch behind every step's SGD launch, on
@@ -253,6 +294,8 @@ class BucketedDataParallel:
 
     def _sgd(self):
         """This step's fused SGD launch, bound to the current lr / decay (or to the device block)."""
+        if self.adam is not None:
+            return self._adamw()
         lr, mu, wd, n = self.lr, self.momentum, self.weight_decay, float(self.comm.world_size)
         hy = self.hyper.dev if self._hyper_on else None
         if capturing() and hy is None:
@@ -275,6 +318,24 @@ class BucketedDataParallel:
             if ema is not None:
                 ema.update()
         return clip_sgd
+
+    def _adamw(self):
+        """This step's fused AdamW launch in the SGD launch's place: clip, AdamW, EMA on one stream."""
+        adam, n = self.adam, float(self.comm.world_size)
+        b1, b2, eps = self.beta1, self.beta2, self.eps
+        hy = self.hyper.dev if self.hyper is not None else None
+        clip, max_norm, ema = self.clip, self.max_grad_norm, self.ema
+        self._bind_adam()  # a no-op unless the device tables were restored (upload_epoch)
+        if clip is not None:
+            clip.bind([self.g])
+
+        def clip_adamw_ema():
+            if clip is not None:
+                clip.run(max_norm, n)
+            adam.run(self.lr, self.weight_decay, b1, b2, eps, n, hy)  # lr / decay: the CPU twin's; the kernel reads hy
+            if ema is not None:
+                ema.update()
+        return clip_adamw_ema
 
     def plan_hyper(self, pairs):
         """Write the pinned source rows of the coming steps' ``(lr, weight_decay)`` ahead of time."""
@@ -354,6 +415,7 @@ class BucketedDataParallel:
 
     def snapshot(self):
         return {"x": self.x.clone(), "buf": self.buf.clone(), "step_count": self.step_count,
+                **({"v": self.v.clone(), "adam": self.adam.snapshot()} if self.adam is not None else {}),
                 **({"clip": self.clip.snapshot()} if self.clip is not None else {}),
                 **({"ema": self.ema.snapshot()} if self.ema is not None else {})}
 
@@ -361,6 +423,9 @@ class BucketedDataParallel:
         self.x.copy_(snap["x"])
         self.buf.copy_(snap["buf"])
         self.step_count = snap["step_count"]
+        if self.adam is not None:
+            self.v.copy_(snap["v"])
+            self.adam.restore(snap["adam"])
         if self.clip is not None:
             self.clip.restore(snap["clip"])
         if self.ema is not None and "ema" in snap:
@@ -371,11 +436,24 @@ class BucketedDataParallel:
             self.step_count += 1
 
     def state_dict(self):
+        if self.adam is not None:  # "momentum_buffer" is the first moment
+            st = self.adam.read()
+            return {"optimizer": "adamw", "momentum_buffer": self.buf.detach().cpu().clone(),
+                    "exp_avg_sq": self.v.detach().cpu().clone(), "b1pow": st["b1pow"], "b2pow": st["b2pow"],
+                    "steps": st["steps"], "lr": self.lr, "weight_decay": self.weight_decay,
+                    "betas": (self.beta1, self.beta2), "eps": self.eps, "momentum": self.momentum}
         return {"momentum_buffer": self.buf.detach().cpu().clone(), "lr": self.lr, "momentum": self.momentum,
                 "weight_decay": self.weight_decay}
 
     def load_state_dict(self, sd):
+        theirs = sd.get("optimizer", "sgd")  # a checkpoint without "optimizer" is an SGD checkpoint
+        if theirs != self.optimizer:
+            raise ValueError(f"dense arm: the checkpoint holds {theirs} optimizer state, this sync runs "
+                             f"{self.optimizer}; they cannot be loaded into each other")
         self.buf.copy_(sd["momentum_buffer"])
+        if self.adam is not None:
+            self.v.copy_(sd["exp_avg_sq"])
+            self.adam.write(sd)
         self.lr = float(sd["lr"])
         self.weight_decay = float(sd.get("weight_decay", 0.0))
         self.momentum = float(sd["momentum"])

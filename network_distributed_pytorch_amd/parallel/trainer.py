@@ -27,6 +27,14 @@ Every strategy has ``attach_ema(ema)``: an ``ops.WeightEma`` (ops/ema.py) whose 
 runs once per step, behind the step's last update launch and on its stream (inside a captured
 step); the native engines' ``snapshot()`` / ``restore()`` include it.  Nothing attached: every
 launch, snapshot and state dict is what it is without.
+
+``optimizer="adamw"`` (with ``betas``, ``eps``, ``decay_1d``) replaces momentum SGD by AdamW
+(ops/adamw.py) behind ``dense`` (the fused launch over the arenas), ``powersgd-ref`` / ``powersgd-api``
+(``FusedAdamW`` over the decompressed, averaged gradients; error memory and wire untouched) and
+``dense-ref`` (``torch.optim.AdamW`` with two param groups, capturable on a device); ``adam_stats()``
+returns the step count.  ``powersgd`` and the local optimisers raise: the fused update kernels step in
+the pass that decompresses and feeds back, and have no Adam variant yet.  With ``optimizer="sgd"``
+every constructor call is exactly what it is without these arguments.
 """
 from __future__ import annotations
 
@@ -34,12 +42,15 @@ from typing import Optional
 
 import torch
 
+from ..ops.adamw import FusedAdamW, check_adam_args
 from ..ops.gradclip import GradClip
 from .comm import Communicator
 from .ddp import BucketedDataParallel, average_gradients
 from .powersgd import PowerSGDOptimizer, PowerSGDReducer, powersgd_bytes_per_step
 
-__all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync"]
+__all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "ADAMW_SYNCS"]
+
+ADAMW_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # the arms that take optimizer="adamw"
 
 
 class PowerSGDSync:
@@ -106,9 +117,18 @@ class PowerSGDSync:
 class ReferencePowerSGDLoop:
     """Algorithm 2 exactly as the reference loop writes it (ddp_init.py:130-178)."""
 
-    def __init__(self, model, comm, lr, momentum, rank, seed=714, native_reducer=False, max_grad_norm=0.0):
+    def __init__(self, model, comm, lr, momentum, rank, seed=714, native_reducer=False, max_grad_norm=0.0,
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, decay_1d=True):
         self.model = model
         self.params = list(model.parameters())
+        # optimizer="adamw": ops.FusedAdamW over the decompressed, averaged gradients the reducer
+        # wrote, in the place of the momentum + SGD lines; error memory and wire untouched
+        self.adam = None
+        if optimizer == "adamw":
+            self.adam = FusedAdamW(self.params, lr, betas=betas, eps=eps,
+                                   decay_mask=[decay_1d or p.dim() > 1 for p in self.params])
+        elif optimizer != "sgd":
+            raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
         self.max_grad_norm = float(max_grad_norm)
         self.clip = _make_clip(self.max_grad_norm, self.params[0].device)
         self.lr, self.lam, self.weight_decay = lr, momentum, 0.0
@@ -139,6 +159,11 @@ class ReferencePowerSGDLoop:
         self.lr = float(lr)
         if weight_decay is not None:
             self.weight_decay = float(weight_decay)
+        if self.adam is not None:
+            self.adam.set_hyper(lr, weight_decay)
+
+    def adam_stats(self):
+        return self.adam.read() if self.adam is not None else None
 
     @torch.no_grad()
     def step(self):
@@ -150,6 +175,12 @@ class ReferencePowerSGDLoop:
             self.bits += self.reducer.reduce(self.send_buffers, grads, self.memories)
         else:
             self.bits += self.reducer.reduce_torch(self.send_buffers, grads, self.memories)
+        if self.adam is not None:  # decoupled decay, moments and the step in one launch (twin on CPU)
+            self.adam.bind(grads)
+            self.adam.step()
+            if self.ema is not None:
+                self.ema.update()
+            return self.bytes_per_step * 8
         if self.weight_decay != 0.0:  # L2 on the decompressed gradient: never in the memory or on the wire
             for p, g in zip(self.params, grads):
                 g.add_(p, alpha=self.weight_decay)
@@ -171,12 +202,26 @@ class ReferencePowerSGDLoop:
 
 
 class ReferenceDenseLoop:
-    def __init__(self, model, comm, lr, momentum, max_grad_norm=0.0):
+    def __init__(self, model, comm, lr, momentum, max_grad_norm=0.0, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8,
+                 decay_1d=True):
         self.model = model
         self.comm = comm
         self.max_grad_norm = float(max_grad_norm)
         self.clip = _make_clip(self.max_grad_norm, next(model.parameters()).device)
-        self.opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum)
+        self.optimizer = optimizer
+        if optimizer == "adamw":
+            # torch.optim.AdamW with two param groups: the reference-semantics comparison arm
+            b1, b2, eps = check_adam_args(betas, eps)
+            ps = list(model.parameters())
+            groups = [{"params": [p for p in ps if decay_1d or p.dim() > 1], "decays": True},
+                      {"params": [p for p in ps if not (decay_1d or p.dim() > 1)], "decays": False}]
+            # capturable on a device: torch refuses to capture AdamW's host-side step count otherwise
+            self.opt = torch.optim.AdamW([g for g in groups if g["params"]], lr=lr, betas=(b1, b2), eps=eps,
+                                         weight_decay=0.0, capturable=ps[0].is_cuda)
+        elif optimizer == "sgd":
+            self.opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum)
+        else:
+            raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
         self.bytes_per_step = 4 * sum(p.numel() for p in model.parameters())
         self._payloads = [4 * p.numel() for p in model.parameters()]  # ddp_init.py:61, one per param
         self.collectives_per_step = len(list(model.parameters())) if comm.active else 0
@@ -194,6 +239,12 @@ class ReferenceDenseLoop:
     def set_hyper(self, lr, weight_decay=None):
         _set_param_groups(self.opt, lr, weight_decay)
 
+    def adam_stats(self):
+        if self.optimizer != "adamw":
+            return None
+        steps = [int(s["step"]) for s in self.opt.state.values() if "step" in s]
+        return {"steps": max(steps) if steps else 0}
+
     def step(self):
         bits = average_gradients(self.model, self.comm)
         _clip(self.clip, self.max_grad_norm, [p.grad for p in self.model.parameters()])
@@ -207,10 +258,14 @@ class ReferenceDenseLoop:
 
 
 class _DenseSync:
-    def __init__(self, model, comm, lr, momentum, bucket_mb, overlap=None, max_grad_norm=0.0):
+    def __init__(self, model, comm, lr, momentum, bucket_mb, overlap=None, max_grad_norm=0.0, **adam):
+        # adam: optimizer / betas / eps / decay_1d, only when the optimiser is not SGD
         self.ddp = BucketedDataParallel(model, comm, lr=lr, momentum=momentum, bucket_mb=bucket_mb, overlap=overlap,
-                                        max_grad_norm=max_grad_norm)
+                                        max_grad_norm=max_grad_norm, **adam)
         self.bytes_per_step = self.ddp.bytes_per_step
+
+    def adam_stats(self):
+        return self.ddp.adam_stats()
 
     @property
     def collectives_per_step(self):
@@ -278,25 +333,36 @@ def _clip(clip: Optional[GradClip], max_grad_norm, grads):
 def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
     for group in opt.param_groups:
         group["lr"] = float(lr)
-        if weight_decay is not None:
+        if weight_decay is not None and group.get("decays", True):  # AdamW's exempt group stays at 0
             group["weight_decay"] = float(weight_decay)
 
 
 def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                     momentum: float = 0.9, rank: int = 4, bucket_mb: Optional[float] = None, seed: int = 714,
-                    max_grad_norm: float = 0.0, **kw):
+                    max_grad_norm: float = 0.0, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                    decay_1d: bool = True, **kw):
     comm = comm if comm is not None else Communicator()
     clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
+    adam = {}  # optimizer="sgd": every constructor call as before
+    if optimizer != "sgd":
+        if optimizer != "adamw":
+            raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
+        if kind not in ADAMW_SYNCS:
+            raise ValueError(f"grad sync {kind!r} has no AdamW: the fused PowerSGD update kernels decompress, feed "
+                             f"back and step in one register-pinned pass (an Adam variant of them is future work) and "
+                             f"the local optimisers are fixed recipes; use one of {', '.join(ADAMW_SYNCS)}")
+        b1, b2, eps = check_adam_args(betas, eps)
+        adam = {"optimizer": "adamw", "betas": (b1, b2), "eps": eps, "decay_1d": bool(decay_1d)}
     if kind == "powersgd":
         return PowerSGDSync(model, comm, lr, momentum, rank, seed=seed, **clip, **kw)
     if kind == "powersgd-ref":
-        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed, **clip)
+        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed, **clip, **adam)
     if kind == "powersgd-api":
-        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed, native_reducer=True, **clip)
+        return ReferencePowerSGDLoop(model, comm, lr, momentum, rank, seed=seed, native_reducer=True, **clip, **adam)
     if kind == "dense":
-        return _DenseSync(model, comm, lr, momentum, bucket_mb, overlap=kw.get("overlap"), **clip)
+        return _DenseSync(model, comm, lr, momentum, bucket_mb, overlap=kw.get("overlap"), **clip, **adam)
     if kind == "dense-ref":
-        return ReferenceDenseLoop(model, comm, lr, momentum, **clip)
+        return ReferenceDenseLoop(model, comm, lr, momentum, **clip, **adam)
     if kind in ("local-sgd-nesterov", "local-adamw"):
         return LocalOptimizer(model, kind, lr, momentum, **clip)
     raise ValueError(f"unknown grad sync {kind!r}")

@@ -32,6 +32,8 @@ AUGMENTS = ("none", "crop_flip")
 NORMALIZES = ("half", "cifar")
 MIXES = ("none", "mixup", "cutmix", "mixup_cutmix")  # ops/image_batch.py: image_mix_batch
 LR_SCHEDULES = ("constant", "step", "cosine")  # utils/schedule.py
+OPTIMIZERS = ("sgd", "adamw")
+ADAMW_GRAD_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # parallel/trainer.py ADAMW_SYNCS
 
 
 @dataclasses.dataclass
@@ -105,6 +107,13 @@ class TrainConfig:
     # exponential moving average of the weights (ops/ema.py), evaluated and checkpointed next to them
     ema_decay: float = 0.0  # 0 = off; 0 < decay < 1: shadow += (1 - d) * (weights - shadow) after every step
     ema_warmup: bool = True  # d = min(decay, (n + 1) / (n + 10)) for update n (the TF / timm warm-up)
+    # the optimiser behind the gradient sync: "sgd" (momentum) or "adamw" (ops/adamw.py; dense, dense-ref,
+    # powersgd-ref and powersgd-api only); with "adamw", weight_decay is the decoupled decay
+    optimizer: str = "sgd"
+    adam_beta1: float = 0.9
+    adam_beta2: float = 0.999
+    adam_eps: float = 1e-8
+    decay_1d: bool = True  # False: biases, LayerNorm / BatchNorm weights (tensors of <= 1 dimension) do not decay
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -190,6 +199,16 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
     if not 0 <= c["ema_decay"] < 1 or (c["ema_decay"] > 0 and not 0 < np.float32(c["ema_decay"]) < 1):
         # NaN fails the comparison too; a decay that rounds to 0 or 1 in fp32 is no average
         raise ConfigError(f"ema_decay = {c['ema_decay']} must lie in [0, 1) (0 = off)")
+    if c["optimizer"] not in OPTIMIZERS:
+        raise ConfigError(f"config['optimizer'] = {c['optimizer']!r}; allowed: {list(OPTIMIZERS)}")
+    for key in ("adam_beta1", "adam_beta2"):  # as fp32, what the kernel receives; NaN fails the comparison too
+        if not 0 <= np.float32(c[key]) < 1:
+            raise ConfigError(f"{key} = {c[key]} must lie in [0, 1)")
+    if not np.float32(c["adam_eps"]) > 0 or not np.isfinite(c["adam_eps"]):
+        raise ConfigError(f"adam_eps = {c['adam_eps']} must be a finite number > 0 (as fp32)")
+    if c["optimizer"] == "adamw" and c["grad_sync"] not in ADAMW_GRAD_SYNCS:
+        raise ConfigError(f"optimizer='adamw' is not available with grad_sync={c['grad_sync']!r} (the fused PowerSGD "
+                          f"engine and the local optimisers have no AdamW); allowed: {list(ADAMW_GRAD_SYNCS)}")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too
         raise ConfigError(f"max_grad_norm = {c['max_grad_norm']} must be >= 0 (0 = off, inf = measure only)")
     if c["max_grad_norm"] > 0 and c["grad_sync"] == "powersgd" and c["overlap"]:

@@ -15,7 +15,9 @@ default).  Additions: ``-spawn`` launches all ranks locally (127.0.0.1 rendezvou
 schedule and L2 weight decay, utils/schedule.py), ``-max_grad_norm`` (clip the gradient by its global L2
 norm, ops/gradclip.py; ``inf`` only measures it), ``-label_smoothing`` (ops/loss.py) and ``-mix`` /
 ``-mix_prob`` (mixup / CutMix of the byte-image batches, ops/image_batch.py; needs ``-data_root``),
-``-ema_decay`` / ``-ema_warmup`` (exponential moving average of the weights, ops/ema.py).
+``-ema_decay`` / ``-ema_warmup`` (exponential moving average of the weights, ops/ema.py), ``-optimizer`` /
+``-adam_beta1`` / ``-adam_beta2`` / ``-adam_eps`` / ``-decay_1d`` (fused AdamW behind the gradient sync,
+ops/adamw.py).
 """
 from __future__ import annotations
 
@@ -87,6 +89,14 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
                    help="keep an exponential moving average of the weights with this decay (default 0 = off)")
     p.add_argument("-ema_warmup", type=int, default=None, choices=[None, 0, 1],
                    help="EMA decay warm-up min(decay, (n + 1) / (n + 10)) (default 1)")
+    p.add_argument("-optimizer", type=str, default=None, choices=[None, "sgd", "adamw"],
+                   help="adamw: fused AdamW behind dense / dense-ref / powersgd-ref / powersgd-api (default sgd); "
+                        "-weight_decay is then the decoupled decay")
+    p.add_argument("-adam_beta1", type=float, default=None, help="AdamW beta1 in [0, 1) (default 0.9)")
+    p.add_argument("-adam_beta2", type=float, default=None, help="AdamW beta2 in [0, 1) (default 0.999)")
+    p.add_argument("-adam_eps", type=float, default=None, help="AdamW eps > 0 (default 1e-8)")
+    p.add_argument("-decay_1d", type=int, default=None, choices=[None, 0, 1],
+                   help="AdamW: 0 exempts biases and LayerNorm / BatchNorm weights from the decay (default 1)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -103,7 +113,8 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "lr_schedule": "lr_schedule", "lr_warmup_steps": "lr_warmup_steps", "lr_min": "lr_min",
         "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay",
         "max_grad_norm": "max_grad_norm", "label_smoothing": "label_smoothing", "mix": "mix",
-        "mix_prob": "mix_prob", "ema_decay": "ema_decay"}
+        "mix_prob": "mix_prob", "ema_decay": "ema_decay", "optimizer": "optimizer", "adam_beta1": "adam_beta1",
+        "adam_beta2": "adam_beta2", "adam_eps": "adam_eps"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
@@ -125,6 +136,8 @@ def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional
         c["overlap"] = bool(args.overlap)
     if args.ema_warmup is not None:
         c["ema_warmup"] = bool(args.ema_warmup)
+    if args.decay_1d is not None:
+        c["decay_1d"] = bool(args.decay_1d)
     if args.quiet:
         c["verbose"] = False
     if args.trace:

@@ -18,7 +18,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("bindings.cpp", "plan.cpp", "comm.cpp
                                                 "multitensor.hip", "batchnorm.hip", "attention.hip", "conv.hip",
                                                 "pool.hip", "embedding.hip", "linear.hip", "loss.hip", "layernorm.hip",
                                                 "tgemm.hip", "ipc.hip", "winograd.hip", "image_batch.hip", "gradclip.hip",
-                                                "ema.hip")]
+                                                "ema.hip", "adamw.hip")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
