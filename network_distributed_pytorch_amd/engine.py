@@ -435,12 +435,9 @@ def run_task(config) -> Dict[str, Any]:
     else:
         logger = JsonlLogger(log_path, rank)
     log_every = int(config.get("log_every") or 0) if logger.enabled else 0
-    flat = getattr(getattr(sync, "opt", None), "x", None)
-    if flat is None:
-        flat = getattr(getattr(sync, "ddp", None), "x", None)
     checker = None
-    if config.get("check_replicas_every") and flat is not None:
-        checker = ReplicaChecker(comm, flat, every=config["check_replicas_every"])
+    if config.get("check_replicas_every") and sync.flat_weights is not None:
+        checker = ReplicaChecker(comm, sync.flat_weights, every=config["check_replicas_every"])
 
     loss_fn = _loss_fn(config, model, crit)
     runner = None
@@ -475,7 +472,7 @@ def run_task(config) -> Dict[str, Any]:
     weight_decay = float(config.get("weight_decay") or 0.0)
     hyper_on = schedule.varies or weight_decay != 0.0
     lr_now = None
-    if hyper_on and hasattr(sync, "plan_hyper"):  # the pinned source rows of the whole run, written once
+    if hyper_on:  # the pinned source rows of the whole run, written once
         sync.plan_hyper((schedule.lr_at(s), weight_decay) for s in range(step, schedule.T))
 
     timer = PhaseTimer() if (config.get("trace_phases") and runner is None) else None
@@ -546,13 +543,14 @@ def run_task(config) -> Dict[str, Any]:
                 epoch_loss += loss.detach()
                 with timer.phase("backward"):
                     loss.backward()
-                if hasattr(sync, "phases"):
-                    for fn, is_comm in sync.phases():
-                        with timer.phase(("comm:" if is_comm else "compute:") + fn.__name__):
-                            fn()
-                else:
+                phases = sync.phases()
+                if phases is None:
                     with timer.phase("grad_sync+update"):
                         sync.step()
+                else:
+                    for fn, is_comm in phases:
+                        with timer.phase(("comm:" if is_comm else "compute:") + fn.__name__):
+                            fn()
             else:
                 sync.zero_grad()
                 loss = loss_fn(batch)
@@ -566,7 +564,7 @@ def run_task(config) -> Dict[str, Any]:
                 if runner is not None and step % checker.every == 0:
                     runner.join()
                 checker.check(step)
-            if health_every and step % health_every == 0 and hasattr(sync, "check_errors"):
+            if health_every and step % health_every == 0:
                 if runner is not None:
                     runner.join()
                 sync.check_errors()  # flag-wait timeouts / MGS barrier / RCCL async errors: fatal
@@ -581,11 +579,11 @@ def run_task(config) -> Dict[str, Any]:
                            step_ms=1e3 * (now - t_prev) / n,
                            samples_per_s=bsz * world * n / max(now - t_prev, 1e-9),
                            payload_bytes=(comm.stats.payload_bytes - pay_prev) / n
-                           if runner is None or graph_mode == "piecewise" else getattr(sync, "bytes_per_step", None),
+                           if runner is None or graph_mode == "piecewise" else sync.bytes_per_step,
                            wire_bytes=(comm.stats.wire_bytes - wire_prev) / n
                            if runner is None or graph_mode == "piecewise" else
-                           _ring_wire(getattr(sync, "bytes_per_step", 0) or 0, comm.paced_world),
-                           bytes_per_step=getattr(sync, "bytes_per_step", None),
+                           _ring_wire(sync.bytes_per_step, comm.paced_world),
+                           bytes_per_step=sync.bytes_per_step,
                            **({"lr": lr_now} if hyper_on else {}),
                            **(_clip_step_record(clip_read()) if clip_on else {}))
                 last_log = (now, comm.stats.payload_bytes, comm.stats.wire_bytes, step)
@@ -594,8 +592,7 @@ def run_task(config) -> Dict[str, Any]:
         # reference: epoch_loss / num_batches (ddp_powersgd_guide_cifar10/ddp_init.py:118,183);
         # a step cap (max_steps_per_epoch, an addition) divides by the steps actually run
         mean = float(epoch_loss.item()) / max(1, num_batches if i == num_batches else i)
-        if hasattr(sync, "check_errors"):
-            sync.check_errors()  # MGS barrier timeouts / RCCL async errors (epoch cadence)
+        sync.check_errors()  # MGS barrier timeouts / RCCL async errors (epoch cadence)
         if hasattr(loader.ds, "check_errors"):
             loader.ds.check_errors()
         losses.append(mean)
@@ -614,7 +611,7 @@ def run_task(config) -> Dict[str, Any]:
             print_epoch(rank, epoch, mean)
             print(">>>>> Rank ", rank, ", epoch ", epoch, " Finished...\n", flush=True)
         logger.log(kind="epoch", epoch=epoch, mean_loss=mean, steps=i, num_batches=num_batches,
-                   bytes_per_step=getattr(sync, "bytes_per_step", None), comm=comm.stats.as_dict(),
+                   bytes_per_step=sync.bytes_per_step, comm=comm.stats.as_dict(),
                    phase_ms=timer.summary() if timer is not None else None, **({"lr": lr_now} if hyper_on else {}),
                    **epoch_rec)
         if config.get("checkpoint_dir"):
@@ -649,14 +646,12 @@ def run_task(config) -> Dict[str, Any]:
     elapsed = time.perf_counter() - t_start - eval_s  # training time: evaluation is reported as eval_s
     _log(config, "All Task Finished")
     _log(config, "==============================\n")
-    flat = getattr(getattr(sync, "opt", None), "x", None)
-    if flat is None:
-        flat = getattr(getattr(sync, "ddp", None), "x", None)
+    flat = sync.flat_weights
     if flat is None:
         flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
     summary = {"epoch_losses": losses, "steps": step, "elapsed_s": elapsed, "samples": samples,
                "samples_per_s": samples / elapsed if elapsed > 0 else None,
-               "bytes_per_step": getattr(sync, "bytes_per_step", None), "comm": comm.stats.as_dict(),
+               "bytes_per_step": sync.bytes_per_step, "comm": comm.stats.as_dict(),
                "comm_backend": comm.backend, "world_size": world, "per_rank_batch": bsz, "graph_mode": graph_mode,
                "param_checksum": float(flat.double().sum().item())}
     if hyper_on:

@@ -28,6 +28,7 @@ __all__ = [
     "SegPlan",
     "read_block4",
     "write_block4",
+    "StateBlock",
     "upload_epoch",
     "classification_metrics",
     "ClassificationMetrics",
@@ -301,6 +302,46 @@ def write_block4(block: torch.Tensor, f0: float, f1: float, u0: int = 0, u1: int
         u &= 0xffffffff
         host[i] = u - (1 << 32) if u >= (1 << 31) else u
     block.copy_(host)
+
+
+class StateBlock:
+    """One 16-byte state block ``{float, float, uint32, uint32}`` that a kernel keeps between launches
+    (``ClipBlock``, ``EmaBlock``, ``AdamBlock``), built from its field ``names`` (two floats, then up to
+    two counters) and their initial values.
+
+    On a device it is ``dev``, an ``int32[4]`` tensor allocated here, before any capture, and never
+    re-allocated: the kernel argument.  On CPU ``dev`` is None and the block is a dict, which the
+    torch twins read and write.  Values are stored as given; a caller that wants fp32 rounding
+    rounds first.
+    """
+
+    def __init__(self, device, names: Sequence[str], init: Sequence):
+        self.names = tuple(names)
+        self.dev: Optional[torch.Tensor] = None
+        if torch.device(device).type == "cuda":
+            self.dev = torch.zeros(4, dtype=torch.int32, device=device)
+        self.write(dict(zip(self.names, init)))
+
+    def read(self) -> dict:
+        """The fields by name: a host sync on a device."""
+        return dict(zip(self.names, read_block4(self.dev))) if self.dev is not None else dict(self._state)
+
+    def write(self, st) -> None:
+        vals = [float(st[k]) if i < 2 else int(st[k]) for i, k in enumerate(self.names)]
+        if self.dev is not None:
+            write_block4(self.dev, *vals)
+        else:
+            self._state = dict(zip(self.names, vals))
+
+    def snapshot(self):
+        """The contents, for :meth:`restore` (a graph warm-up leaves no trace in the block)."""
+        return self.dev.clone() if self.dev is not None else dict(self._state)
+
+    def restore(self, snap) -> None:
+        if self.dev is not None:
+            self.dev.copy_(snap)
+        else:
+            self._state = dict(snap)
 
 
 def delay_ns(ns: int) -> None:

@@ -39,9 +39,9 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _UPLOADS, capturing, read_block4, upload, write_block4
+from . import _UPLOADS, StateBlock, capturing, upload
 from ._ext import ext
-from .hyper import HyperBlock
+from .hyper import HyperState
 
 __all__ = ["FusedAdamW", "AdamWCore", "adamw_scalars", "check_adam_args"]
 
@@ -131,7 +131,8 @@ class AdamWCore:
         self.rows: List[tuple] = []
         self._key = None
         self._n_ent = self._n_blocks = 0
-        self._state = {"b1pow": 1.0, "b2pow": 1.0, "steps": 0}  # the twin's block
+        self.state = StateBlock(self.device, ("b1pow", "b2pow", "steps"), (1.0, 1.0, 0))
+        self.block = self.state.dev  # the kernel's argument (None on CPU: the twin keeps a dict)
         if self.cuda:
             assert not capturing(), "the AdamW tables are built before capture"
             X = ext()
@@ -140,8 +141,6 @@ class AdamWCore:
             self._ent = torch.empty(self._cap * X.SIZEOF_SEGENTRY, dtype=torch.uint8, device=self.device)
             self._prefix = torch.empty(self._cap, dtype=torch.int64, device=self.device)
             self.ctr = torch.zeros(X.arrive_ctr_words(self._max_blocks), dtype=torch.int32, device=self.device)
-            self.block = torch.zeros(4, dtype=torch.int32, device=self.device)
-            write_block4(self.block, 1.0, 1.0, 0, 0)
 
     def bind(self, rows: Sequence[tuple]) -> None:
         rows = list(rows)
@@ -185,47 +184,42 @@ class AdamWCore:
             ext().adamw_step(self._ent, self._prefix, self._n_ent, self._n_blocks, self.ctr, self.block, hyper,
                              self.m, self.v, float(beta1), float(beta2), float(eps), float(div))
             return
-        st = self._state
+        st = self.state.read()
         S = adamw_scalars(st["b1pow"], st["b2pow"], lr, wd, beta1, beta2)
         with torch.no_grad():
             for g, x, off, dec in self.rows:
                 n = x.numel()
                 _twin_(x.view(-1), g.reshape(-1), self.m[off: off + n], self.v[off: off + n], S, beta1, beta2, eps,
                        float(div), bool(dec) and F(wd) != F(0.0))
-        self._state = {"b1pow": float(S["p1"]), "b2pow": float(S["p2"]), "steps": st["steps"] + 1}
+        self.state.write({"b1pow": float(S["p1"]), "b2pow": float(S["p2"]), "steps": st["steps"] + 1})
 
     # ---- the block ----------------------------------------------------------------------------
     def read(self) -> Dict[str, Any]:
         """``{"b1pow", "b2pow", "steps"}``: a host sync on a device."""
-        if self.cuda:
-            return dict(zip(("b1pow", "b2pow", "steps"), read_block4(self.block)))
-        return dict(self._state)
+        return self.state.read()
 
     def write(self, st: Dict[str, Any]) -> None:
-        self._state = {"b1pow": float(F(st["b1pow"])), "b2pow": float(F(st["b2pow"])), "steps": int(st["steps"])}
-        if self.cuda:
-            write_block4(self.block, self._state["b1pow"], self._state["b2pow"], self._state["steps"], 0)
+        self.state.write({"b1pow": float(F(st["b1pow"])), "b2pow": float(F(st["b2pow"])), "steps": st["steps"]})
 
     def snapshot(self):
-        return self.block.clone() if self.cuda else dict(self._state)
+        return self.state.snapshot()
 
     def restore(self, snap) -> None:
-        if self.cuda:
-            self.block.copy_(snap)
-        else:
-            self._state = dict(snap)
+        self.state.restore(snap)
 
 
-class FusedAdamW:
+class FusedAdamW(HyperState):
     """The AdamW of the module docstring over ``params`` (tensors updated in place; never
     re-targeted), ``decay_mask[i]`` False exempting tensor ``i`` from the weight decay.
 
     Owns the two flat fp32 moment arenas, in which every moment sits as far past a 16-byte
     boundary as its parameter (an aligned parameter keeps the float4 path), ``exp_avg`` /
     ``exp_avg_sq`` (views shaped like ``params``), and on a device the table, the tickets, the
-    state block and a :class:`HyperBlock`.  Everything exists after construction, which is eager;
+    state block and a :class:`HyperBlock` (the :class:`HyperState` protocol; the kernel always reads it).  Everything exists after construction, which is eager;
     :meth:`step` is one launch and capture-safe.  On a CPU device the same class runs the twin.
     """
+
+    _arm = "FusedAdamW"
 
     def __init__(self, params: Sequence[torch.Tensor], lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decay_mask: Optional[Sequence[bool]] = None):
@@ -236,7 +230,6 @@ class FusedAdamW:
         lr, wd = float(lr), float(weight_decay)
         if not (math.isfinite(lr) and lr >= 0.0) or not (math.isfinite(wd) and wd >= 0.0):
             raise ValueError(f"FusedAdamW: lr and weight_decay must be finite and >= 0, got {lr}, {wd}")
-        self.lr, self.weight_decay = float(F(lr)), float(F(wd))
         self.decays = [True] * len(self.params) if decay_mask is None else [bool(d) for d in decay_mask]
         if len(self.decays) != len(self.params):
             raise ValueError(f"FusedAdamW: decay_mask of {len(self.decays)} for {len(self.params)} parameters")
@@ -268,7 +261,7 @@ class FusedAdamW:
         self.exp_avg_sq = [self.v_arena[o: o + p.numel()].view(p.shape) for o, p in zip(self.offsets, self.params)]
         blocks = sum((p.numel() + 2047) // 2048 for p in self.params)
         self.core = AdamWCore(self.device, self.m_arena, self.v_arena, len(self.params), blocks)
-        self.hyper = HyperBlock(self.device, self.lr, self.weight_decay) if cuda else None
+        self._init_hyper(float(F(lr)), float(F(wd)), block=cuda, on=True)
         self._bound = False
 
     # ---- the rule -----------------------------------------------------------------------------
@@ -312,23 +305,7 @@ class FusedAdamW:
         the twin on CPU."""
         if not self._bound:
             raise RuntimeError("FusedAdamW.step: bind() the gradients first")
-        self.core.run(self.lr, self.weight_decay, self.beta1, self.beta2, self.eps, div,
-                      self.hyper.dev if self.hyper is not None else None)
-
-    def set_hyper(self, lr: float, weight_decay: Optional[float] = None) -> None:
-        """Learning rate and weight decay of the steps from now on (fp32 values), captured replays
-        included: on a device one 16-byte async copy on the current stream, none when neither
-        changed.  Never inside a capture."""
-        wd = self.weight_decay if weight_decay is None else float(weight_decay)
-        assert wd >= 0, "weight_decay >= 0"
-        self.lr, self.weight_decay = float(F(lr)), float(F(wd))
-        if self.hyper is not None:
-            self.hyper.set(self.lr, self.weight_decay)
-
-    def plan_hyper(self, pairs) -> None:
-        """Write the pinned source rows of the coming steps' ``(lr, weight_decay)`` ahead of time."""
-        if self.hyper is not None:
-            self.hyper.prefill(pairs)
+        self.core.run(self.lr, self.weight_decay, self.beta1, self.beta2, self.eps, div, self._hyper_arg())
 
     # ---- state --------------------------------------------------------------------------------
     def read(self) -> Dict[str, Any]:
@@ -369,8 +346,4 @@ class FusedAdamW:
                     t.copy_(val)
         self.core.write(sd)
         if "lr" in sd:
-            self.lr = float(F(sd["lr"]))
-            self.weight_decay = float(F(sd.get("weight_decay", self.weight_decay)))
-            if self.hyper is not None:
-                assert not capturing(), "load_state_dict() inside a graph capture"
-                self.hyper.set(self.lr, self.weight_decay, force=True)
+            self._load_hyper(float(F(sd["lr"])), float(F(sd.get("weight_decay", self.weight_decay))))

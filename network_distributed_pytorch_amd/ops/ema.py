@@ -25,7 +25,7 @@ from typing import Any, Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import SegPlan, read_block4, write_block4
+from . import SegPlan, StateBlock
 from ._ext import ext
 
 __all__ = ["WeightEma", "ema_decay_at"]
@@ -107,7 +107,8 @@ class WeightEma:
         with torch.no_grad():
             for s, t in zip(self.shadow, self.tensors):
                 s.copy_(t)
-        self._state = {"decay": 0.0, "weight": 0.0, "updates": 0}  # the twin's block
+        self.state = StateBlock(self.device, ("decay", "weight", "updates"), (0.0, 0.0, 0))
+        self.block = self.state.dev  # the kernels' argument (None on CPU: the twin keeps a dict)
         if cuda:
             specs = []
             for r, (i0, n, _, _) in enumerate(runs):
@@ -118,7 +119,6 @@ class WeightEma:
                 specs.append((live, self.arena[offs[r]: offs[r] + n], 1, 0, 1.0))
             self.plan = SegPlan(specs, self.device)
             self.ctr = torch.zeros(ext().arrive_ctr_words(self.plan.n_blocks), dtype=torch.int32, device=self.device)
-            self.block = torch.zeros(4, dtype=torch.int32, device=self.device)
 
     # ---- the rule ---------------------------------------------------------------------------
     def update(self) -> None:
@@ -127,14 +127,14 @@ class WeightEma:
             if not self.plan.launch(ext().ema_update, self.ctr, self.block, self.decay, self.warmup):
                 raise RuntimeError("WeightEma.update: empty table")
             return
-        st = self._state
-        d, w = ema_decay_at(self.decay, st["updates"], self.warmup)
+        n = self.state.read()["updates"]
+        d, w = ema_decay_at(self.decay, n, self.warmup)
         with torch.no_grad():
             for s, x in zip(self.shadow, self.tensors):
                 t = torch.sub(x, s)
                 u = torch.mul(t, float(w))
                 s.copy_(torch.add(s, u))
-        st["decay"], st["weight"], st["updates"] = float(d), float(w), st["updates"] + 1
+        self.state.write({"decay": float(d), "weight": float(w), "updates": n + 1})
 
     def swap(self) -> None:
         """Exchange live tensors and shadows bitwise (twice: the identity)."""
@@ -151,34 +151,23 @@ class WeightEma:
     # ---- state ------------------------------------------------------------------------------
     def read(self) -> Dict[str, Any]:
         """``{"decay", "weight", "updates"}`` of the block: a host sync on a device."""
-        if self.device.type == "cuda":
-            return dict(zip(("decay", "weight", "updates"), read_block4(self.block)))
-        return dict(self._state)
-
-    def _write_block(self, st: Dict[str, Any]) -> None:
-        self._state = {"decay": float(st["decay"]), "weight": float(st["weight"]), "updates": int(st["updates"])}
-        if self.device.type == "cuda":
-            write_block4(self.block, self._state["decay"], self._state["weight"], self._state["updates"])
+        return self.state.read()
 
     def reset(self) -> None:
         """The state after construction: the shadow a copy of the live tensors, ``updates = 0``."""
         with torch.no_grad():
             for s, t in zip(self.shadow, self.tensors):
                 s.copy_(t)
-        self._write_block({"decay": 0.0, "weight": 0.0, "updates": 0})
+        self.state.write({"decay": 0.0, "weight": 0.0, "updates": 0})
 
     def snapshot(self):
         """Shadow and block, for :meth:`restore` (a graph warm-up leaves no trace)."""
-        blk = self.block.clone() if self.device.type == "cuda" else dict(self._state)
-        return self.arena.clone(), blk
+        return self.arena.clone(), self.state.snapshot()
 
     def restore(self, snap) -> None:
         arena, blk = snap
         self.arena.copy_(arena)
-        if self.device.type == "cuda":
-            self.block.copy_(blk)
-        else:
-            self._state = dict(blk)
+        self.state.restore(blk)
 
     def state_dict(self, names: Sequence[str]) -> Dict[str, Any]:
         """``{"shadow": {name: CPU tensor}, "updates", "decay", "weight"}``; ``names`` are the
@@ -199,4 +188,4 @@ class WeightEma:
                 if tuple(v.shape) != tuple(s.shape):
                     raise ValueError(f"WeightEma.load_state_dict: shape {tuple(v.shape)} for {tuple(s.shape)}")
                 s.copy_(v)
-        self._write_block(sd)
+        self.state.write(sd)  # as stored: not rounded again

@@ -28,7 +28,7 @@ from typing import Any, Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import SegPlan, read_block4
+from . import SegPlan, StateBlock
 from ._ext import ext
 
 __all__ = ["GradClip", "clip_grad_norm_"]
@@ -72,7 +72,8 @@ class GradClip:
         self.device = torch.device(device)
         self.tensors: List[torch.Tensor] = []
         self._retired: list = []  # outgrown partials: a captured graph may still hold the address
-        self._state = {"norm": 0.0, "coef": 1.0, "clipped": 0, "steps": 0}  # the twin's block
+        self.state = StateBlock(self.device, ("norm", "coef", "clipped", "steps"), (0.0, 1.0, 0, 0))
+        self.clip = self.state.dev  # the kernels' argument (None on CPU: the twin keeps a dict)
         self._empty = True  # the last run had nothing to reduce: norm 0, coef 1
         if self.device.type == "cuda":
             assert not torch.cuda.is_current_stream_capturing(), "GradClip is built before capture"
@@ -81,8 +82,6 @@ class GradClip:
             # the two-level arrival tickets of the table's workgroups: zero, re-armed by every launch
             self.ctr = torch.zeros(ext().arrive_ctr_words(self.partial.numel()), dtype=torch.int32,
                                    device=self.device)
-            self.clip = torch.zeros(4, dtype=torch.int32, device=self.device)
-            self.clip[1:2].view(torch.float32).fill_(1.0)
 
     def bind(self, tensors: Sequence[torch.Tensor]) -> None:
         """Re-target the table at ``tensors`` (uploaded only when an address changed; inside a
@@ -117,20 +116,16 @@ class GradClip:
         if self._empty:
             return
         norm, coef = _twin(self.tensors, max_norm, div)
-        st = self._state
-        st["norm"], st["coef"] = float(norm), float(coef)
-        st["steps"] += 1
-        st["clipped"] += int(coef != np.float32(1.0))
+        st = self.state.read()
+        self.state.write({"norm": float(norm), "coef": float(coef), "steps": st["steps"] + 1,
+                          "clipped": st["clipped"] + int(coef != np.float32(1.0))})
 
     def snapshot(self):
         """The block's contents, for :meth:`restore` (a graph warm-up leaves no trace in the counters)."""
-        return self.clip.clone() if self.device.type == "cuda" else dict(self._state)
+        return self.state.snapshot()
 
     def restore(self, snap) -> None:
-        if self.device.type == "cuda":
-            self.clip.copy_(snap)
-        else:
-            self._state = dict(snap)
+        self.state.restore(snap)
 
     def norm_tensor(self) -> torch.Tensor:
         """The fp32 norm of the last run as a 0-dim tensor on the device (no host sync)."""
@@ -138,14 +133,11 @@ class GradClip:
             return torch.zeros((), dtype=torch.float32, device=self.device)
         if self.device.type == "cuda":
             return self.clip[0:1].view(torch.float32).clone().reshape(())
-        return torch.tensor(self._state["norm"], dtype=torch.float32)
+        return torch.tensor(self.state.read()["norm"], dtype=torch.float32)
 
     def read(self) -> Dict[str, Any]:
         """``{"norm", "coef", "clipped", "steps"}`` of the block: a host sync on a device."""
-        if self.device.type == "cuda":
-            out = dict(zip(("norm", "coef", "clipped", "steps"), read_block4(self.clip)))
-        else:
-            out = dict(self._state)
+        out = self.state.read()
         if self._empty:
             out["norm"], out["coef"] = 0.0, 1.0
         return out

@@ -49,14 +49,13 @@ from __future__ import annotations
 
 from typing import Any, Dict, List, Optional
 
-import numpy as np
 import torch
 
 from ..ops import SegPlan, capturing, gradarena, gradfinish, sgd_momentum_
 from ..ops.adamw import AdamWCore, check_adam_args
-from ..ops.gradclip import GradClip
-from ..ops.hyper import HyperBlock
+from ..ops.hyper import HyperState
 from .comm import Communicator, all_reduce, world_size
+from .sync import GradSync
 
 __all__ = ["average_gradients", "BucketedDataParallel", "DEFAULT_BUCKET_MB"]
 
@@ -79,7 +78,9 @@ def average_gradients(model: torch.nn.Module, comm: Optional[Communicator] = Non
     return bits
 
 
-class BucketedDataParallel:
+class BucketedDataParallel(HyperState, GradSync):
+    _arm = "dense arm"
+
     def __init__(self, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                  momentum: float = 0.9, bucket_mb: Optional[float] = None, broadcast_params: bool = True,
                  overlap: Optional[bool] = None, weight_decay: float = 0.0,
@@ -92,21 +93,16 @@ class BucketedDataParallel:
         self.decay_1d = bool(decay_1d)
         if optimizer == "adamw":
             self.beta1, self.beta2, self.eps = check_adam_args(betas, eps)
-        assert max_grad_norm >= 0, "max_grad_norm >= 0 (0: off, inf: measure only)"
-        self.max_grad_norm = float(max_grad_norm)
         bucket_mb = DEFAULT_BUCKET_MB if bucket_mb is None else float(bucket_mb)
         self.model = model
         self.comm = comm if comm is not None else Communicator()
-        self.lr = float(lr)
         self.momentum = float(momentum)
-        self.weight_decay = float(weight_decay)
         self.params: List[torch.nn.Parameter] = [p for p in model.parameters() if p.requires_grad]
         self.device = self.params[0].device
         # device block [lr, weight_decay, 0, 0], allocated before any capture; the SGD kernel reads it
         # once set_hyper() was called or a decay is on, else lr goes by value
-        self.hyper = HyperBlock(self.device, self.lr, self.weight_decay) if self.device.type == "cuda" else None
-        self._hyper_on = self.hyper is not None and self.weight_decay != 0.0
-        self._captured_by_value = False
+        self._init_hyper(float(lr), float(weight_decay), block=self.device.type == "cuda",
+                         on=True if optimizer == "adamw" else None)  # the AdamW kernel has no by-value lr
         order = list(reversed(self.params))
         offs, o = {}, 0
         for p in order:
@@ -168,11 +164,9 @@ class BucketedDataParallel:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
         self.step_count = 0
         # global-norm clip over the flat gradient arena as ONE table entry, built before any capture
-        self.clip: Optional[GradClip] = None
-        if self.max_grad_norm > 0:
-            self.clip = GradClip(self.device, capacity=1, blocks=(self.numel + 2047) // 2048)
+        self._init_clip(max_grad_norm, self.device, capacity=1, blocks=(self.numel + 2047) // 2048)
+        if self.clip is not None:
             self.clip.bind([self.g])
-        self.ema = None  # ops.WeightEma updated behind the SGD launch (attach_ema)
         # AdamW: second-moment arena, and the table over (g, x, buf, v): one entry per run of
         # parameters (arena order, padding included: zero g / m / v keep it zero) that decay alike
         self.adam: Optional[AdamWCore] = None
@@ -191,7 +185,6 @@ class BucketedDataParallel:
             self.adam = AdamWCore(self.device, self.buf, self.v, len(runs),
                                   sum((e - s + 2047) // 2048 for s, e, _ in runs))
             self._bind_adam()
-            self._hyper_on = self.hyper is not None  # the kernel has no by-value lr
 
     def _bind_adam(self):
         self.adam.bind([(self.g[s:e], self.x[s:e], s, dec) for s, e, dec in self.adam_runs])
@@ -200,17 +193,12 @@ class BucketedDataParallel:
         """``{"b1pow", "b2pow", "steps"}`` of the AdamW block (a host sync), or None with SGD."""
         return self.adam.read() if self.adam is not None else None
 
-    def attach_ema(self, ema):
-        """Keep ``ema`` (ops/ema.py) of the weights: one launch behind every step's SGD launch, on
-        its stream (the side stream in stream mode), inside the captured step; part of
-        :meth:`snapshot`.  None detaches."""
-        assert not capturing(), "attach_ema() inside a graph capture"
-        self.ema = ema
+    @property
+    def flat_weights(self) -> torch.Tensor:
+        return self.x
 
-    def clip_stats(self) -> Optional[Dict[str, Any]]:
-        """``{"norm", "coef", "clipped", "steps"}`` of the gradient clip (a host sync), or None when
-        ``max_grad_norm`` is 0.  The norm is that of the averaged gradient, equal on every rank."""
-        return self.clip.read() if self.clip is not None else None
+    def check_errors(self):
+        self.comm.check()
 
     @property
     def bytes_per_step(self) -> int:
@@ -293,82 +281,35 @@ class BucketedDataParallel:
             self._works[b] = None
 
     def _sgd(self):
-        """This step's fused SGD launch, bound to the current lr / decay (or to the device block)."""
+        """This step's update, bound to the current lr / decay (or to the device block): the clip if
+        any (norm of sum g / N, arena scaled in place), the fused SGD or AdamW launch, the EMA tail,
+        all on one stream."""
+        n = float(self.comm.world_size)
+        hy = self._hyper_arg()
         if self.adam is not None:
-            return self._adamw()
-        lr, mu, wd, n = self.lr, self.momentum, self.weight_decay, float(self.comm.world_size)
-        hy = self.hyper.dev if self._hyper_on else None
-        if capturing() and hy is None:
-            self._captured_by_value = True
-        ema = self.ema
-        if self.clip is None:
-            if ema is None:
-                return lambda: sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
+            adam, b1, b2, eps = self.adam, self.beta1, self.beta2, self.eps
+            self._bind_adam()  # a no-op unless the device tables were restored (upload_epoch)
 
-            def sgd_ema():  # the EMA reads the weights the SGD launch wrote: same stream, behind it
+            def update():  # lr / decay: the CPU twin's; the kernel reads hy
+                adam.run(self.lr, self.weight_decay, b1, b2, eps, n, hy)
+        else:
+            lr, mu, wd = self.lr, self.momentum, self.weight_decay
+
+            def update():
                 sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
-                ema.update()
-            return sgd_ema
         clip, max_norm = self.clip, self.max_grad_norm
-        clip.bind([self.g])  # a no-op unless the device tables were restored (upload_epoch)
-
-        def clip_sgd():  # norm of sum g / N, arena scaled in place, then the SGD: all on one stream
-            clip.run(max_norm, n)
-            sgd_momentum_(self.x, self.g, self.buf, lr, mu, n, weight_decay=wd, hyper=hy)
-            if ema is not None:
-                ema.update()
-        return clip_sgd
-
-    def _adamw(self):
-        """This step's fused AdamW launch in the SGD launch's place: clip, AdamW, EMA on one stream."""
-        adam, n = self.adam, float(self.comm.world_size)
-        b1, b2, eps = self.beta1, self.beta2, self.eps
-        hy = self.hyper.dev if self.hyper is not None else None
-        clip, max_norm, ema = self.clip, self.max_grad_norm, self.ema
-        self._bind_adam()  # a no-op unless the device tables were restored (upload_epoch)
         if clip is not None:
-            clip.bind([self.g])
+            clip.bind([self.g])  # a no-op unless the device tables were restored (upload_epoch)
 
-        def clip_adamw_ema():
+        def clip_update_ema():
             if clip is not None:
                 clip.run(max_norm, n)
-            adam.run(self.lr, self.weight_decay, b1, b2, eps, n, hy)  # lr / decay: the CPU twin's; the kernel reads hy
-            if ema is not None:
-                ema.update()
-        return clip_adamw_ema
+            update()
+            self._after_update()  # the EMA reads the weights the update wrote: same stream, behind it
+        return clip_update_ema
 
-    def plan_hyper(self, pairs):
-        """Write the pinned source rows of the coming steps' ``(lr, weight_decay)`` ahead of time."""
-        if self.hyper is not None:
-            self.hyper.prefill(pairs)
-
-    def set_hyper(self, lr: float, weight_decay: Optional[float] = None):
-        """Learning rate and L2 weight decay of the steps from now on (fp32 values), captured replays
-        included; never called inside a capture.  On a device: one 16-byte async copy into the block,
-        none when neither value changed.
-
-        Ordering of the copy (after the previous step's SGD launch, before this step's): in stream
-        mode the SGD launch runs on the communicator's side stream — replayed, at the tail of the
-        comm graph, which is not joined with the current stream between steps — so the copy goes on
-        the side stream, behind it in stream order.  Otherwise the whole step is on the current
-        stream and so is the copy."""
-        wd = self.weight_decay if weight_decay is None else float(weight_decay)
-        assert wd >= 0, "weight_decay >= 0"
-        lr, wd = float(np.float32(lr)), float(np.float32(wd))
-        if self._captured_by_value and (lr != float(np.float32(self.lr)) or wd != 0.0):
-            raise RuntimeError("dense arm: the captured step holds lr by value; call set_hyper() before capturing")
-        self.lr, self.weight_decay = lr, wd
-        if self.hyper is not None:
-            self._hyper_on = True
-            self._upload_hyper()
-
-    def _upload_hyper(self, force: bool = False):
-        assert not capturing(), "set_hyper() inside a graph capture"
-        if self.stream_mode:
-            with self.comm.on_side():
-                self.hyper.set(self.lr, self.weight_decay, force)
-        else:
-            self.hyper.set(self.lr, self.weight_decay, force)
+    def _hyper_on_side(self) -> bool:
+        return self.stream_mode
 
     @torch.no_grad()
     def phase_sgd(self):
@@ -416,8 +357,7 @@ class BucketedDataParallel:
     def snapshot(self):
         return {"x": self.x.clone(), "buf": self.buf.clone(), "step_count": self.step_count,
                 **({"v": self.v.clone(), "adam": self.adam.snapshot()} if self.adam is not None else {}),
-                **({"clip": self.clip.snapshot()} if self.clip is not None else {}),
-                **({"ema": self.ema.snapshot()} if self.ema is not None else {})}
+                **self._snapshot_extras()}
 
     def restore(self, snap):
         self.x.copy_(snap["x"])
@@ -426,10 +366,7 @@ class BucketedDataParallel:
         if self.adam is not None:
             self.v.copy_(snap["v"])
             self.adam.restore(snap["adam"])
-        if self.clip is not None:
-            self.clip.restore(snap["clip"])
-        if self.ema is not None and "ema" in snap:
-            self.ema.restore(snap["ema"])
+        self._restore_extras(snap)
 
     def count_step(self):
         if not capturing():
@@ -454,9 +391,5 @@ class BucketedDataParallel:
         if self.adam is not None:
             self.v.copy_(sd["exp_avg_sq"])
             self.adam.write(sd)
-        self.lr = float(sd["lr"])
-        self.weight_decay = float(sd.get("weight_decay", 0.0))
         self.momentum = float(sd["momentum"])
-        if self.hyper is not None:  # the block follows the loaded values
-            self._hyper_on = self._hyper_on or self.weight_decay != 0.0
-            self._upload_hyper(force=True)
+        self._load_hyper(float(sd["lr"]), float(sd.get("weight_decay", 0.0)))

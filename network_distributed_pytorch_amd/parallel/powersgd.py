@@ -35,15 +35,15 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ..ops import SegPlan, capturing, ext, gradfinish, taps, upload, upload_epoch
-from ..ops.gradclip import GradClip
-from ..ops.hyper import HyperBlock
+from ..ops.hyper import HyperState
 from .comm import Communicator, n_bits
+from .sync import GradSync
 from ..knobs import fusion_on
 
 __all__ = [
@@ -482,7 +482,7 @@ class _Group:
         self.q_seg_fused: Optional[SegPlan] = None
 
 
-class PowerSGDOptimizer:
+class PowerSGDOptimizer(HyperState, GradSync):
     """Fused EF-SGD-with-momentum PowerSGD step (ddp_init.py:121-178) over flat arenas.
 
     Parameters are re-pointed into a flat parameter arena ``x`` (every high-rank slot 64-B
@@ -538,6 +538,8 @@ class PowerSGDOptimizer:
     to ``False`` and ``overlap=True`` / ``set_overlap(True)`` raise.
     """
 
+    _arm = "PowerSGD"
+
     def __init__(self, params, lr: float, momentum: float = 0.9, rank: int = 4,
                  random_seed: int = 714, reuse_query: bool = True,
                  comm: Optional[Communicator] = None, write_grad: bool = False,
@@ -547,13 +549,9 @@ class PowerSGDOptimizer:
         self.params: List[torch.nn.Parameter] = [p for p in params]
         assert self.params, "no parameters"
         assert weight_decay >= 0, "weight_decay >= 0"
-        assert max_grad_norm >= 0, "max_grad_norm >= 0 (0: off, inf: measure only)"
-        self.max_grad_norm = float(max_grad_norm)
-        if self.max_grad_norm > 0 and overlap:
+        if max_grad_norm > 0 and overlap:
             raise ValueError("PowerSGD: overlap=True cannot be combined with max_grad_norm > 0 (the global "
                              "norm needs every gradient before the first group's pipeline may start)")
-        self.lr = float(lr)
-        self.weight_decay = float(weight_decay)
         self.momentum = float(momentum)
         self.rank = int(rank)
         self.reuse_query = reuse_query
@@ -607,9 +605,7 @@ class PowerSGDOptimizer:
         self.native = self.buf.native
         # device block [lr, weight_decay, 0, 0], allocated before any capture; the kernels read it
         # once set_hyper() was called or a decay is on, else lr goes by value (see set_hyper)
-        self.hyper = HyperBlock(self.device, self.lr, self.weight_decay) if self.native else None
-        self._hyper_on = self.native and self.weight_decay != 0.0
-        self._captured: Optional[Tuple[bool, bool]] = None  # (block read, decay on) of a captured step
+        self._init_hyper(float(lr), float(weight_decay), block=self.native)
         # dead-tap compaction (ops/taps.py; NDP_FUSION_OFF=dead_taps): the support version the plan
         # was last compared with (None: compare at the next step)
         self.dead_taps = self.native and bool(shapes) and fusion_on("dead_taps")
@@ -627,11 +623,9 @@ class PowerSGDOptimizer:
         self._r1_key = None
         # global-norm clip of this rank's gradients (ops/gradclip.py): table, partials and the
         # {norm, coef, clipped, steps} block exist before any capture
-        self.ema = None  # ops.WeightEma updated behind the last update launch (attach_ema)
-        self.clip: Optional[GradClip] = None
-        if self.max_grad_norm > 0:
-            self.clip = GradClip(self.device, capacity=len(self.params),
-                                 blocks=sum((p.numel() + 2047) // 2048 for p in self.params))
+        self._init_clip(max_grad_norm, self.device, capacity=len(self.params),
+                        blocks=sum((p.numel() + 2047) // 2048 for p in self.params))
+        if self.clip is not None:
             overlap = False  # overlap=None resolves to the serial step
 
         # default: overlap when a step has wire time to hide (N > 1 or link emulation)
@@ -726,7 +720,7 @@ class PowerSGDOptimizer:
         p0, p1 = B.p_range(g.lo, g.hi)
         q0, q1 = B.q_range(g.lo, g.hi)
         mode, lr, mom, spins = 2 if self.write_grad else 1, self.lr, self.momentum, self.orth_max_spins
-        hy = self._hyper()
+        hy = self._hyper_arg()
 
         pp = self.p_prev if self.lazy_ef else None
 
@@ -768,8 +762,7 @@ class PowerSGDOptimizer:
                 self._r1_out.set(outs)
                 self._r1_key = key
             r1 = slice(self.r1_start, self.arena_numel)
-            lr, mom, hy = self.lr, self.momentum, self._hyper()
-            ema = self.ema
+            lr, mom, hy = self.lr, self.momentum, self._hyper_arg()
 
             def rank1():
                 self._r1_pack.run()
@@ -778,11 +771,10 @@ class PowerSGDOptimizer:
                                  self.r1_upd if self.write_grad else None, lr, mom, hyper=hy)
                 if self.write_grad:
                     self._r1_out.run()
-                if ema is not None:  # behind the step's last update launch, same side item
-                    ema.update()
+                self._after_update()  # the EMA: behind the step's last update launch, same side item
             self.comm.side_launch(rank1)
         elif self.ema is not None:
-            self.comm.side_launch(self.ema.update)
+            self.comm.side_launch(self._after_update)
         self.comm.side_join()
 
     # -- helpers -------------------------------------------------------------------------
@@ -892,20 +884,14 @@ class PowerSGDOptimizer:
         self.buf.check_orth()
         self.comm.check()
 
-    def clip_stats(self) -> Optional[Dict[str, Any]]:
-        """``{"norm", "coef", "clipped", "steps"}`` of the gradient clip (a host sync), or None when
-        ``max_grad_norm`` is 0.  The norm is this rank's own."""
-        return self.clip.read() if self.clip is not None else None
+    @property
+    def flat_weights(self) -> torch.Tensor:
+        return self.x
 
-    def attach_ema(self, ema):
-        """Keep ``ema`` (ops/ema.py) of the weights: one launch per step behind the step's last
-        update launch, on its stream.  Serial step and :meth:`phases`: the tail of
-        :meth:`phase_update`, inside the captured segment.  Overlap groups: the last side-stream
-        item, ahead of the release of the next compute graph (the table may hold BatchNorm
-        running statistics, which the next forward rewrites).  Part of :meth:`snapshot`.  None
-        detaches."""
-        assert not capturing(), "attach_ema() inside a graph capture"
-        self.ema = ema
+    # attach_ema(): the EMA launch is the tail of phase_update (serial step and phases(), inside the
+    # captured segment) or, with overlap groups, the last side-stream item, ahead of the release of
+    # the next compute graph (the table may hold BatchNorm running statistics, which the next
+    # forward rewrites)
 
     # -- the step --------------------------------------------------------------------------
     # Serial path: step() = phase_p -> comm_p -> phase_q -> comm_q -> phase_update.  The
@@ -916,9 +902,7 @@ class PowerSGDOptimizer:
         B = self.buf
         self._ensure_queries()
         grads = self._grads()
-        if self.clip is not None:  # before M = g + e: the error feedback sees the clipped gradient
-            self.clip.bind(grads)
-            self.clip.run(self.max_grad_norm)
+        self._clip_grads(grads)  # before M = g + e: the error feedback sees the clipped gradient
         if not self.native:
             return
         self._sync_supports()
@@ -950,7 +934,7 @@ class PowerSGDOptimizer:
         if self.native:
             X = ext()
             r1 = slice(self.r1_start, self.arena_numel)
-            hy = self._hyper()
+            hy = self._hyper_arg()
             if B.shapes and B.fused and self.r1_numel:  # the rank-1 step rides in the update launch
                 X.psgd_update(B.geom, B.ptrs, B.u_items, B.comm_buf, B.q_memory, float(N), B.q_warm,
                               2 if self.write_grad else 1, self.lr, self.momentum, B.max_rank,
@@ -970,8 +954,7 @@ class PowerSGDOptimizer:
                     self._r1_out.run()
         else:
             self._step_torch(N, [p.grad for p in self.params])
-        if self.ema is not None:
-            self.ema.update()
+        self._after_update()
         self.count_step()
 
     def count_step(self):
@@ -1018,58 +1001,17 @@ class PowerSGDOptimizer:
         self._reset_groups()
 
     # -- hyper-parameter block -----------------------------------------------------------------
-    def _hyper(self) -> Optional[torch.Tensor]:
-        """The ``hyper=`` argument of this step's update launches (None: lr by value, no decay)."""
-        if capturing():
-            self._captured = (self._hyper_on, self.weight_decay != 0.0)
-        return self.hyper.dev if self._hyper_on else None
+    # lr / weight_decay / hyper / _hyper_on, set_hyper() and plan_hyper(): ops/hyper.py HyperState
+    def _hyper_on_side(self) -> bool:
+        return bool(self.overlap)  # the update launches of the overlap groups run on the side stream
 
-    def plan_hyper(self, pairs):
-        """Write the pinned source rows of the coming steps' ``(lr, weight_decay)`` ahead of time."""
-        if self.hyper is not None:
-            self.hyper.prefill(pairs)
-
-    def set_hyper(self, lr: float, weight_decay: Optional[float] = None):
-        """Learning rate and L2 weight decay of the steps from now on, captured replays included.
-
-        Both are rounded to fp32 once, kept in ``self.lr`` / ``self.weight_decay`` (what the torch
-        twin uses) and, on the native path, uploaded into the device block by one 16-byte async copy
-        from a pinned row; nothing is enqueued when neither changed.  Never called inside a
-        capture.  A step captured before the first call holds ``lr`` by value, and a captured step
-        holds its dead-tap plan: changing what such a graph froze raises.
-
-        Ordering of the copy: it must follow the previous step's last update launch and precede
-        this step's first one.  Without overlap every launch of a step — eager or replayed — is on
-        the current stream, and so is the copy.  With overlap groups the update launches run on
-        the communicator's side stream; replayed, they sit at the tail of the comm graph, which is
-        launched on that stream and is not joined with the current one between steps (a device
-        flag, not the stream, releases the next compute graph), so a copy on the current stream
-        could overtake them.  The copy therefore goes on the side stream itself: stream order puts
-        it after the previous comm graph (or eager side work) and before the next."""
-        wd = self.weight_decay if weight_decay is None else float(weight_decay)
-        assert wd >= 0, "weight_decay >= 0"
-        lr, wd = float(np.float32(lr)), float(np.float32(wd))
-        if self._captured is not None:
-            block, decay = self._captured
-            if not block and (lr != float(np.float32(self.lr)) or wd != 0.0):
-                raise RuntimeError("PowerSGD: the captured step holds lr by value; call set_hyper() before capturing")
-            if decay != (wd != 0.0):
-                raise RuntimeError("PowerSGD: weight_decay cannot be switched on or off after capture (the step "
-                                   "froze its dead-tap plan); capture again")
+    def _check_hyper(self, lr: float, wd: float) -> None:
+        """A captured step holds its dead-tap plan: switching the decay on or off under it raises."""
+        if self._captured_decay is not None and self._captured_decay != (wd != 0.0):
+            raise RuntimeError("PowerSGD: weight_decay cannot be switched on or off after capture (the step "
+                               "froze its dead-tap plan); capture again")
         if (wd != 0.0) != (self.weight_decay != 0.0):
             self._taps_seen = None  # decay on: every matrix full (_wanted_supports); off: compact again
-        self.lr, self.weight_decay = lr, wd
-        if self.hyper is not None:
-            self._hyper_on = True
-            self._upload_hyper()
-
-    def _upload_hyper(self, force: bool = False):
-        assert not capturing(), "set_hyper() inside a graph capture"
-        if self.overlap:  # the update launches run on the side stream (see set_hyper)
-            with self.comm.on_side():
-                self.hyper.set(self.lr, self.weight_decay, force)
-        else:
-            self.hyper.set(self.lr, self.weight_decay, force)
 
     def _step_torch(self, N, grads):
         B = self.buf
@@ -1246,8 +1188,7 @@ class PowerSGDOptimizer:
 
     def snapshot(self):
         # e / m in the full layout: the warm-up steps between snapshot and restore may re-plan
-        return {**({"clip": self.clip.snapshot()} if self.clip is not None else {}),
-                **({"ema": self.ema.snapshot()} if self.ema is not None else {}),
+        return {**self._snapshot_extras(),
                 "x": self.x.clone(), "e": self._full_arena(self._e).clone(), "p_prev": self.p_prev.clone(),
                 "lazy_pending": self._lazy_pending, "m": self.m.clone(), "q": self.buf.q_warm.clone(),
                 "step_count": self.step_count, "bits": self.bits_communicated, "q_ready": self._q_ready,
@@ -1264,10 +1205,7 @@ class PowerSGDOptimizer:
         self.bits_communicated = snap["bits"]
         self._q_ready = snap["q_ready"]
         self.rng.set_state(snap["rng"])
-        if self.clip is not None:
-            self.clip.restore(snap["clip"])
-        if self.ema is not None and "ema" in snap:
-            self.ema.restore(snap["ema"])
+        self._restore_extras(snap)
 
     # -- checkpoint / resume ---------------------------------------------------------------
     def state_dict(self):
@@ -1300,12 +1238,8 @@ class PowerSGDOptimizer:
         self.buf.q_warm.copy_(sd["q_warm"])
         self._q_ready = bool(sd.get("q_ready", self.step_count > 0)) and self.reuse_query
         self.rng.set_state(_rng_state_from_dict(sd["rng_state"]))
-        self.lr = float(sd["lr"])
-        self.weight_decay = float(sd.get("weight_decay", 0.0))
         self.momentum = float(sd["momentum_coef"])
-        if self.hyper is not None:  # the block follows the loaded values
-            self._hyper_on = self._hyper_on or self.weight_decay != 0.0
-            self._upload_hyper(force=True)
+        self._load_hyper(float(sd["lr"]), float(sd.get("weight_decay", 0.0)))
 
 
 def _rng_state_to_dict(st):

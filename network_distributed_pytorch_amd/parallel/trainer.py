@@ -1,40 +1,15 @@
-"""Gradient-synchronisation strategies behind one interface (zero_grad / step).
+"""``build_grad_sync(kind, model, comm, ...)``: the gradient-synchronisation strategies, each a
+:class:`GradSync` (parallel/sync.py: the interface, and what every strategy has in common).
 
-``build_grad_sync(kind, model, comm, ...)``:
-
-=================  ===========================================================================
-``powersgd``       fused native engine (:class:`PowerSGDOptimizer`): EF + PowerSGD + momentum
-                   + SGD over flat arenas; on a device the per-group pipelines (6 gfx950
-                   launches + 2 collectives each) overlap backward on the side stream.
-``powersgd-ref``   reference semantics, eager per-tensor loops (ddp_init.py:149-178 with the
-                   reducer's torch path) — the "eager reference" comparison arm.
-``dense``          bucketed all-reduce overlapped with backward + fused SGD-momentum kernel.
-``dense-ref``      reference dense arm: blocking per-parameter all-reduce + torch.optim.SGD
-                   (ddp_guide_cifar10/ddp_init.py:57-62,111,124-125).
-=================  ===========================================================================
-
-Every strategy has ``set_hyper(lr, weight_decay)``: the learning rate and the L2 weight decay of
-the steps from now on (the engine calls it before every step when a schedule or a decay is on).
-The native engines forward it to their optimiser's device block, the reference loops apply it
-in torch.
-
-Every strategy takes ``max_grad_norm`` (0: off; ``inf``: measure only) and has ``clip_stats()``: the
-``{"norm", "coef", "clipped", "steps"}`` block of the global-norm gradient clip (ops/gradclip.py), or
-None when clipping is off.  The PowerSGD arms clip each rank's own gradient before the error
-feedback; the dense arms and the local optimisers clip the averaged gradient before the update.
-
-Every strategy has ``attach_ema(ema)``: an ``ops.WeightEma`` (ops/ema.py) whose ``update()`` then
-runs once per step, behind the step's last update launch and on its stream (inside a captured
-step); the native engines' ``snapshot()`` / ``restore()`` include it.  Nothing attached: every
-launch, snapshot and state dict is what it is without.
-
-``optimizer="adamw"`` (with ``betas``, ``eps``, ``decay_1d``) replaces momentum SGD by AdamW
-(ops/adamw.py) behind ``dense`` (the fused launch over the arenas), ``powersgd-ref`` / ``powersgd-api``
-(``FusedAdamW`` over the decompressed, averaged gradients; error memory and wire untouched) and
-``dense-ref`` (``torch.optim.AdamW`` with two param groups, capturable on a device); ``adam_stats()``
-returns the step count.  ``powersgd`` and the local optimisers raise: the fused update kernels step in
-the pass that decompresses and feeds back, and have no Adam variant yet.  With ``optimizer="sgd"``
-every constructor call is exactly what it is without these arguments.
+======================  =====================================================================
+``powersgd``            :class:`PowerSGDSync`: the fused native engine (parallel/powersgd.py)
+``powersgd-ref``        :class:`ReferencePowerSGDLoop`, the reducer's torch path
+``powersgd-api``        :class:`ReferencePowerSGDLoop`, the native reducer behind the reference API
+``dense``               :class:`_DenseSync`: bucketed, backward-overlapped all-reduce (parallel/ddp.py)
+``dense-ref``           :class:`ReferenceDenseLoop`: blocking per-parameter all-reduce + torch optimiser
+``local-sgd-nesterov``  :class:`LocalOptimizer`, no communication
+``local-adamw``         :class:`LocalOptimizer`, no communication
+======================  =====================================================================
 """
 from __future__ import annotations
 
@@ -43,78 +18,28 @@ from typing import Optional
 import torch
 
 from ..ops.adamw import FusedAdamW, check_adam_args
-from ..ops.gradclip import GradClip
 from .comm import Communicator
 from .ddp import BucketedDataParallel, average_gradients
 from .powersgd import PowerSGDOptimizer, PowerSGDReducer, powersgd_bytes_per_step
+from .sync import GradSync
 
 __all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "ADAMW_SYNCS"]
 
 ADAMW_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # the arms that take optimizer="adamw"
 
 
-class PowerSGDSync:
+class PowerSGDSync(PowerSGDOptimizer):
     def __init__(self, model, comm, lr, momentum, rank, seed=714, **kw):
-        self.opt = PowerSGDOptimizer(model.parameters(), lr=lr, momentum=momentum, rank=rank,
-                                     random_seed=seed, comm=comm, **kw)
-        b = powersgd_bytes_per_step(list(model.parameters()), rank)
-        self.bytes_per_step = b["total"]
+        super().__init__(model.parameters(), lr=lr, momentum=momentum, rank=rank, random_seed=seed, comm=comm, **kw)
+        self.bytes_per_step = powersgd_bytes_per_step(list(model.parameters()), rank)["total"]
 
     @property
-    def collectives_per_step(self):
-        return self.opt.collectives_per_step
-
-    @property
-    def comm(self):
-        return self.opt.comm
-
-    def collective_payloads(self):
-        return self.opt.collective_payloads()
-
-    def zero_grad(self):
-        self.opt.zero_grad()
-
-    def step(self):
-        return self.opt.step()
-
-    def set_hyper(self, lr, weight_decay=None):
-        self.opt.set_hyper(lr, weight_decay)
-
-    def plan_hyper(self, pairs):
-        self.opt.plan_hyper(pairs)
-
-    def phases(self):
-        return self.opt.phases()
-
-    def clip_stats(self):
-        return self.opt.clip_stats()
-
-    def attach_ema(self, ema):
-        self.opt.attach_ema(ema)
-
-    def count_step(self):
-        self.opt.count_step()
-
-    def prepare(self):
-        self.opt.prepare()
-
-    def snapshot(self):
-        return self.opt.snapshot()
-
-    def restore(self, snap):
-        self.opt.restore(snap)
-
-    def check_errors(self):
-        self.opt.check_errors()
-
-    def state_dict(self):
-        return self.opt.state_dict()
-
-    def load_state_dict(self, sd):
-        self.opt.load_state_dict(sd)
+    def opt(self):
+        """Compatibility name from when this class wrapped the optimiser: the object itself."""
+        return self
 
 
-class ReferencePowerSGDLoop:
+class ReferencePowerSGDLoop(GradSync):
     """Algorithm 2 exactly as the reference loop writes it (ddp_init.py:130-178)."""
 
     def __init__(self, model, comm, lr, momentum, rank, seed=714, native_reducer=False, max_grad_norm=0.0,
@@ -129,8 +54,7 @@ class ReferencePowerSGDLoop:
                                    decay_mask=[decay_1d or p.dim() > 1 for p in self.params])
         elif optimizer != "sgd":
             raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
-        self.max_grad_norm = float(max_grad_norm)
-        self.clip = _make_clip(self.max_grad_norm, self.params[0].device)
+        self._init_clip(max_grad_norm, self.params[0].device)
         self.lr, self.lam, self.weight_decay = lr, momentum, 0.0
         self.reducer = PowerSGDReducer(seed, self.params[0].device, 0, True, rank=rank, comm=comm)
         self.native_reducer = native_reducer
@@ -143,13 +67,9 @@ class ReferencePowerSGDLoop:
         self.bytes_per_step = b["total"]
         self._payloads = [b["p"], b["rank1"], b["q"]]  # reducer.py:126, :132, :145
         self.collectives_per_step = 3 if comm.active else 0
-        self.ema = None
 
     def collective_payloads(self):
         return list(self._payloads)
-
-    def attach_ema(self, ema):
-        self.ema = ema
 
     def zero_grad(self):
         for p in self.params:
@@ -168,7 +88,7 @@ class ReferencePowerSGDLoop:
     @torch.no_grad()
     def step(self):
         grads = [p.grad for p in self.params]
-        _clip(self.clip, self.max_grad_norm, grads)  # this rank's own gradient, before s = g + e
+        self._clip_grads(grads)  # this rank's own gradient, before s = g + e
         for g, e, s in zip(grads, self.memories, self.send_buffers):
             s.data[:] = g + e
         if self.native_reducer:
@@ -178,8 +98,7 @@ class ReferencePowerSGDLoop:
         if self.adam is not None:  # decoupled decay, moments and the step in one launch (twin on CPU)
             self.adam.bind(grads)
             self.adam.step()
-            if self.ema is not None:
-                self.ema.update()
+            self._after_update()
             return self.bytes_per_step * 8
         if self.weight_decay != 0.0:  # L2 on the decompressed gradient: never in the memory or on the wire
             for p, g in zip(self.params, grads):
@@ -193,21 +112,16 @@ class ReferencePowerSGDLoop:
         self.first = False
         for p, g in zip(self.params, grads):
             p.data.add_(g, alpha=-self.lr)
-        if self.ema is not None:
-            self.ema.update()
+        self._after_update()
         return self.bytes_per_step * 8
 
-    def clip_stats(self):
-        return self.clip.read() if self.clip is not None else None
 
-
-class ReferenceDenseLoop:
+class ReferenceDenseLoop(GradSync):
     def __init__(self, model, comm, lr, momentum, max_grad_norm=0.0, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8,
                  decay_1d=True):
         self.model = model
         self.comm = comm
-        self.max_grad_norm = float(max_grad_norm)
-        self.clip = _make_clip(self.max_grad_norm, next(model.parameters()).device)
+        self._init_clip(max_grad_norm, next(model.parameters()).device)
         self.optimizer = optimizer
         if optimizer == "adamw":
             # torch.optim.AdamW with two param groups: the reference-semantics comparison arm
@@ -225,13 +139,9 @@ class ReferenceDenseLoop:
         self.bytes_per_step = 4 * sum(p.numel() for p in model.parameters())
         self._payloads = [4 * p.numel() for p in model.parameters()]  # ddp_init.py:61, one per param
         self.collectives_per_step = len(list(model.parameters())) if comm.active else 0
-        self.ema = None
 
     def collective_payloads(self):
         return list(self._payloads)
-
-    def attach_ema(self, ema):
-        self.ema = ema
 
     def zero_grad(self):
         self.opt.zero_grad()
@@ -247,87 +157,22 @@ class ReferenceDenseLoop:
 
     def step(self):
         bits = average_gradients(self.model, self.comm)
-        _clip(self.clip, self.max_grad_norm, [p.grad for p in self.model.parameters()])
+        self._clip_grads([p.grad for p in self.model.parameters()])
         self.opt.step()
-        if self.ema is not None:
-            self.ema.update()
+        self._after_update()
         return bits
 
-    def clip_stats(self):
-        return self.clip.read() if self.clip is not None else None
 
-
-class _DenseSync:
+class _DenseSync(BucketedDataParallel):
     def __init__(self, model, comm, lr, momentum, bucket_mb, overlap=None, max_grad_norm=0.0, **adam):
         # adam: optimizer / betas / eps / decay_1d, only when the optimiser is not SGD
-        self.ddp = BucketedDataParallel(model, comm, lr=lr, momentum=momentum, bucket_mb=bucket_mb, overlap=overlap,
-                                        max_grad_norm=max_grad_norm, **adam)
-        self.bytes_per_step = self.ddp.bytes_per_step
-
-    def adam_stats(self):
-        return self.ddp.adam_stats()
+        super().__init__(model, comm, lr=lr, momentum=momentum, bucket_mb=bucket_mb, overlap=overlap,
+                         max_grad_norm=max_grad_norm, **adam)
 
     @property
-    def collectives_per_step(self):
-        return self.ddp.collectives_per_step
-
-    @property
-    def comm(self):
-        return self.ddp.comm
-
-    def collective_payloads(self):
-        return self.ddp.collective_payloads()
-
-    def snapshot(self):
-        return self.ddp.snapshot()
-
-    def restore(self, snap):
-        self.ddp.restore(snap)
-
-    def check_errors(self):
-        self.ddp.comm.check()
-
-    def zero_grad(self):
-        self.ddp.zero_grad()
-
-    def step(self):
-        return self.ddp.step()
-
-    def set_hyper(self, lr, weight_decay=None):
-        self.ddp.set_hyper(lr, weight_decay)
-
-    def plan_hyper(self, pairs):
-        self.ddp.plan_hyper(pairs)
-
-    def phases(self):
-        return self.ddp.phases()
-
-    def clip_stats(self):
-        return self.ddp.clip_stats()
-
-    def attach_ema(self, ema):
-        self.ddp.attach_ema(ema)
-
-    def count_step(self):
-        self.ddp.count_step()
-
-    def state_dict(self):
-        return self.ddp.state_dict()
-
-    def load_state_dict(self, sd):
-        self.ddp.load_state_dict(sd)
-
-
-def _make_clip(max_grad_norm, device) -> Optional[GradClip]:
-    assert max_grad_norm >= 0, "max_grad_norm >= 0 (0: off, inf: measure only)"
-    return GradClip(device) if max_grad_norm > 0 else None
-
-
-def _clip(clip: Optional[GradClip], max_grad_norm, grads):
-    """Clip ``grads`` in place by their global norm (device kernels or the torch twin)."""
-    if clip is not None:
-        clip.bind([g for g in grads if g is not None])
-        clip.run(max_grad_norm)
+    def ddp(self):
+        """Compatibility name from when this class wrapped the data-parallel engine: the object itself."""
+        return self
 
 
 def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
@@ -368,7 +213,7 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
     raise ValueError(f"unknown grad sync {kind!r}")
 
 
-class LocalOptimizer:
+class LocalOptimizer(GradSync):
     """Single-GPU baselines, no communication (reference C17):
     ``local-sgd-nesterov`` = SGD(lr, momentum=0.9, nesterov=True)
     (ddp_powersgd_distillBERT_IMDb/IMDb_distillBERT_example.py:57);
@@ -376,18 +221,11 @@ class LocalOptimizer:
 
     def __init__(self, model, kind, lr, momentum, max_grad_norm=0.0):
         self.model = model
-        self.max_grad_norm = float(max_grad_norm)
-        self.clip = _make_clip(self.max_grad_norm, next(model.parameters()).device)
+        self._init_clip(max_grad_norm, next(model.parameters()).device)
         if kind == "local-adamw":
             self.opt = torch.optim.AdamW(model.parameters(), lr=lr)
         else:
             self.opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=momentum, nesterov=True)
-        self.bytes_per_step = 0
-        self.collectives_per_step = 0
-        self.ema = None
-
-    def attach_ema(self, ema):
-        self.ema = ema
 
     def zero_grad(self):
         self.opt.zero_grad()
@@ -396,14 +234,10 @@ class LocalOptimizer:
         _set_param_groups(self.opt, lr, weight_decay)
 
     def step(self):
-        _clip(self.clip, self.max_grad_norm, [p.grad for p in self.model.parameters()])
+        self._clip_grads([p.grad for p in self.model.parameters()])
         self.opt.step()
-        if self.ema is not None:
-            self.ema.update()
+        self._after_update()
         return 0
-
-    def clip_stats(self):
-        return self.clip.read() if self.clip is not None else None
 
     def state_dict(self):
         return self.opt.state_dict()

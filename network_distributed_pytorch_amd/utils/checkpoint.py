@@ -72,7 +72,7 @@ def save_checkpoint(path: str, model: torch.nn.Module, sync=None, epoch: int = 0
     """``ema``: ``WeightEma.state_dict(names)``, stored under ``"ema"`` in the rank-0 file."""
     rank = get_rank() if rank is None else rank
     world = world_size() if world is None else world
-    sync_state = sync.state_dict() if sync is not None and hasattr(sync, "state_dict") else None
+    sync_state = sync.state_dict() if sync is not None else None  # a GradSync; None: it keeps no state
     _atomic_save({"format": FORMAT, "rank": int(rank), "world": int(world), "sync": sync_state,
                   "epoch": int(epoch), "step": int(step), **_rng_state()}, rank_file(path, rank))
     if rank != 0:
@@ -120,7 +120,7 @@ def load_checkpoint(path: str, model: torch.nn.Module, sync=None, strict: bool =
                           "per-rank error memories restart from rank 0's")
     elif world > 1:
         warnings.warn(f"{rf} missing: rank {rank} resumes with rank 0's gradient-sync state")
-    if sync is not None and local.get("sync") is not None and hasattr(sync, "load_state_dict"):
+    if sync is not None and local.get("sync") is not None:
         sync.load_state_dict(local["sync"])
     _set_rng(local)
     if ema is not None:

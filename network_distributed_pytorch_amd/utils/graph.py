@@ -53,6 +53,7 @@ import torch.distributed as dist
 
 from ..ops import _UPLOADS, ext
 from ..parallel.comm import world_size
+from ..parallel.sync import GradSync
 from ..knobs import fusion_on
 
 # NDP_FUSION_OFF=defer_uploads: capture-time table uploads stay memcpy nodes re-run on every replay
@@ -267,10 +268,7 @@ class GraphedStep(StepRunner):
     """Back-compat: capture one closure (full mode)."""
 
     def __init__(self, fn: Callable[[], None], warmup: int = 3, enabled: bool = True):
-        class _NoSync:
+        class _NoSync(GradSync):
             def step(self):
                 pass
-
-            def phases(self):
-                return []
         super().__init__(fn, _NoSync(), mode="full" if enabled else "none", warmup=warmup)
