@@ -1133,12 +1133,22 @@ py::tuple tg_plan(const std::vector<int64_t>& geom, int64_t B) {
 }
 
 // the GEMM description tgemm launches for (geom, B, dir) — host-side, for the CPU emulation
-// test of the index algebra (tests/test_tgemm_cpu.py)
-py::dict tg_describe(const std::vector<int64_t>& geom, int64_t B, int64_t dir) {
+// test of the index algebra (tests/test_tgemm_cpu.py) — and the kernel instance and slab count
+// run() launches when the A / B base pointers sit a_misalign / b_misalign bytes past a 16-B
+// boundary (tests/tg_cases.py): akf, bnf, wa, wb name tgemm_kernel<64,64,32, AKF, BNF, WA, WB, 2>
+py::dict tg_describe(const std::vector<int64_t>& geom, int64_t B, int64_t dir, int64_t a_misalign,
+                     int64_t b_misalign) {
   const ndp::ConvGeom g = conv_geom(geom);
   TORCH_CHECK(ndp::tg_class(g) >= 0, "tg_describe: no tgemm path");
+  TORCH_CHECK(dir >= 0 && dir <= 2, "tg_describe: dir 0 (forward), 1 (grad-x) or 2 (grad-W)");
+  TORCH_CHECK(a_misalign >= 0 && a_misalign < 16 && b_misalign >= 0 && b_misalign < 16,
+              "tg_describe: misalignment is the base pointer modulo 16");
   bool akf = false, bnf = false;
-  const ndp::TgArgs a = ndp::tg_args(g, (int)B, (int)dir, &akf, &bnf);
+  ndp::TgArgs a = ndp::tg_args(g, (int)B, (int)dir, &akf, &bnf);
+  // never dereferenced: tg_launch reads the low 4 bits only
+  a.a = reinterpret_cast<const float*>(static_cast<uintptr_t>(a_misalign));
+  a.b = reinterpret_cast<const float*>(static_cast<uintptr_t>(b_misalign));
+  const ndp::TgLaunch l = ndp::tg_launch(a, akf, bnf, ndp::tg_splits(g, (int)B, (int)dir));
   auto idx = [](const ndp::TgIndex& t) { return py::make_tuple(t.so, t.si, t.sh); };
   py::dict d;
   d["am"] = idx(a.am); d["ak"] = idx(a.ak); d["bk"] = idx(a.bk); d["bn"] = idx(a.bn);
@@ -1146,7 +1156,21 @@ py::dict tg_describe(const std::vector<int64_t>& geom, int64_t B, int64_t dir) {
   d["M"] = a.M; d["N"] = a.N; d["K"] = a.K; d["slab"] = a.slab;
   d["akf"] = akf; d["bnf"] = bnf;
   d["splits"] = ndp::tg_splits(g, (int)B, (int)dir);
+  d["wa"] = l.wa; d["wb"] = l.wb; d["slabs"] = l.slabs; d["kchunk"] = l.kchunk;
   return d;
+}
+
+// Split-K slabs that this launch sums itself are added by float4 stores (conv_slab_sum_kernel):
+// the tensor they are summed into must then start on a 16-B boundary.  Slabs left to the
+// consumer (deferred == defer without an addend) and single-split launches store scalars.
+static void tg_check_out(const torch::Tensor& out, const char* name, const ndp::ConvGeom& g, int B, int dir,
+                         bool deferred, const char* who) {
+  bool akf = false, bnf = false;
+  const ndp::TgArgs a = ndp::tg_args(g, B, dir, &akf, &bnf);
+  const int slabs = ndp::tg_launch(a, akf, bnf, ndp::tg_splits(g, B, dir)).slabs;
+  if (slabs <= 1 || deferred) return;
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) & 15) == 0, who, ": 16-B aligned ", name,
+              " (", slabs, " split-K slabs are summed into it)");
 }
 
 static int tg_batch(const torch::Tensor& t, const ndp::ConvGeom& g, const char* who) {
@@ -1174,6 +1198,7 @@ int64_t tg_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor y, const std::vec
   conv_check(w, "w", g.Co, g.C, g.KH, g.KW);
   conv_check(y, "y", B, g.Co, g.OH, g.OW);
   float* pp = tg_part(part, ndp::tg_splits(g, B, 0), y.numel(), "tg_fwd");
+  tg_check_out(y, "y", g, B, 0, defer, "tg_fwd");
   const int left = ndp::launch_tg_fwd(x.data_ptr<float>(), w.data_ptr<float>(), y.data_ptr<float>(), B, g, pp,
                                       cur_stream(), defer);
   check_launch("launch_tg_fwd");
@@ -1194,6 +1219,7 @@ int64_t tg_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, const std:
     TORCH_CHECK((reinterpret_cast<uintptr_t>(addend->data_ptr()) & 15) == 0, "tg_dgrad: 16-B aligned addend");
     ap = addend->data_ptr<float>();
   }
+  tg_check_out(dx, "dx", g, B, 1, defer && ap == nullptr, "tg_dgrad");
   const int left = ndp::launch_tg_dgrad(dy.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), B, g, pp,
                                         cur_stream(), ap, defer);
   check_launch("launch_tg_dgrad");
@@ -1211,6 +1237,7 @@ int64_t tg_wgrad(torch::Tensor x, torch::Tensor dy, torch::Tensor out, const std
   const int64_t n = (int64_t)g.Co * g.C;
   TORCH_CHECK(out.numel() == n, "tg_wgrad: out must hold ", n, " floats");
   float* pp = tg_part(part, ndp::tg_splits(g, B, 2), n, "tg_wgrad");
+  tg_check_out(out, "out", g, B, 2, defer, "tg_wgrad");
   const int left = ndp::launch_tg_wgrad(x.data_ptr<float>(), dy.data_ptr<float>(), out.data_ptr<float>(), B, g, pp,
                                         cur_stream(), defer);
   check_launch("launch_tg_wgrad");
@@ -1886,7 +1913,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     check_launch("conv_flush_pending");
   });
   m.def("tg_plan", &tg_plan);
-  m.def("tg_describe", &tg_describe);
+  m.def("tg_describe", &tg_describe, py::arg("geom"), py::arg("B"), py::arg("dir"), py::arg("a_misalign") = 0,
+        py::arg("b_misalign") = 0);
   m.def("tg_fwd", &tg_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("geom"), py::arg("part") = py::none(),
         py::arg("defer") = false);
   m.def("tg_dgrad", &tg_dgrad, py::arg("dy"), py::arg("w"), py::arg("dx"), py::arg("geom"),

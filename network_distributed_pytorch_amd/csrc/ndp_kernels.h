@@ -596,6 +596,13 @@ int tg_class(const ConvGeom& g);
 TgArgs tg_args(const ConvGeom& g, int B, int dir, bool* akf, bool* bnf);
 // split-K slabs of direction dir (0 fwd, 1 grad-x, 2 grad-W) for batch B (1 = no scratch)
 int tg_splits(const ConvGeom& g, int B, int dir);
+// what run() launches for a described GEMM and `splits` allotted slabs: the load widths of A / B
+// (4 = 16-B loads; only the 16-B alignment of a.a / a.b is read), the k range of one split and
+// the slabs left after rounding it to whole k-tiles (<= splits)
+struct TgLaunch {
+  int wa, wb, slabs, kchunk;
+};
+TgLaunch tg_launch(const TgArgs& a, bool akf, bool bnf, int splits);
 // defer: leave the split-K slabs in part and return their count (1 = y / dx final)
 int launch_tg_fwd(const float* x, const float* w, float* y, int B, const ConvGeom& g, float* part, hipStream_t s,
                   bool defer = false);

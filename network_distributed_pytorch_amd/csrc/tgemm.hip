@@ -359,15 +359,12 @@ void launch_tile(const TgArgs& a, bool akf, bool bnf, bool va, bool vb, dim3 gri
 // returns the number of split-K slabs left in a.part (defer), or 1 when final_out is written
 int run(TgArgs a, bool akf, bool bnf, int splits, float* final_out, hipStream_t s, bool defer = false) {
   const TgTile tile = tg_tile(a.M, a.N);
-  const int ktiles = (a.K + tile.bk - 1) / tile.bk;
-  const int per = (ktiles + splits - 1) / splits;
-  a.kchunk = per * tile.bk;
-  splits = (ktiles + per - 1) / per;
+  const TgLaunch l = tg_launch(a, akf, bnf, splits);
+  a.kchunk = l.kchunk;
+  splits = l.slabs;
   if (splits <= 1) a.part = nullptr;
   const dim3 grid((a.N + tile.bn - 1) / tile.bn, (a.M + tile.bm - 1) / tile.bm, splits);
-  const bool va = vec_ok(akf ? a.ak : a.am, akf ? a.am : a.ak, a.a, akf ? a.K : a.M);
-  const bool vb = vec_ok(bnf ? a.bn : a.bk, bnf ? a.bk : a.bn, a.b, bnf ? a.N : a.K);
-  launch_tile<kTile64.bm, kTile64.bn, kTile64.bk, 2>(a, akf, bnf, va, vb, grid, s);
+  launch_tile<kTile64.bm, kTile64.bn, kTile64.bk, 2>(a, akf, bnf, l.wa == 4, l.wb == 4, grid, s);
   if (splits <= 1) return 1;
   if (defer && a.addend == nullptr) return splits;  // the consumer (fused BN, gradfinish) sums them
   launch_slab_sum(a.part, final_out, a.slab, splits, s, a.addend);
@@ -375,6 +372,15 @@ int run(TgArgs a, bool akf, bool bnf, int splits, float* final_out, hipStream_t 
 }
 
 }  // namespace
+
+TgLaunch tg_launch(const TgArgs& a, bool akf, bool bnf, int splits) {
+  const TgTile tile = tg_tile(a.M, a.N);
+  const int ktiles = (a.K + tile.bk - 1) / tile.bk;
+  const int per = (ktiles + splits - 1) / splits;
+  const bool va = vec_ok(akf ? a.ak : a.am, akf ? a.am : a.ak, a.a, akf ? a.K : a.M);
+  const bool vb = vec_ok(bnf ? a.bn : a.bk, bnf ? a.bk : a.bn, a.b, bnf ? a.N : a.K);
+  return TgLaunch{va ? 4 : 1, vb ? 4 : 1, (ktiles + per - 1) / per, per * tile.bk};
+}
 
 int tg_class(const ConvGeom& g) {
   const int hw = g.H * g.W;

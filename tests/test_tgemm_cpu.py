@@ -15,6 +15,15 @@ CASES = [
     (2, 6, 2, 2, 4, 1, 1, 0),     # pointwise, 2x2
     (3, 7, 16, 16, 5, 1, 1, 0),   # pointwise, 16x16
 ]
+# 2-pixel maps: no operand index of x / dy is unit-stride over >= 4 elements, so the loads walk the
+# channel index instead (stride 2: slow but correct) and _coalesced does not hold
+CASES_2PX = [
+    (2, 8, 1, 2, 4, 1, 1, 0),     # pointwise, 1x2
+    (2, 6, 2, 1, 4, 1, 1, 0),     # pointwise, 2x1, C % 4 != 0
+]
+CASES_NEW = CASES_2PX + [
+    (4, 18, 4, 4, 20, 1, 1, 0),   # pointwise, 4x4, C % 4 != 0
+]
 
 
 def _off(idx, i):
@@ -41,7 +50,7 @@ def _coalesced(d):
     return a_ok and b_ok
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + CASES_NEW)
 def test_tgemm_index_algebra(case):
     from network_distributed_pytorch_amd.ops import ext
 
@@ -64,8 +73,13 @@ def test_tgemm_index_algebra(case):
     out, _, _ = _emulate(d2, dy.reshape(-1), x.reshape(-1), w.numel())
     assert torch.allclose(out, dw_ref.reshape(-1), atol=1e-10), "grad-W"
     for d in (d0, d1, d2):
-        assert _coalesced(d), d
+        if case not in CASES_2PX:
+            assert _coalesced(d), d
         assert d["splits"] >= 1
+    if case in CASES_2PX:  # the mappings of tg_args for maps below 4 pixels
+        assert (d0["akf"], d0["bnf"]) == (True, False)
+        assert (d1["akf"], d1["bnf"]) == (False, False)
+        assert (d2["akf"], d2["bnf"]) == (False, False)
 
 
 def test_tgemm_small_maps_not_covered():
