@@ -25,6 +25,8 @@
 //   Consequences: g = m = v = 0 leaves x1 as it is (the dense arena's zero padding stays zero, and
 //   with wd == 0 a -0 in x survives); NaN and inf propagate as in the torch twin (ops/adamw.py).
 //
+//   The per-element lines are adamw_elem (adamw_elem.h), which the PowerSGD update kernels that
+//   step with AdamW (powersgd.hip) share.
 //   Contraction and rounding.  The build uses -ffp-contract=fast: every product that feeds an add
 //   or a subtract passes an empty asm (the ema.hip / image_batch.hip idiom) and is never contracted.
 //   The divisions are __fdiv_rn, IEEE under hipcc's default correctly rounded divide / sqrt.  The
@@ -55,43 +57,12 @@
 //   elements of g, x, m, v) are half of the VGPRs.
 #include <hip/hip_runtime.h>
 
+#include "adamw_elem.h"
 #include "arrival.h"
 #include "ndp_kernels.h"
 #include "seg_block.h"
 
 namespace ndp {
-
-// the launch's scalars, wave-uniform
-struct AdamScalars {
-  float beta1, beta2, om1, om2, ss, sb, eps, c, div;
-  bool scale, decay;
-};
-
-// one element of the rule; every product that feeds an add or a subtract passes an empty asm
-__device__ __forceinline__ void adamw_elem(float& x, float g, float& m, float& v, const AdamScalars& S) {
-  const float gg = S.scale ? __fdiv_rn(g, S.div) : g;
-  float x1 = x;
-  if (S.decay) x1 = __fmul_rn(x, S.c);
-  asm volatile("" : "+v"(x1));
-  float a = __fmul_rn(S.beta1, m);
-  float b = __fmul_rn(S.om1, gg);
-  asm volatile("" : "+v"(a));
-  asm volatile("" : "+v"(b));
-  const float mn = __fadd_rn(a, b);
-  float g2 = __fmul_rn(gg, gg);
-  asm volatile("" : "+v"(g2));
-  float d = __fmul_rn(S.beta2, v);
-  float e = __fmul_rn(S.om2, g2);
-  asm volatile("" : "+v"(d));
-  asm volatile("" : "+v"(e));
-  const float vn = __fadd_rn(d, e);
-  const float den = __fadd_rn(__fdiv_rn(__builtin_sqrtf(vn), S.sb), S.eps);
-  float u = __fmul_rn(S.ss, __fdiv_rn(mn, den));
-  asm volatile("" : "+v"(u));
-  x = __fsub_rn(x1, u);
-  m = mn;
-  v = vn;
-}
 
 __global__ __launch_bounds__(256) void adamw_step_kernel(const SegEntry* __restrict__ ents,
                                                          const int64_t* __restrict__ prefix, int n_ent,

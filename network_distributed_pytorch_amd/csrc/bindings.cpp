@@ -370,6 +370,115 @@ T* block4_ptr(const torch::Tensor& t, const char* who) {
   return reinterpret_cast<T*>(t.data_ptr<int32_t>());
 }
 
+// the Adam arguments the two PowerSGD AdamW launches share: hyper / block / tickets present and large
+// enough for `grid` workgroups, betas in [0, 1), eps > 0, and [mom_ptr, mom_ptr + n) as well as its
+// image v_delta elements further both inside `moments` (= [m | v], one tensor)
+ndp::AdamArgs adam_args(const char* who, const OptT& hyper, const OptT& block, const OptT& ctr, int64_t grid,
+                        const torch::Tensor& moments, int64_t v_delta, double beta1, double beta2, double eps,
+                        bool decay_1d, bool advance) {
+  TORCH_CHECK(hyper.has_value(), who, ": the hyper block [lr, weight_decay, 0, 0] is required (lr and wd never go by value)");
+  TORCH_CHECK(block.has_value(), who, ": the AdamBlock is required");
+  TORCH_CHECK(ctr.has_value(), who, ": the arrival tickets are required");
+  check_f32(moments, "moments");
+  TORCH_CHECK(v_delta > 0 && v_delta <= moments.numel() / 2, who, ": v_delta must lie in (0, moments.numel() / 2]");
+  TORCH_CHECK(v_delta % 4 == 0, who, ": v_delta must be a multiple of 4 (v is as far past 16 bytes as m: MatGeom.vec covers it)");
+  TORCH_CHECK((float)beta1 >= 0.0f && (float)beta1 < 1.0f && (float)beta2 >= 0.0f && (float)beta2 < 1.0f, who,
+              ": betas must be in [0, 1)");
+  TORCH_CHECK((float)eps > 0.0f, who, ": eps must be > 0 as fp32");
+  ndp::AdamArgs a{};
+  a.block = block4_ptr<ndp::AdamBlock>(*block, who);
+  a.ctr = ticket_ptr(*ctr, grid, who);
+  a.v_delta = v_delta;
+  a.beta1 = (float)beta1, a.beta2 = (float)beta2, a.eps = (float)eps;
+  a.decay_1d = decay_1d ? 1 : 0;
+  a.advance = advance ? 1 : 0;
+  return a;
+}
+// a rank-1 moment slice: inside the m half of `moments`, so that its v image is inside the tensor too
+void check_r1_moments(const char* who, const torch::Tensor& r1_mom, const torch::Tensor& moments, int64_t v_delta) {
+  const float* lo = moments.data_ptr<float>();
+  const float* p = r1_mom.data_ptr<float>();
+  TORCH_CHECK(p >= lo && p + r1_mom.numel() <= lo + moments.numel() - v_delta, who,
+              ": the rank-1 moments (and their image v_delta further) must lie inside the moment tensor");
+}
+
+// psgd_update with the AdamW element rule (powersgd.hip psgd_update_adam_wide_kernel; ndp_kernels.h
+// AdamArgs).  geom_host: the plan's host geometry (build_plan "geom"), checked here without a sync:
+// every rank <= 16 and no dead-tap compacted matrix.  moments = [m | v]: MatPtrs.mom / r1_mom point into
+// its first half and v lies v_delta elements further.  No allocation, no sync: capture-safe.
+void psgd_update_adam(torch::Tensor geom, torch::Tensor ptrs, torch::Tensor items, torch::Tensor p_hat,
+                      torch::Tensor q_sum, double q_div, OptT q_warm, int mode, int max_rank, torch::Tensor geom_host,
+                      OptT hyper, OptT block, OptT ctr, torch::Tensor moments, int64_t v_delta, double beta1,
+                      double beta2, double eps, bool decay_1d, bool advance, OptT p_prev, OptT r1_buf, double r1_div,
+                      OptT r1_mom, OptT r1_x, OptT r1_g) {
+  const char* who = "psgd_update_adam";
+  check_dev(geom, "geom"); check_dev(ptrs, "ptrs"); check_dev(items, "items");
+  check_f32(p_hat, "p_hat"); check_f32(q_sum, "q_sum");
+  TORCH_CHECK(mode == 1 || mode == 2, who, ": modes 1 / 2 only (0 and 3 are psgd_update's)");
+  TORCH_CHECK(max_rank >= 1 && max_rank <= ndp::kUWideMaxRank, who, ": plan rank <= 16 only (the wide update tile)");
+  TORCH_CHECK(!geom_host.is_cuda() && geom_host.scalar_type() == torch::kUInt8 && geom_host.is_contiguous() &&
+                  geom_host.numel() % (int64_t)sizeof(MatGeom) == 0 && geom_host.numel() <= geom.numel(),
+              who, ": geom_host is the plan's host geometry (uint8, CPU)");
+  const int64_t n_mats = geom_host.numel() / (int64_t)sizeof(MatGeom);
+  const MatGeom* gh = reinterpret_cast<const MatGeom*>(geom_host.data_ptr());
+  for (int64_t i = 0; i < n_mats; ++i) {
+    TORCH_CHECK(gh[i].tap_T == 0, who, ": matrix ", i, " is dead-tap compacted; the Adam update needs the full layout");
+    TORCH_CHECK(gh[i].r <= ndp::kUWideMaxRank, who, ": matrix ", i, " has rank ", gh[i].r, " > 16");
+  }
+  const int n_items = (int)n_of(items, sizeof(UItem));
+  TORCH_CHECK(n_items == 0 || n_mats > 0, who, ": items without geometry");
+  float* qw = nullptr;
+  if (q_warm.has_value()) { check_f32(*q_warm, "q_warm"); qw = q_warm->data_ptr<float>(); }
+  float* pp = nullptr;
+  if (p_prev.has_value()) { check_f32(*p_prev, "p_prev"); pp = p_prev->data_ptr<float>(); }
+  ndp::R1Step r1{};
+  if (r1_buf.has_value()) {  // the rank-1 group's step rides in the same launch
+    TORCH_CHECK(r1_mom.has_value() && r1_x.has_value(), who, ": rank-1 step needs mom and x");
+    check_f32(*r1_buf, "r1_buf"); check_f32(*r1_mom, "r1_mom"); check_f32(*r1_x, "r1_x");
+    TORCH_CHECK(r1_buf->numel() == r1_mom->numel() && r1_buf->numel() == r1_x->numel(), "rank-1 size mismatch");
+    r1.buf = r1_buf->data_ptr<float>();
+    r1.mom = r1_mom->data_ptr<float>();
+    r1.x = r1_x->data_ptr<float>();
+    if (r1_g.has_value()) {
+      check_f32(*r1_g, "r1_g");
+      TORCH_CHECK(r1_g->numel() == r1_buf->numel(), "rank-1 size mismatch");
+      r1.g = r1_g->data_ptr<float>();
+    }
+    r1.n = r1_buf->numel();
+    r1.div = (float)r1_div;
+  }
+  const ndp::AdamArgs a = adam_args(who, hyper, block, ctr, ndp::psgd_update_adam_grid(n_items, r1.n), moments, v_delta,
+                                    beta1, beta2, eps, decay_1d, advance);
+  if (r1.n > 0) check_r1_moments(who, *r1_mom, moments, v_delta);
+  ndp::launch_psgd_update_adam(reinterpret_cast<const MatGeom*>(geom.data_ptr()),
+                               reinterpret_cast<const MatPtrs*>(ptrs.data_ptr()),
+                               reinterpret_cast<const UItem*>(items.data_ptr()), n_items, p_hat.data_ptr<float>(),
+                               q_sum.data_ptr<float>(), (float)q_div, qw, mode, max_rank, cur_stream(), pp, r1,
+                               hyper_ptr(hyper), a);
+  check_launch("launch_psgd_update_adam");
+}
+
+// the <=1-D group's AdamW step alone (powersgd.hip rank1_adam_step_kernel): gg = buf / div
+void rank1_adam_step(torch::Tensor buf, double div, torch::Tensor mom, torch::Tensor x, OptT g, OptT hyper, OptT block,
+                     OptT ctr, torch::Tensor moments, int64_t v_delta, double beta1, double beta2, double eps,
+                     bool decay_1d, bool advance) {
+  const char* who = "rank1_adam_step";
+  check_f32(buf, "buf"); check_f32(mom, "mom"); check_f32(x, "x");
+  TORCH_CHECK(buf.numel() == mom.numel() && buf.numel() == x.numel(), "rank1_adam_step size mismatch");
+  float* gp = nullptr;
+  if (g.has_value()) {
+    check_f32(*g, "g");
+    TORCH_CHECK(g->numel() == buf.numel(), "rank1_adam_step size mismatch");
+    gp = g->data_ptr<float>();
+  }
+  const ndp::AdamArgs a = adam_args(who, hyper, block, ctr, ndp::rank1_adam_grid(buf.numel()), moments, v_delta, beta1,
+                                    beta2, eps, decay_1d, advance);
+  if (buf.numel() > 0) check_r1_moments(who, mom, moments, v_delta);
+  ndp::launch_rank1_adam_step(buf.data_ptr<float>(), (float)div, mom.data_ptr<float>(), x.data_ptr<float>(), gp,
+                              buf.numel(), cur_stream(), hyper_ptr(hyper), a);
+  check_launch("launch_rank1_adam_step");
+}
+
 void seg_reduce(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks) {
   const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "seg_reduce");
   ndp::launch_seg_reduce(t.entries, t.prefix, t.n_entries, t.n_blocks, cur_stream());
@@ -1824,6 +1933,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hyper") = OptT());
   m.def("rank1_step", &rank1_step, py::arg("buf"), py::arg("div"), py::arg("mom"), py::arg("x"), py::arg("g"),
         py::arg("lr"), py::arg("momentum"), py::arg("hyper") = OptT());
+  m.def("psgd_update_adam", &psgd_update_adam, py::arg("geom"), py::arg("ptrs"), py::arg("items"), py::arg("p_hat"),
+        py::arg("q_sum"), py::arg("q_div"), py::arg("q_warm"), py::arg("mode"), py::arg("max_rank"),
+        py::arg("geom_host"), py::arg("hyper"), py::arg("block"), py::arg("ctr"), py::arg("moments"),
+        py::arg("v_delta"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("decay_1d"),
+        py::arg("advance"), py::arg("p_prev") = OptT(), py::arg("r1_buf") = OptT(), py::arg("r1_div") = 1.0,
+        py::arg("r1_mom") = OptT(), py::arg("r1_x") = OptT(), py::arg("r1_g") = OptT());
+  m.def("rank1_adam_step", &rank1_adam_step, py::arg("buf"), py::arg("div"), py::arg("mom"), py::arg("x"),
+        py::arg("g"), py::arg("hyper"), py::arg("block"), py::arg("ctr"), py::arg("moments"), py::arg("v_delta"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("decay_1d"), py::arg("advance"));
+  m.def("psgd_update_adam_grid", &ndp::psgd_update_adam_grid);
+  m.def("rank1_adam_grid", &ndp::rank1_adam_grid);
   m.def("seg_reduce", &seg_reduce);
   m.def("sgd_momentum", &sgd_momentum, py::arg("x"), py::arg("g"), py::arg("buf"), py::arg("lr"), py::arg("mu"),
         py::arg("div"), py::arg("hyper") = OptT());

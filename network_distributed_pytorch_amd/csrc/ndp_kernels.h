@@ -373,6 +373,32 @@ constexpr int kAdamNoDecay = 1;  // SegEntry.pad bit: the entry takes no weight 
 void launch_adamw_step(const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
                        unsigned* ctr, AdamBlock* block, const float* hyper, float* m, float* v, float beta1,
                        float beta2, float eps, float div, hipStream_t s);
+
+// ---- AdamW inside the PowerSGD update pass (powersgd.hip) -----------------------------------
+// The wide update launch (16 x 256 tiles, plan rank <= kUWideMaxRank, full layout only) with the
+// element rule above in the place of momentum SGD: g := the decompressed value, div = 1, every
+// matrix decays; the rank-1 tail takes g := buf / div and decays when decay_1d.  Modes 1 / 2 only,
+// and mode 2 writes g = the decompressed, averaged gradient.  m is MatPtrs.mom / R1Step.mom, v lies
+// v_delta elements behind it.  lr and wd always come from the hyper block (never null).
+// A step may hold several of these launches (one per overlap group, then the rank-1 one): all read
+// the block as it was before the step, and only the last one, advance != 0, draws the tickets (ctr:
+// arrive_ctr_words(grid) zeroed uint32, re-armed) and has its last arriver write {p1, p2, steps + 1, 0}.
+struct AdamArgs {
+  AdamBlock* block;
+  unsigned* ctr;
+  int64_t v_delta;
+  float beta1, beta2, eps;
+  int decay_1d;
+  int advance;
+};
+// workgroups of one launch_psgd_update_adam / launch_rank1_adam_step (what ctr is sized by)
+int64_t psgd_update_adam_grid(int n_items, int64_t r1_n);
+int64_t rank1_adam_grid(int64_t n);
+void launch_psgd_update_adam(const MatGeom* geom, const MatPtrs* ptrs, const UItem* items, int n_items,
+                             const float* p_hat, const float* q_sum, float q_div, float* q_warm, int mode,
+                             int max_rank, hipStream_t s, float* p_prev, R1Step r1, const float* hyper, AdamArgs a);
+void launch_rank1_adam_step(const float* buf, float div, float* mom, float* x, float* g, int64_t n, hipStream_t s,
+                            const float* hyper, AdamArgs a);
 }  // namespace ndp
 
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include "adamw_elem.h"
+#include "arrival.h"
 #include "hyper.h"
 #include "ndp_kernels.h"
 #include "seg_block.h"
@@ -1128,6 +1130,231 @@ __global__ __launch_bounds__(256) void rank1_step_kernel(const float* __restrict
   }
 }
 
+// ----------------------------------------------------------------------------------
+// The wide update stage with AdamW in the place of momentum SGD (ndp_kernels.h AdamArgs): the
+// tile, the Q registers, the wave-uniform P-hat row, the fmaf order (so the decompressed value o is
+// bit for bit psgd_update_wide_kernel's), the warm-start Q and the p_prev write are that kernel's;
+// the element rule is adamw_elem (adamw_elem.h; the rule is the header comment of adamw.hip) with
+// g := o, div = 1 and every matrix decaying.  Modes 1 / 2 only; mode 2 writes g = o.  Full layout
+// only: a dead-tap compacted matrix is refused by the binding and skipped here.
+//   Streams.  m = MatPtrs.mom and v = mom + v_delta (and M when e is stored, and e) are touched
+//   once per step: non-temporal loads and stores.  x gets plain ones: the next forward reads it.
+//   All float4 loads of a wave's four rows are issued before the barrier below.
+//   The block (adamw.hip "Who writes the block").  Thread 0 reads b1pow / b2pow / steps and hands
+//   them to the workgroup through LDS behind ONE barrier, which every wave reaches: the per-wave
+//   exit of rows past the matrix comes after it.  A step may have several of these launches (one
+//   per overlap group, then the rank-1 one), in order on one stream: those with advance == 0 only
+//   read the block; in the step's last one, advance != 0, thread 0 of every workgroup (rank-1 tail
+//   included) draws the two-level ticket of arrival.h at its end, after the barrier, so after
+//   every read of the block by its workgroup, and the last arriver writes {p1, p2, steps + 1, 0}
+//   and re-arms the ticket.  Nobody waits, no floating-point atomic, replay-safe.
+//   Resources (hipcc --offload-arch=gfx950 -O3 -ffp-contract=fast, -Rpass-analysis=kernel-resource-usage):
+//   the table at the kernel.
+// ----------------------------------------------------------------------------------
+struct AdamShared {
+  float b1pow, b2pow;
+  unsigned steps;
+};
+
+// thread 0: the block into LDS (before the workgroup's barrier)
+__device__ __forceinline__ void adam_block_stage(AdamShared& sh, const AdamBlock* block) {
+  if (threadIdx.x == 0) {
+    sh.b1pow = block->b1pow;
+    sh.b2pow = block->b2pow;
+    sh.steps = block->steps;
+  }
+}
+
+// thread 0 of every workgroup of an advancing launch, at its end
+__device__ __forceinline__ void adam_block_advance(const AdamArgs& A, const AdamShared& sh, float p1, float p2) {
+  if (!A.advance || threadIdx.x != 0 || !arrive_last_grouped(A.ctr)) return;
+  A.block->b1pow = p1;
+  A.block->b2pow = p2;
+  A.block->steps = sh.steps + 1u;
+  A.block->pad = 0u;
+  arrive_rearm(A.ctr);
+}
+
+// the <=1-D group's step by workgroups [first, first + count) of the launch: gg = buf / div
+__device__ __forceinline__ void rank1_adam_body(const R1Step& r1, AdamScalars S, int64_t v_delta, unsigned wg,
+                                                unsigned count) {
+  const bool scale = r1.div != 1.0f;
+  const float NDP_GLOBAL* buf = (const float NDP_GLOBAL*)r1.buf;
+  float NDP_GLOBAL* mom = (float NDP_GLOBAL*)r1.mom;
+  float NDP_GLOBAL* x = (float NDP_GLOBAL*)r1.x;
+  float NDP_GLOBAL* gout = (float NDP_GLOBAL*)r1.g;
+  const int64_t stride = (int64_t)count * 256;
+  for (int64_t k = (int64_t)wg * 256 + threadIdx.x; k < r1.n; k += stride) {
+    const float b = buf[k];
+    const float gg = scale ? __fdiv_rn(b, r1.div) : b;
+    float xk = x[k];
+    float mk = __builtin_nontemporal_load(mom + k);
+    float vk = __builtin_nontemporal_load(mom + v_delta + k);
+    adamw_elem(xk, gg, mk, vk, S);
+    x[k] = xk;
+    __builtin_nontemporal_store(mk, mom + k);
+    __builtin_nontemporal_store(vk, mom + v_delta + k);
+    if (gout) gout[k] = gg;
+  }
+}
+
+// Resources, psgd_update_adam_wide_kernel<RQ> (no scratch, no spills, 0 AGPRs, 12 B of LDS in all three):
+//   RQ = 4:   111 VGPRs, 77 SGPRs, occupancy 4 waves/SIMD
+//   RQ = 8:   127 VGPRs, 77 SGPRs, occupancy 4 waves/SIMD
+//   RQ = 16:  159 VGPRs, 86 SGPRs, occupancy 3 waves/SIMD
+// rank1_adam_step_kernel: 30 VGPRs, 54 SGPRs, no scratch, occupancy 8.
+// 64 of the VGPRs are the stream in flight across the barrier (4 rows x float4 of M, m, v, x), 4 RQ
+// are Qs.  amdgpu_waves_per_eu is pinned (min = max) to what the report shows the registers allow,
+// 4 up to RQ = 8 and 3 at RQ = 16: asking for more made RQ = 16 keep Qs in scratch.  The P-hat loop
+// has no early exit (`if (c < r)`, not `break`): with the break, RQ = 16 did not unroll and Qs
+// went to 272 B/lane of scratch.  Neither figure has been timed against a neighbour.
+template <int RQ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RQ <= 8 ? 4 : 3, RQ <= 8 ? 4 : 3)))
+void psgd_update_adam_wide_kernel(
+    const MatGeom* __restrict__ geom, const MatPtrs* __restrict__ ptrs, const UItem* __restrict__ items,
+    const float* __restrict__ p_hat, const float* __restrict__ q_sum, float q_div, float* __restrict__ q_warm,
+    int mode, float* __restrict__ p_prev, R1Step r1, const float* __restrict__ hyper, AdamArgs A) {
+  __shared__ AdamShared sh;
+  adam_block_stage(sh, A.block);
+  const float lr = hyper[0], wd = hyper[1];
+  float p1, p2;
+  if ((int)blockIdx.x >= r1.n_items) {  // the rank-1 group's step, same launch
+    __syncthreads();
+    AdamScalars S = adam_launch_scalars(sh.b1pow, sh.b2pow, lr, wd, A.beta1, A.beta2, A.eps, p1, p2);
+    S.decay = wd != 0.f && A.decay_1d != 0;
+    rank1_adam_body(r1, S, A.v_delta, blockIdx.x - r1.n_items, gridDim.x - r1.n_items);
+    adam_block_advance(A, sh, p1, p2);
+    return;
+  }
+  const UItem it = items[blockIdx.x];
+  const MatGeom g = geom[it.mat];
+  const GPtrs pt = gptrs(ptrs[it.mat]);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = g.r, n = g.n, m = g.m;
+  const float* P = p_hat + g.p_off;
+  const float* Q = q_sum + g.q_off;
+  const bool full = g.tap_T == 0;  // a compacted matrix never gets here (bindings.cpp): touch nothing of it
+
+  if (q_warm != nullptr && it.row0 == 0 && wave == 0 && full) {
+    float* W = q_warm + g.q_off;
+    const int cnt = min(kUWideCols, m - it.col0) * r;
+    const int64_t base = (int64_t)it.col0 * r;
+    for (int idx = lane; idx < cnt; idx += 64) W[base + idx] = Q[base + idx] / q_div;
+  }
+
+  const int arow0 = it.row0 + wave * kURowsPerWave;
+  const bool active = arow0 < n && full;  // wave-uniform; wave 0 of a full matrix always is
+  const bool lazy = p_prev != nullptr;
+  const bool wg = mode == 2;
+  if (active && lazy && it.col0 == 0 && lane < r) {  // this row block's P-hat for the next P pass
+#pragma unroll
+    for (int i = 0; i < kURowsPerWave; ++i)
+      if (arow0 + i < n) p_prev[g.p_off + (int64_t)(arow0 + i) * r + lane] = P[(int64_t)(arow0 + i) * r + lane];
+  }
+  const int b = it.col0 + 4 * lane;
+  const int nb = max(0, min(4, m - b));  // valid columns of this lane (vec: 0 or 4)
+  float NDP_GLOBAL* const vmom = pt.mom + A.v_delta;
+  // the HBM stream first: M (= g + e) unless lazy, both moments, parameters of every row of the wave
+  f32x4 Mv[kURowsPerWave], Mm[kURowsPerWave], Vv[kURowsPerWave], Xv[kURowsPerWave];
+  if (g.vec) {
+#pragma unroll
+    for (int i = 0; i < kURowsPerWave; ++i) {
+      const bool ok = active && nb == 4 && arow0 + i < n;
+      const int64_t o = (int64_t)(arow0 + i) * m + b;
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      Mv[i] = (ok && !lazy) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(pt.mread + o)) : z;
+      Mm[i] = ok ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(pt.mom + o)) : z;
+      Vv[i] = ok ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 NDP_GLOBAL*>(vmom + o)) : z;
+      Xv[i] = ok ? ld4(pt.x + o) : z;
+    }
+  }
+  // Qs = Q_sum / N for this lane's columns (reducer.py:147)
+  float qv[4][RQ];
+  const bool q4 = (r & 3) == 0 && (g.q_off & 3) == 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool okq = active && j < nb;
+    if (q4) {
+#pragma unroll
+      for (int c = 0; c < RQ; c += 4) {
+        f32x4 t = (okq && c < r) ? ld4(Q + (int64_t)(b + j) * r + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) qv[j][c + u] = t[u] / q_div;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < RQ; ++c) qv[j][c] = (okq && c < r) ? Q[(int64_t)(b + j) * r + c] / q_div : 0.f;
+    }
+  }
+  __syncthreads();  // the block is in LDS; no wave has left yet
+  AdamScalars S = adam_launch_scalars(sh.b1pow, sh.b2pow, lr, wd, A.beta1, A.beta2, A.eps, p1, p2);
+  S.decay = wd != 0.f;
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < kURowsPerWave; ++i) {
+      const int a = arow0 + i;
+      if (a >= n) break;  // wave-uniform
+      const float* prow = P + (int64_t)a * r;
+      f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < RQ; ++c) {
+        if (c < r) {  // wave-uniform; no early exit, so the loop unrolls and qv stays in registers
+          const float pv = prow[c];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) o[j] = fmaf(pv, qv[j][c], o[j]);
+        }
+      }
+      const int64_t ro = (int64_t)a * m;
+      if (g.vec) {
+        if (nb != 4) continue;
+        f32x4 mm = Mm[i], vv = Vv[i], xx = Xv[i];
+        if (!lazy) __builtin_nontemporal_store(Mv[i] - o, reinterpret_cast<f32x4 NDP_GLOBAL*>(pt.e + ro + b));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float xk = xx[j], mk = mm[j], vk = vv[j];
+          adamw_elem(xk, o[j], mk, vk, S);
+          xx[j] = xk, mm[j] = mk, vv[j] = vk;
+        }
+        __builtin_nontemporal_store(mm, reinterpret_cast<f32x4 NDP_GLOBAL*>(pt.mom + ro + b));
+        __builtin_nontemporal_store(vv, reinterpret_cast<f32x4 NDP_GLOBAL*>(vmom + ro + b));
+        st4(pt.x + ro + b, xx);
+        if (wg) st4(pt.g + ro + b, o);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j >= nb) break;
+          const int64_t k = ro + b + j;
+          if (!lazy) __builtin_nontemporal_store(__builtin_nontemporal_load(pt.mread + k) - o[j], pt.e + k);
+          float xk = pt.x[k];
+          float mk = __builtin_nontemporal_load(pt.mom + k);
+          float vk = __builtin_nontemporal_load(vmom + k);
+          adamw_elem(xk, o[j], mk, vk, S);
+          pt.x[k] = xk;
+          __builtin_nontemporal_store(mk, pt.mom + k);
+          __builtin_nontemporal_store(vk, vmom + k);
+          if (wg) pt.g[k] = o[j];
+        }
+      }
+    }
+  }
+  adam_block_advance(A, sh, p1, p2);
+}
+
+// the <=1-D group's AdamW step on its own (the overlap path's rank-1 side item): the tail above
+__global__ __launch_bounds__(256) void rank1_adam_step_kernel(R1Step r1, const float* __restrict__ hyper,
+                                                              AdamArgs A) {
+  __shared__ AdamShared sh;
+  adam_block_stage(sh, A.block);
+  const float lr = hyper[0], wd = hyper[1];
+  __syncthreads();
+  float p1, p2;
+  AdamScalars S = adam_launch_scalars(sh.b1pow, sh.b2pow, lr, wd, A.beta1, A.beta2, A.eps, p1, p2);
+  S.decay = wd != 0.f && A.decay_1d != 0;
+  rank1_adam_body(r1, S, A.v_delta, blockIdx.x, gridDim.x);
+  adam_block_advance(A, sh, p1, p2);
+}
+
 // ---------------------------------- launchers -------------------------------------
 static inline void allow_lds(const void* fn, size_t bytes) {
   // gfx950 has 160 KiB of LDS per CU; dynamic requests above 64 KiB must be opted in.
@@ -1239,6 +1466,39 @@ void launch_rank1_step(const float* buf, float div, float* mom, float* x, float*
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(rank1_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, buf, div, mom,
                      x, g, n, lr, momentum, hyper);
+}
+
+int64_t psgd_update_adam_grid(int n_items, int64_t r1_n) {
+  return (int64_t)std::max(n_items, 0) + (r1_n > 0 ? std::min<int64_t>((r1_n + 255) / 256, 512) : 0);
+}
+
+int64_t rank1_adam_grid(int64_t n) { return n > 0 ? std::min<int64_t>((n + 255) / 256, 1024) : 0; }
+
+void launch_psgd_update_adam(const MatGeom* geom, const MatPtrs* ptrs, const UItem* items, int n_items,
+                             const float* p_hat, const float* q_sum, float q_div, float* q_warm, int mode,
+                             int max_rank, hipStream_t s, float* p_prev, R1Step r1, const float* hyper, AdamArgs a) {
+  r1.n_items = n_items;
+  const unsigned grid = (unsigned)psgd_update_adam_grid(n_items, r1.n);
+  if (grid == 0) return;
+  // the caller checks (bindings.cpp): modes 1 / 2, max_rank <= kUWideMaxRank, full layout
+  if (max_rank <= 4)
+    hipLaunchKernelGGL(psgd_update_adam_wide_kernel<4>, dim3(grid), dim3(256), 0, s, geom, ptrs, items, p_hat, q_sum,
+                       q_div, q_warm, mode, p_prev, r1, hyper, a);
+  else if (max_rank <= 8)
+    hipLaunchKernelGGL(psgd_update_adam_wide_kernel<8>, dim3(grid), dim3(256), 0, s, geom, ptrs, items, p_hat, q_sum,
+                       q_div, q_warm, mode, p_prev, r1, hyper, a);
+  else if (max_rank <= kUWideMaxRank)
+    hipLaunchKernelGGL(psgd_update_adam_wide_kernel<kUWideMaxRank>, dim3(grid), dim3(256), 0, s, geom, ptrs, items,
+                       p_hat, q_sum, q_div, q_warm, mode, p_prev, r1, hyper, a);
+}
+
+void launch_rank1_adam_step(const float* buf, float div, float* mom, float* x, float* g, int64_t n, hipStream_t s,
+                            const float* hyper, AdamArgs a) {
+  const int64_t blocks = rank1_adam_grid(n);
+  if (blocks <= 0) return;
+  R1Step r1{};
+  r1.buf = buf, r1.mom = mom, r1.x = x, r1.g = g, r1.n = n, r1.div = div;
+  hipLaunchKernelGGL(rank1_adam_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, r1, hyper, a);
 }
 
 }  // namespace ndp

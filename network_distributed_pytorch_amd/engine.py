@@ -395,7 +395,7 @@ def run_task(config) -> Dict[str, Any]:
     comm = Communicator(link=link, emulate_world=config.get("emulate_world"),
                         device=device if device.type == "cuda" else None)
     extra = {}
-    if config["grad_sync"] == "powersgd":
+    if config["grad_sync"] in ("powersgd", "powersgd-adamw"):
         extra = {"write_grad": config.get("write_grad", False), "reuse_query": config.get("reuse_query", True),
                  "overlap": config.get("overlap"), "groups": config.get("psgd_groups")}
         if not extra["reuse_query"]:

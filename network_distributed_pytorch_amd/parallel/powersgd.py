@@ -40,7 +40,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..ops import SegPlan, capturing, ext, gradfinish, taps, upload, upload_epoch
+from ..ops import SegPlan, StateBlock, capturing, ext, gradfinish, taps, upload, upload_epoch
+from ..ops.adamw import _twin_ as _adamw_twin_, adamw_scalars, check_adam_args
 from ..ops.hyper import HyperState
 from .comm import Communicator, n_bits
 from .sync import GradSync
@@ -536,6 +537,20 @@ class PowerSGDOptimizer(HyperState, GradSync):
     clipped gradient, and :meth:`clip_stats` reports a rank-local norm.  The norm needs every
     gradient, so the per-group pipelines cannot start during backward: ``overlap=None`` resolves
     to ``False`` and ``overlap=True`` / ``set_overlap(True)`` raise.
+
+    **AdamW** (``optimizer="adamw"`` with ``betas``, ``eps_adam``, ``decay_1d``; ``eps`` is the
+    orthogonaliser's): the update launches apply the AdamW rule of ops/adamw.py to the decompressed
+    value in the pass that decompresses (csrc/powersgd.hip ``psgd_update_adam_wide_kernel``, ``g := out``,
+    ``div = 1``; the <=1-D group with ``g := rank1 / N``), in the place of momentum SGD; ``momentum`` is
+    ignored, ``weight_decay`` is the decoupled decay (every matrix; the <=1-D group with ``decay_1d``),
+    ``write_grad`` leaves ``p.grad = out``, the decompressed, averaged gradient.  Error memory, P, Q and
+    the wire are untouched.  The moment arena is ``[m | v]`` in one tensor, the 16-byte block
+    ``{b1pow, b2pow, steps}`` (:meth:`adam_stats`) starts as ``{1, 1, 0}``, and the hyper block is
+    always read.  A step may hold several update launches (one per overlap group, then the rank-1
+    one): all read the block as it was before the step and only the last one advances it.  Scope:
+    plan rank <= 16 (above it the constructor raises) and the full layout only (no dead-tap
+    compaction, whatever the decay).  With ``optimizer="sgd"`` nothing of this is allocated, launched or
+    stored.
     """
 
     _arm = "PowerSGD"
@@ -545,9 +560,17 @@ class PowerSGDOptimizer(HyperState, GradSync):
                  comm: Optional[Communicator] = None, write_grad: bool = False,
                  broadcast_params: bool = True, rng_compat: bool = False, eps: float = 1e-8,
                  native: Optional[bool] = None, overlap: Optional[bool] = None, groups: Optional[int] = None,
-                 weight_decay: float = 0.0, max_grad_norm: float = 0.0):
+                 weight_decay: float = 0.0, max_grad_norm: float = 0.0, optimizer: str = "sgd",
+                 betas=(0.9, 0.999), eps_adam: float = 1e-8, decay_1d: bool = True):
         self.params: List[torch.nn.Parameter] = [p for p in params]
         assert self.params, "no parameters"
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"PowerSGD: unknown optimizer {optimizer!r} (sgd, adamw)")
+        self.optimizer = optimizer
+        self.adam = optimizer == "adamw"
+        if self.adam:
+            self.beta1, self.beta2, self.eps_adam = check_adam_args(betas, eps_adam)
+            self.decay_1d = bool(decay_1d)
         assert weight_decay >= 0, "weight_decay >= 0"
         if max_grad_norm > 0 and overlap:
             raise ValueError("PowerSGD: overlap=True cannot be combined with max_grad_norm > 0 (the global "
@@ -586,7 +609,13 @@ class PowerSGDOptimizer(HyperState, GradSync):
         f32 = dict(dtype=torch.float32, device=self.device)
         self.x = torch.zeros(o, **f32)
         self._e = torch.zeros(o, **f32)
-        self._m = torch.zeros(o, **f32)
+        if self.adam:  # [m | v] in one tensor: v lies _v_delta elements behind m, as far past 16 bytes
+            self._v_delta = (o + _ALIGN - 1) // _ALIGN * _ALIGN
+            self._moments = torch.zeros(2 * self._v_delta, **f32)
+            self._m = self._moments[:o]
+            self._v = self._moments[self._v_delta: self._v_delta + o]
+        else:
+            self._m = torch.zeros(o, **f32)
         self.offsets = offs
         with torch.no_grad():
             for p in self.params:
@@ -603,9 +632,21 @@ class PowerSGDOptimizer(HyperState, GradSync):
         self.r1_upd = torch.zeros(self.r1_numel if write_grad else 0, **f32)
         self.buf = _PlanBuffers(shapes, self.rank, self.r1_numel, self.device, native=native is not False)
         self.native = self.buf.native
+        if self.adam and self.buf.max_rank > _LAZY_MAX_RANK:
+            raise ValueError(f"PowerSGD with optimizer='adamw': plan rank {self.buf.max_rank} > {_LAZY_MAX_RANK}; the "
+                             "AdamW update exists for the wide update tile only (rank <= 16)")
         # device block [lr, weight_decay, 0, 0], allocated before any capture; the kernels read it
-        # once set_hyper() was called or a decay is on, else lr goes by value (see set_hyper)
-        self._init_hyper(float(lr), float(weight_decay), block=self.native)
+        # once set_hyper() was called or a decay is on, else lr goes by value (see set_hyper); the
+        # AdamW launches have no by-value lr: always on
+        self._init_hyper(float(lr), float(weight_decay), block=self.native, on=True if self.adam else None)
+        if self.adam:
+            # the AdamBlock and, on a device, the arrival tickets of the largest update launch (the
+            # fused one: every update item + 512 rank-1 blocks; the rank-1 launch alone: 1024)
+            self.adam_state = StateBlock(self.device, ("b1pow", "b2pow", "steps"), (1.0, 1.0, 0))
+            if self.native:
+                X = ext()
+                self._adam_ctr = torch.zeros(X.arrive_ctr_words(self.buf.counts["n_u_items"] + 1024),
+                                             dtype=torch.int32, device=self.device)
         # dead-tap compaction (ops/taps.py; NDP_FUSION_OFF=dead_taps): the support version the plan
         # was last compared with (None: compare at the next step)
         self.dead_taps = self.native and bool(shapes) and fusion_on("dead_taps")
@@ -730,6 +771,10 @@ class PowerSGDOptimizer(HyperState, GradSync):
             B.orth(float(N), self.eps, B.items("orth", g.lo, g.hi), spins)
             B.run_q(B.items("q", g.lo, g.hi), g.q_seg, g.q_seg_fused)
             self.comm.all_reduce(B.q_memory[q0:q1])                       # reducer.py:145 (group g)
+            if self.adam:  # the block advances in the step's last update launch: the rank-1 one if any
+                self._update_adam(B.items("u", g.lo, g.hi), N, pp, hy,
+                                  advance=g is self.groups[-1] and not self.r1_numel)
+                return
             X.psgd_update(B.geom, B.ptrs, B.items("u", g.lo, g.hi), B.comm_buf, B.q_memory, float(N),
                           B.q_warm, mode, lr, mom, B.max_rank, pp, hyper=hy)
         self.comm.side_launch(pipeline)
@@ -767,8 +812,11 @@ class PowerSGDOptimizer(HyperState, GradSync):
             def rank1():
                 self._r1_pack.run()
                 self.comm.all_reduce(B.rank1_buf)                           # reducer.py:132
-                ext().rank1_step(B.rank1_buf, float(N), self._m[r1], self.x[r1],
-                                 self.r1_upd if self.write_grad else None, lr, mom, hyper=hy)
+                if self.adam:
+                    self._rank1_adam(N, hy, advance=True)
+                else:
+                    ext().rank1_step(B.rank1_buf, float(N), self._m[r1], self.x[r1],
+                                     self.r1_upd if self.write_grad else None, lr, mom, hyper=hy)
                 if self.write_grad:
                     self._r1_out.run()
                 self._after_update()  # the EMA: behind the step's last update launch, same side item
@@ -776,6 +824,28 @@ class PowerSGDOptimizer(HyperState, GradSync):
         elif self.ema is not None:
             self.comm.side_launch(self._after_update)
         self.comm.side_join()
+
+    # -- AdamW launches ------------------------------------------------------------------------
+    def _adam_kw(self, advance: bool, hyper):
+        """The Adam arguments of one update launch; ``advance``: it is the step's last one."""
+        return dict(hyper=hyper, block=self.adam_state.dev, ctr=self._adam_ctr, moments=self._moments,
+                    v_delta=self._v_delta, beta1=self.beta1, beta2=self.beta2, eps=self.eps_adam,
+                    decay_1d=self.decay_1d, advance=bool(advance))
+
+    def _update_adam(self, items, N, pp, hy, advance: bool, **r1):
+        B = self.buf
+        ext().psgd_update_adam(B.geom, B.ptrs, items, B.comm_buf, B.q_memory, float(N), B.q_warm,
+                               2 if self.write_grad else 1, B.max_rank, geom_host=B._geom_host, p_prev=pp,
+                               **self._adam_kw(advance, hy), **r1)
+
+    def _rank1_adam(self, N, hy, advance: bool):
+        r1 = slice(self.r1_start, self.arena_numel)
+        ext().rank1_adam_step(self.buf.rank1_buf, float(N), self._m[r1], self.x[r1],
+                              self.r1_upd if self.write_grad else None, **self._adam_kw(advance, hy))
+
+    def adam_stats(self):
+        """The AdamW block ``{"b1pow", "b2pow", "steps"}`` (a host sync on a device), or None with SGD."""
+        return self.adam_state.read() if self.adam else None
 
     # -- helpers -------------------------------------------------------------------------
     def zero_grad(self, set_to_none: bool = True):
@@ -935,7 +1005,20 @@ class PowerSGDOptimizer(HyperState, GradSync):
             X = ext()
             r1 = slice(self.r1_start, self.arena_numel)
             hy = self._hyper_arg()
-            if B.shapes and B.fused and self.r1_numel:  # the rank-1 step rides in the update launch
+            if self.adam:
+                pp = self.p_prev if self.lazy_ef else None
+                ride = bool(B.shapes and B.fused and self.r1_numel)  # the rank-1 step rides in the update launch
+                if ride:
+                    self._update_adam(B.u_items, N, pp, hy, advance=True, r1_buf=B.rank1_buf, r1_div=float(N),
+                                      r1_mom=self._m[r1], r1_x=self.x[r1],
+                                      r1_g=self.r1_upd if self.write_grad else None)
+                elif B.shapes:
+                    self._update_adam(B.u_items, N, pp, hy, advance=not self.r1_numel)
+                if self.r1_numel and not ride:
+                    self._rank1_adam(N, hy, advance=True)
+                if self.r1_numel and self.write_grad:
+                    self._r1_out.run()
+            elif B.shapes and B.fused and self.r1_numel:  # the rank-1 step rides in the update launch
                 X.psgd_update(B.geom, B.ptrs, B.u_items, B.comm_buf, B.q_memory, float(N), B.q_warm,
                               2 if self.write_grad else 1, self.lr, self.momentum, B.max_rank,
                               self.p_prev if self.lazy_ef else None, r1_buf=B.rank1_buf, r1_div=float(N),
@@ -1006,7 +1089,10 @@ class PowerSGDOptimizer(HyperState, GradSync):
         return bool(self.overlap)  # the update launches of the overlap groups run on the side stream
 
     def _check_hyper(self, lr: float, wd: float) -> None:
-        """A captured step holds its dead-tap plan: switching the decay on or off under it raises."""
+        """A captured step holds its dead-tap plan: switching the decay on or off under it raises.
+        Under AdamW every matrix is always full: the plan does not depend on the decay."""
+        if self.adam:
+            return
         if self._captured_decay is not None and self._captured_decay != (wd != 0.0):
             raise RuntimeError("PowerSGD: weight_decay cannot be switched on or off after capture (the step "
                                "froze its dead-tap plan); capture again")
@@ -1037,9 +1123,19 @@ class PowerSGDOptimizer(HyperState, GradSync):
         self.comm.all_reduce(B.q_memory)
         B.q_memory.div_(N)
         B.q_warm.copy_(B.q_memory)
+        if self.adam:  # the scalars of the block as it is before the step, for every tensor of it
+            st = self.adam_state.read()
+            S = adamw_scalars(st["b1pow"], st["b2pow"], lr, wd, self.beta1, self.beta2)
+            decays_hi = np.float32(wd) != np.float32(0.0)
         for i, (p, M) in enumerate(zip(self.high, Ms)):
             out = torch.matmul(B.p_view(i), B.q_view(i).t()).view(-1)
             self._view(self._e, p).copy_(M.reshape(-1) - out)
+            if self.adam:  # g := out, div = 1, every matrix decays
+                _adamw_twin_(self._view(self.x, p), out, self._view(self._m, p), self._view(self._v, p), S,
+                             self.beta1, self.beta2, self.eps_adam, 1.0, decays_hi)
+                if self.write_grad:
+                    gmap[id(p)].copy_(out.view_as(p))
+                continue
             if wd != 0.0:  # after decompression and the error memory: d = out + wd x
                 out = out.add(self._view(self.x, p), alpha=wd)
             mom = self._view(self._m, p)
@@ -1048,6 +1144,18 @@ class PowerSGDOptimizer(HyperState, GradSync):
             self._view(self.x, p).add_(upd, alpha=-lr)
             if self.write_grad:
                 gmap[id(p)].copy_(upd.view_as(p))
+        if self.adam:
+            if self.r1_numel:  # g := rank1 / N (the twin divides, as the kernel does), decay_1d decides the decay
+                r1 = slice(self.r1_start, self.arena_numel)
+                _adamw_twin_(self.x[r1], B.rank1_buf, self._m[r1], self._v[r1], S, self.beta1, self.beta2,
+                             self.eps_adam, float(N), bool(decays_hi) and self.decay_1d)
+                if self.write_grad:
+                    gg = B.rank1_buf if N == 1 else torch.div(B.rank1_buf, torch.tensor(float(N)))
+                    for p in self.rank1:
+                        s = self.offsets[id(p)] - self.r1_start
+                        gmap[id(p)].copy_(gg[s: s + p.numel()].view_as(p))
+            self.adam_state.write({"b1pow": float(S["p1"]), "b2pow": float(S["p2"]), "steps": st["steps"] + 1})
+            return
         if self.r1_numel:
             r1 = slice(self.r1_start, self.arena_numel)
             out = B.rank1_buf / N
@@ -1066,7 +1174,7 @@ class PowerSGDOptimizer(HyperState, GradSync):
         """(T, mask) of every high-rank parameter whose recorded support has dead taps, else (0, 0).
         With weight decay a dead tap's weight still moves (d = wd x), so it needs its momentum:
         every matrix reports (0, 0), the full plan."""
-        if self.weight_decay != 0.0:
+        if self.weight_decay != 0.0 or self.adam:  # the AdamW update tile is the full one only
             return [(0, 0)] * len(self.high)
         out = []
         for p in self.high:
@@ -1192,7 +1300,8 @@ class PowerSGDOptimizer(HyperState, GradSync):
                 "x": self.x.clone(), "e": self._full_arena(self._e).clone(), "p_prev": self.p_prev.clone(),
                 "lazy_pending": self._lazy_pending, "m": self.m.clone(), "q": self.buf.q_warm.clone(),
                 "step_count": self.step_count, "bits": self.bits_communicated, "q_ready": self._q_ready,
-                "rng": self.rng.get_state()}
+                "rng": self.rng.get_state(),
+                **({"v": self._v.clone(), "adam": self.adam_state.snapshot()} if self.adam else {})}
 
     def restore(self, snap):
         self.x.copy_(snap["x"])
@@ -1205,11 +1314,21 @@ class PowerSGDOptimizer(HyperState, GradSync):
         self.bits_communicated = snap["bits"]
         self._q_ready = snap["q_ready"]
         self.rng.set_state(snap["rng"])
+        if self.adam:
+            self._v.copy_(snap["v"])
+            self.adam_state.restore(snap["adam"])
         self._restore_extras(snap)
 
     # -- checkpoint / resume ---------------------------------------------------------------
     def state_dict(self):
+        adam = {}
+        if self.adam:  # "momentum" is the first moment
+            st = self.adam_state.read()
+            adam = {"optimizer": "adamw", "exp_avg_sq": self._v.detach().cpu().clone(), "b1pow": st["b1pow"],
+                    "b2pow": st["b2pow"], "steps": st["steps"], "betas": (self.beta1, self.beta2),
+                    "eps_adam": self.eps_adam, "decay_1d": self.decay_1d}
         return {
+            **adam,
             "step_count": self.step_count,
             "bits_communicated": self.bits_communicated,
             "error": self.e.detach().cpu().clone(),  # materialised (lazy error feedback)
@@ -1225,6 +1344,10 @@ class PowerSGDOptimizer(HyperState, GradSync):
 
     def load_state_dict(self, sd):
         assert sd["rank"] == self.rank, "checkpoint compression rank differs"
+        theirs = sd.get("optimizer", "sgd")  # a checkpoint without "optimizer" is an SGD checkpoint
+        if theirs != self.optimizer:
+            raise ValueError(f"PowerSGD: the checkpoint holds {theirs} optimizer state, this sync runs "
+                             f"{self.optimizer}; they cannot be loaded into each other")
         self.step_count = int(sd["step_count"])
         self.bits_communicated = int(sd["bits_communicated"])
         if any(lay is not None for lay in self.buf.layout):
@@ -1235,6 +1358,10 @@ class PowerSGDOptimizer(HyperState, GradSync):
         self.p_prev.zero_()  # e is the true error memory: no pending correction
         self._lazy_pending = False
         self._m.copy_(sd["momentum"])
+        if self.adam:
+            self._v.copy_(sd["exp_avg_sq"])
+            self.adam_state.write({"b1pow": float(np.float32(sd["b1pow"])), "b2pow": float(np.float32(sd["b2pow"])),
+                                   "steps": int(sd["steps"])})
         self.buf.q_warm.copy_(sd["q_warm"])
         self._q_ready = bool(sd.get("q_ready", self.step_count > 0)) and self.reuse_query
         self.rng.set_state(_rng_state_from_dict(sd["rng_state"]))

@@ -7,6 +7,8 @@
 ``powersgd``       fused native engine (:class:`PowerSGDOptimizer`): EF + PowerSGD + momentum
                    + SGD over flat arenas; on a device the per-group pipelines (6 gfx950
                    launches + 2 collectives each) overlap backward on the side stream.
+``powersgd-adamw`` the same engine with AdamW in its update pass in the place of momentum SGD
+                   (``optimizer="adamw"`` of :class:`PowerSGDOptimizer`; rank <= 16, full layout).
 ``powersgd-ref``   reference semantics, eager per-tensor loops (ddp_init.py:149-178 with the
                    reducer's torch path) — the "eager reference" comparison arm.
 ``dense``          bucketed all-reduce overlapped with backward + fused SGD-momentum kernel.
@@ -33,8 +35,8 @@ launch, snapshot and state dict is what it is without.
 (ops/adamw.py) behind ``dense`` (the fused launch over the arenas), ``powersgd-ref`` / ``powersgd-api``
 (``FusedAdamW`` over the decompressed, averaged gradients; error memory and wire untouched) and
 ``dense-ref`` (``torch.optim.AdamW`` with two param groups, capturable on a device); ``adam_stats()``
-returns the step count.  ``powersgd`` and the local optimisers raise: the fused update kernels step in
-the pass that decompresses and feeds back, and have no Adam variant yet.  With ``optimizer="sgd"``
+returns the step count.  ``powersgd`` and the local optimisers raise: the fused engine's Adam variant is
+its own kind, ``powersgd-adamw`` (the kind is the optimiser choice, as ``local-adamw``).  With ``optimizer="sgd"``
 every constructor call is exactly what it is without these arguments.
 """
 from __future__ import annotations

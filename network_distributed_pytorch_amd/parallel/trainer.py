@@ -3,6 +3,7 @@
 
 ======================  =====================================================================
 ``powersgd``            :class:`PowerSGDSync`: the fused native engine (parallel/powersgd.py)
+``powersgd-adamw``      :class:`PowerSGDSync` with ``optimizer="adamw"``: the same engine, AdamW in its update pass
 ``powersgd-ref``        :class:`ReferencePowerSGDLoop`, the reducer's torch path
 ``powersgd-api``        :class:`ReferencePowerSGDLoop`, the native reducer behind the reference API
 ``dense``               :class:`_DenseSync`: bucketed, backward-overlapped all-reduce (parallel/ddp.py)
@@ -189,6 +190,13 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
     comm = comm if comm is not None else Communicator()
     clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
     adam = {}  # optimizer="sgd": every constructor call as before
+    if kind == "powersgd-adamw":
+        # the kind is the optimiser choice (as local-adamw): optimizer "sgd" here means "unspecified"
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
+        b1, b2, eps = check_adam_args(betas, eps)
+        return PowerSGDSync(model, comm, lr, momentum, rank, seed=seed, optimizer="adamw", betas=(b1, b2),
+                            eps_adam=eps, decay_1d=bool(decay_1d), **clip, **kw)
     if optimizer != "sgd":
         if optimizer != "adamw":
             raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")

@@ -23,7 +23,9 @@ class ConfigError(ValueError):
     pass
 
 
-GRAD_SYNCS = ("powersgd", "powersgd-ref", "powersgd-api", "dense", "dense-ref", "local-sgd-nesterov", "local-adamw")
+GRAD_SYNCS = ("powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref", "local-sgd-nesterov",
+              "local-adamw")
+PSGD_ENGINE_SYNCS = ("powersgd", "powersgd-adamw")  # the fused native engine (parallel/powersgd.py)
 TASKS = ("cifar", "imdb", "mlp")
 GRAPH_MODES = ("auto", "full", "piecewise", "none")
 LINKS = ("none", "1g", "10g", "100g")
@@ -108,7 +110,8 @@ class TrainConfig:
     ema_decay: float = 0.0  # 0 = off; 0 < decay < 1: shadow += (1 - d) * (weights - shadow) after every step
     ema_warmup: bool = True  # d = min(decay, (n + 1) / (n + 10)) for update n (the TF / timm warm-up)
     # the optimiser behind the gradient sync: "sgd" (momentum) or "adamw" (ops/adamw.py; dense, dense-ref,
-    # powersgd-ref and powersgd-api only); with "adamw", weight_decay is the decoupled decay
+    # powersgd-ref and powersgd-api only; grad_sync="powersgd-adamw" is the fused engine with AdamW and sets
+    # it); with "adamw", weight_decay is the decoupled decay
     optimizer: str = "sgd"
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
@@ -178,7 +181,7 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError("bucket_mb must be > 0")
     if c["psgd_groups"] is not None and c["psgd_groups"] < 1:
         raise ConfigError("psgd_groups must be >= 1")
-    if c["graph_mode"] in ("full", "piecewise") and c["grad_sync"] == "powersgd" and not c["reuse_query"]:
+    if c["graph_mode"] in ("full", "piecewise") and c["grad_sync"] in PSGD_ENGINE_SYNCS and not c["reuse_query"]:
         raise ConfigError("graph capture needs reuse_query=True (the per-step query re-draw is host-side)")
     if c["log_every"] < 1 or c["training_epochs"] < 0 or c["timeout_s"] <= 0:
         raise ConfigError("log_every >= 1, training_epochs >= 0, timeout_s > 0 required")
@@ -206,13 +209,15 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
             raise ConfigError(f"{key} = {c[key]} must lie in [0, 1)")
     if not np.float32(c["adam_eps"]) > 0 or not np.isfinite(c["adam_eps"]):
         raise ConfigError(f"adam_eps = {c['adam_eps']} must be a finite number > 0 (as fp32)")
-    if c["optimizer"] == "adamw" and c["grad_sync"] not in ADAMW_GRAD_SYNCS:
+    if c["grad_sync"] == "powersgd-adamw":  # the kind is the optimiser choice, as local-adamw
+        c["optimizer"] = "adamw"
+    elif c["optimizer"] == "adamw" and c["grad_sync"] not in ADAMW_GRAD_SYNCS:
         raise ConfigError(f"optimizer='adamw' is not available with grad_sync={c['grad_sync']!r} (the fused PowerSGD "
                           f"engine and the local optimisers have no AdamW); allowed: {list(ADAMW_GRAD_SYNCS)}")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too
         raise ConfigError(f"max_grad_norm = {c['max_grad_norm']} must be >= 0 (0 = off, inf = measure only)")
-    if c["max_grad_norm"] > 0 and c["grad_sync"] == "powersgd" and c["overlap"]:
-        raise ConfigError("grad_sync='powersgd' with overlap=True cannot be combined with max_grad_norm > 0: the "
+    if c["max_grad_norm"] > 0 and c["grad_sync"] in PSGD_ENGINE_SYNCS and c["overlap"]:
+        raise ConfigError(f"grad_sync={c['grad_sync']!r} with overlap=True cannot be combined with max_grad_norm > 0: the "
                           "global norm needs every gradient before a group's pipeline may start")
     if not 0 <= c["lr_min"] <= c["learning_rate"]:
         raise ConfigError(f"lr_min {c['lr_min']} must lie in [0, learning_rate = {c['learning_rate']}]")

@@ -40,7 +40,7 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-model", type=str, default=None)
     p.add_argument("-num_classes", type=int, default=None)
     p.add_argument("-grad_sync", type=str, default=None,
-                   choices=[None, "powersgd", "powersgd-ref", "powersgd-api", "dense", "dense-ref"])
+                   choices=[None, "powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref"])
     p.add_argument("-rank_r", type=int, default=None, help="PowerSGD compression rank")
     p.add_argument("-batch", type=int, default=None, help="global batch")
     p.add_argument("-lr", type=float, default=None)
