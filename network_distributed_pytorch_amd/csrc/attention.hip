@@ -222,7 +222,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 }
 
 // ---------------------------------------------------------------------------------------
-// backward.  delta[bh][q] = sum_d dO[q][d] * O[q][d]
+// backward.  delta[bh][q] = sum_d dO[q][d] * O[q][d], accumulated in double and rounded once:
+// dS = P (dP - delta) cancels two numbers of magnitude |dO . V| (about sqrt(64) for unit inputs), so
+// every rounding of delta's 64 products and of their sum lands in dS at that magnitude; with one
+// key, where dS is identically zero, the fp32 sum left dq 1.0e-6 from zero (tests/
+// test_bert_kernels_gpu.py, S = 1 with dropout).  The kernel is bound by its two reads.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const float* __restrict__ o, const float* __restrict__ dout,
                                                              float* __restrict__ delta, int B, int S, int H) {
@@ -230,12 +234,12 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const float* __rest
   const int lane = threadIdx.x & 63;
   if (row >= B * S * H) return;
   const int64_t off = (int64_t)row * kD + lane;
-  float v = o[off] * dout[off];
+  double v = (double)o[off] * (double)dout[off];   // exact
 #pragma unroll
   for (int x = 32; x > 0; x >>= 1) v += __shfl_xor(v, x, 64);
   if (lane == 0) {
     const int h = row % H, bs = row / H, s = bs % S, b = bs / S;
-    delta[((int64_t)b * H + h) * S + s] = v;
+    delta[((int64_t)b * H + h) * S + s] = (float)v;
   }
 }
 
@@ -477,28 +481,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 }
 
 // ------------------------------------ launchers ------------------------------------------
+// Dropout threshold (hash < thr drops) and keep scale 1 / (1 - p), in double exactly as ln_drop
+// (bindings.cpp) and the host twin ops/attention.py dropout_keep_mask.  In fp32, float(p) * 2^32 lies
+// above the double value (by 7 at p = 0.1, 13 at p = 0.2, 52 at p = 0.3) and an element whose hash fell
+// in between was dropped here and kept by the twin; 4294967295.0f is 2^32, so an fp32 cap leaves the
+// conversion undefined for p near 1; and a double p < 1 that rounds to 1.0f gives an infinite scale.
+static void attn_drop(double p, uint32_t* thr, float* scale) {
+  if (!(p > 0.0)) return;  // thr = 0: no dropout
+  const double t = p * 4294967296.0;
+  *thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+  *scale = (float)(1.0 / (1.0 - p));
+}
+
 void launch_attn_fwd(const float* q, const float* k, const float* v, const int32_t* mask, float* o, float* lse,
-                     int B, int S, int H, float scale, const int32_t* seed, float p_drop, hipStream_t s,
+                     int B, int S, int H, float scale, const int32_t* seed, double p_drop, hipStream_t s,
                      int64_t ldq) {
   AttnArgs a{q, k, v, mask, o, lse, B, S, H, scale, seed, 0u, 1.f, ldq > 0 ? ldq : (int64_t)H * kD};
-  if (p_drop > 0.f) {
-    a.drop_thr = (uint32_t)fminf(p_drop * 4294967296.0f, 4294967295.0f);
-    a.drop_scale = 1.f / (1.f - p_drop);
-  }
+  attn_drop(p_drop, &a.drop_thr, &a.drop_scale);
   hipLaunchKernelGGL(attn_fwd_kernel, dim3((S + 63) / 64, B * H), dim3(256), 0, s, a);
 }
 
 void launch_attn_bwd(const float* q, const float* k, const float* v, const int32_t* mask, const float* o,
                      const float* dout, const float* lse, float* delta, float* dq, float* dk, float* dv, int B,
-                     int S, int H, float scale, const int32_t* seed, float p_drop, hipStream_t s, int64_t ldq) {
+                     int S, int H, float scale, const int32_t* seed, double p_drop, hipStream_t s, int64_t ldq) {
   const int rows = B * S * H;
   hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, o, dout, delta, B, S, H);
   AttnBwdArgs a{q, k, v, mask, dout, lse, delta, dq, dk, dv, B, S, H, scale, seed, 0u, 1.f,
                 ldq > 0 ? ldq : (int64_t)H * kD};
-  if (p_drop > 0.f) {
-    a.drop_thr = (uint32_t)fminf(p_drop * 4294967296.0f, 4294967295.0f);
-    a.drop_scale = 1.f / (1.f - p_drop);
-  }
+  attn_drop(p_drop, &a.drop_thr, &a.drop_scale);
   hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3((S + 63) / 64, B * H), dim3(256), 0, s, a);
   hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((S + 63) / 64, B * H), dim3(256), 0, s, a);
 }

@@ -1823,7 +1823,7 @@ void attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, c10::optional<t
   }
   const int32_t* sp = attn_seed(seed, p_drop);
   ndp::launch_attn_fwd(q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(), mp, o.data_ptr<float>(),
-                       lse.data_ptr<float>(), B, S, H, (float)scale, sp, (float)p_drop, cur_stream(), ld);
+                       lse.data_ptr<float>(), B, S, H, (float)scale, sp, p_drop, cur_stream(), ld);
   check_launch("launch_attn_fwd");
 }
 
@@ -1850,7 +1850,7 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, c10::optional<t
   ndp::launch_attn_bwd(q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(), mp, o.data_ptr<float>(),
                        dout.data_ptr<float>(), lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr<float>(),
                        dk.data_ptr<float>(), dv.data_ptr<float>(), B, S, H, (float)scale, sp,
-                       (float)p_drop, cur_stream(), ld);
+                       p_drop, cur_stream(), ld);
   check_launch("launch_attn_bwd");
 }
 
