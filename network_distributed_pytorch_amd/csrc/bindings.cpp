@@ -1597,6 +1597,49 @@ void adamw_step(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, 
   check_launch("launch_adamw_step");
 }
 
+// top-k sparsification (topk.hip): flat fp32 arenas, int32 scratch of >= topk_scratch_words(n) zeroed
+// words, an int32[8] block and out = int32 [2k].  No allocation, no sync: capture-safe.
+void topk_check_arena(const torch::Tensor& t, const char* name, int64_t n) {
+  check_f32(t, name);
+  TORCH_CHECK(t.numel() == n, "topk: ", name, " has ", t.numel(), " elements, expected ", n);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "topk: ", name, " must be 16-byte aligned");
+}
+const int32_t* topk_check_i32(const torch::Tensor& t, const char* name, int64_t least) {
+  check_dev(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.numel() >= least, "topk: ", name, " must be int32 of >= ", least,
+              " elements");
+  return t.data_ptr<int32_t>();
+}
+
+void topk_select(torch::Tensor g, torch::Tensor e, int64_t k, torch::Tensor scratch, torch::Tensor block,
+                 torch::Tensor out, int64_t stage) {
+  const int64_t n = e.numel();
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), "topk_select: 1 <= n < 2^31 required");
+  TORCH_CHECK(k >= 1 && k <= n, "topk_select: 1 <= k <= n required, got k = ", k, ", n = ", n);
+  TORCH_CHECK(stage >= -1 && stage <= 4, "topk_select: stage -1 (all) or 0..4");
+  topk_check_arena(g, "g", n); topk_check_arena(e, "e", n);
+  auto* sc = const_cast<int32_t*>(topk_check_i32(scratch, "scratch", ndp::topk_scratch_words(n)));
+  TORCH_CHECK(block.numel() == 8, "topk_select: the block is 8 int32 words");
+  auto* blk = const_cast<int32_t*>(topk_check_i32(block, "block", 8));
+  auto* o = const_cast<int32_t*>(topk_check_i32(out, "out", 2 * k));
+  TORCH_CHECK(out.numel() == 2 * k, "topk_select: out must be int32 [2k]");
+  ndp::launch_topk_select(g.data_ptr<float>(), e.data_ptr<float>(), n, k, reinterpret_cast<uint32_t*>(sc),
+                          reinterpret_cast<ndp::TopkBlock*>(blk), o, (int)stage, cur_stream());
+  check_launch("launch_topk_select");
+}
+
+void topk_update(torch::Tensor x, torch::Tensor b, torch::Tensor gathered, int64_t k, int64_t world, double lr,
+                 double lam, c10::optional<torch::Tensor> hyper) {
+  const int64_t n = x.numel();
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), "topk_update: 1 <= n < 2^31 required");
+  TORCH_CHECK(k >= 1 && k <= n && world >= 1 && world < (1 << 24), "topk_update: 1 <= k <= n and 1 <= world < 2^24");
+  topk_check_arena(x, "x", n); topk_check_arena(b, "b", n);
+  const int32_t* gp = topk_check_i32(gathered, "gathered", world * 2 * k);
+  ndp::launch_topk_update(x.data_ptr<float>(), b.data_ptr<float>(), n, gp, k, (int)world, (float)lr, (float)lam,
+                          hyper_ptr(hyper), cur_stream());
+  check_launch("launch_topk_update");
+}
+
 // batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
 // [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
 // shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
@@ -2073,6 +2116,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step", &adamw_step, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
         py::arg("ctr"), py::arg("block"), py::arg("hyper"), py::arg("m"), py::arg("v"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("div"));
+  m.def("topk_select", &topk_select, py::arg("g"), py::arg("e"), py::arg("k"), py::arg("scratch"), py::arg("block"),
+        py::arg("out"), py::arg("stage") = -1);
+  m.def("topk_update", &topk_update, py::arg("x"), py::arg("b"), py::arg("gathered"), py::arg("k"), py::arg("world"),
+        py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
+  m.def("topk_scratch_words", &ndp::topk_scratch_words);
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));

@@ -399,6 +399,33 @@ void launch_psgd_update_adam(const MatGeom* geom, const MatPtrs* ptrs, const UIt
                              int max_rank, hipStream_t s, float* p_prev, R1Step r1, const float* hyper, AdamArgs a);
 void launch_rank1_adam_step(const float* buf, float div, float* mom, float* x, float* g, int64_t n, hipStream_t s,
                             const float* hyper, AdamArgs a);
+
+// ---- top-k sparsification with error feedback (topk.hip) -------------------------------------
+// Flat fp32 arenas of n < 2^31 elements, 16-byte aligned; 1 <= k <= n.  scratch:
+// topk_scratch_words(n) zeroed uint32 ([histogram | arrival tickets | per-chunk counts]; every
+// launch leaves the histogram zero and the tickets armed), blk: the select's device block, out:
+// int32 [2k] = idx ascending | bits(val).
+constexpr int kTopkChunk = 8192;  // elements per workgroup of the five select launches
+constexpr int kTopkTile = 2048;   // elements per workgroup of the update launch
+constexpr int kTopkBins = 2048;   // words of the global digit histogram
+struct TopkBlock {
+  uint32_t prefix;  // the digits of T found so far
+  uint32_t krem;    // entries still to take among the keys with that prefix
+  uint32_t T;       // after pass 2: the k-th largest key,
+  uint32_t c;       //   #{key > T}
+  uint32_t ties;    //   and k - c, the keys == T to take in index order
+  uint32_t pad[3];
+};
+int64_t topk_scratch_words(int64_t n);
+// m = g + e into e, then (idx, val) of the k selected entries into out and 0 into their e.
+// stage < 0: the five launches (pass 0, 1, 2, count, compact); 0..4: that launch alone.
+void launch_topk_select(const float* g, float* e, int64_t n, int64_t k, uint32_t* scratch, TopkBlock* blk,
+                        int32_t* out, int stage, hipStream_t s);
+// gathered: int32 [world][2k], one select output per rank; x, b updated in place by the element
+// rule with o = (sum over ranks in rank order of the values at the element) / world.  hyper: the
+// device block [lr, weight_decay, 0, 0], or null (lr by value, no decay).
+void launch_topk_update(float* x, float* b, int64_t n, const int32_t* gathered, int64_t k, int world, float lr,
+                        float lam, const float* hyper, hipStream_t s);
 }  // namespace ndp
 
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------

@@ -81,6 +81,8 @@ def default_config(**over) -> Dict[str, Any]:
         ema_decay=0.0, ema_warmup=True,
         # the optimiser behind the gradient sync: "sgd" or "adamw" (ops/adamw.py; weight_decay is then decoupled)
         optimizer="sgd", adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, decay_1d=True,
+        # grad_sync="topk" (parallel/topk.py): the fraction of the parameters each rank sends per step
+        topk_ratio=0.01,
     )
     cfg.update(over)
     return cfg
@@ -402,6 +404,8 @@ def run_task(config) -> Dict[str, Any]:
             graph_mode = "none"  # the per-step query re-draw is host-side (not capturable)
     elif config["grad_sync"] == "dense":
         extra = {"overlap": config.get("overlap")}
+    elif config["grad_sync"] == "topk":
+        extra = {"overlap": config.get("overlap"), "topk_ratio": float(config.get("topk_ratio", 0.01))}
     max_grad_norm = float(config.get("max_grad_norm") or 0.0)
     if max_grad_norm > 0:  # off: build_grad_sync is called exactly as before
         extra["max_grad_norm"] = max_grad_norm

@@ -555,6 +555,38 @@ class Communicator:
             return _StreamWork() if async_op else None
         return dist.all_gather(out_list, t, group=self.group, async_op=async_op)
 
+    def all_gather_into(self, out: torch.Tensor, t: torch.Tensor) -> None:
+        """Every rank's ``t`` into ONE flat ``out`` (``world_size * t.numel()`` elements, rank order),
+        no per-rank copies: the step-path gather (top-k's one collective).  Stream-ordered and
+        capturable on the native RCCL plane.  Accounted as a ring all-gather: payload ``S`` (this
+        rank's bytes), wire ``(N - 1) S`` per rank, ``alpha + 8 (N - 1) S / bandwidth`` on an emulated
+        link, against the all-reduce's ``2 (N - 1) / N * S``."""
+        n = self.paced_world
+        payload = t.nelement() * t.element_size()
+        wire = 0.0 if n <= 1 else float(n - 1) * payload
+        secs = self.link.alpha_s + 8.0 * wire / self.link.bandwidth_bps if self.link is not None and n > 1 else 0.0
+        self.stats.calls += 1
+        self.stats.payload_bytes += payload
+        self.stats.wire_bytes += wire
+        self.stats.emulated_seconds += secs
+        flat = out.view(-1)
+        if not self.active:
+            assert flat.numel() == t.numel(), "all_gather_into: out must hold world_size * t.numel() elements"
+            if flat.data_ptr() != t.data_ptr():
+                flat.copy_(t.reshape(-1))
+            self._pace(secs, t.is_cuda)
+            return
+        assert flat.numel() == self.world_size * t.numel() and out.is_contiguous() and t.is_contiguous()
+        if self._native is not None and t.is_cuda:
+            if isinstance(self._native, IpcDataPlane) and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("all_gather_into: the IPC data plane gathers through host memory, which cannot be "
+                                   "captured; run this step eagerly or piecewise, or use the RCCL plane")
+            self._captured |= torch.cuda.is_current_stream_capturing()
+            self._native.all_gather(flat, t.reshape(-1))
+        else:  # c10d: the rows of out are the output list, written in place
+            dist.all_gather(list(flat.view(self.world_size, -1).unbind(0)), t.reshape(-1), group=self.group)
+        self._pace(secs, t.is_cuda)
+
     def broadcast(self, t: torch.Tensor, src: int = 0):
         if not self.active:
             return None

@@ -14,6 +14,8 @@
 ``dense``          bucketed all-reduce overlapped with backward + fused SGD-momentum kernel.
 ``dense-ref``      reference dense arm: blocking per-parameter all-reduce + torch.optim.SGD
                    (ddp_guide_cifar10/ddp_init.py:57-62,111,124-125).
+``topk``           exact global top-k of ``g + e`` with error feedback (:class:`TopKSync`): 5 select
+                   launches, one all-gather of ``(idx, val)``, one decompress + momentum + SGD launch.
 =================  ===========================================================================
 
 Every strategy has ``set_hyper(lr, weight_decay)``: the learning rate and the L2 weight decay of

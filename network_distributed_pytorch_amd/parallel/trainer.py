@@ -10,6 +10,7 @@
 ``dense-ref``           :class:`ReferenceDenseLoop`: blocking per-parameter all-reduce + torch optimiser
 ``local-sgd-nesterov``  :class:`LocalOptimizer`, no communication
 ``local-adamw``         :class:`LocalOptimizer`, no communication
+``topk``                :class:`TopKSync`: exact global top-k with error feedback, one all-gather (parallel/topk.py)
 ======================  =====================================================================
 """
 from __future__ import annotations
@@ -23,8 +24,9 @@ from .comm import Communicator
 from .ddp import BucketedDataParallel, average_gradients
 from .powersgd import PowerSGDOptimizer, PowerSGDReducer, powersgd_bytes_per_step
 from .sync import GradSync
+from .topk import TopKSync
 
-__all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "ADAMW_SYNCS"]
+__all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "TopKSync", "ADAMW_SYNCS"]
 
 ADAMW_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # the arms that take optimizer="adamw"
 
@@ -186,7 +188,7 @@ def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
 def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                     momentum: float = 0.9, rank: int = 4, bucket_mb: Optional[float] = None, seed: int = 714,
                     max_grad_norm: float = 0.0, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
-                    decay_1d: bool = True, **kw):
+                    decay_1d: bool = True, topk_ratio: float = 0.01, **kw):
     comm = comm if comm is not None else Communicator()
     clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
     adam = {}  # optimizer="sgd": every constructor call as before
@@ -202,7 +204,8 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
             raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
         if kind not in ADAMW_SYNCS:
             raise ValueError(f"grad sync {kind!r} has no AdamW: the fused PowerSGD update kernels decompress, feed "
-                             f"back and step in one register-pinned pass (an Adam variant of them is future work) and "
+                             f"back and step in one register-pinned pass (an Adam variant of them is future work), "
+                             f"the top-k update kernel is momentum SGD only and "
                              f"the local optimisers are fixed recipes; use one of {', '.join(ADAMW_SYNCS)}")
         b1, b2, eps = check_adam_args(betas, eps)
         adam = {"optimizer": "adamw", "betas": (b1, b2), "eps": eps, "decay_1d": bool(decay_1d)}
@@ -218,6 +221,9 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
         return ReferenceDenseLoop(model, comm, lr, momentum, **clip, **adam)
     if kind in ("local-sgd-nesterov", "local-adamw"):
         return LocalOptimizer(model, kind, lr, momentum, **clip)
+    if kind == "topk":
+        return TopKSync(model, comm, lr=lr, momentum=momentum, topk_ratio=topk_ratio, overlap=kw.get("overlap"),
+                        **clip)
     raise ValueError(f"unknown grad sync {kind!r}")
 
 

@@ -24,7 +24,7 @@ class ConfigError(ValueError):
 
 
 GRAD_SYNCS = ("powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref", "local-sgd-nesterov",
-              "local-adamw")
+              "local-adamw", "topk")
 PSGD_ENGINE_SYNCS = ("powersgd", "powersgd-adamw")  # the fused native engine (parallel/powersgd.py)
 TASKS = ("cifar", "imdb", "mlp")
 GRAPH_MODES = ("auto", "full", "piecewise", "none")
@@ -117,6 +117,8 @@ class TrainConfig:
     adam_beta2: float = 0.999
     adam_eps: float = 1e-8
     decay_1d: bool = True  # False: biases, LayerNorm / BatchNorm weights (tensors of <= 1 dimension) do not decay
+    # grad_sync="topk" (parallel/topk.py): the fraction of the parameters each rank sends per step
+    topk_ratio: float = 0.01  # k = max(1, ceil(topk_ratio * parameters)), 0 < ratio <= 1
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -213,7 +215,11 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         c["optimizer"] = "adamw"
     elif c["optimizer"] == "adamw" and c["grad_sync"] not in ADAMW_GRAD_SYNCS:
         raise ConfigError(f"optimizer='adamw' is not available with grad_sync={c['grad_sync']!r} (the fused PowerSGD "
-                          f"engine and the local optimisers have no AdamW); allowed: {list(ADAMW_GRAD_SYNCS)}")
+                          f"engine, top-k and the local optimisers have no AdamW); allowed: {list(ADAMW_GRAD_SYNCS)}")
+    if c["grad_sync"] == "topk" and not 0 < c["topk_ratio"] <= 1:  # NaN fails the comparison too
+        raise ConfigError(f"topk_ratio = {c['topk_ratio']} must lie in (0, 1]")
+    if c["grad_sync"] == "topk" and c["overlap"]:
+        raise ConfigError("grad_sync='topk' has no backward overlap: the global selection needs every gradient")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too
         raise ConfigError(f"max_grad_norm = {c['max_grad_norm']} must be >= 0 (0 = off, inf = measure only)")
     if c["max_grad_norm"] > 0 and c["grad_sync"] in PSGD_ENGINE_SYNCS and c["overlap"]:

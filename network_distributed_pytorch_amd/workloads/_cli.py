@@ -17,7 +17,7 @@ norm, ops/gradclip.py; ``inf`` only measures it), ``-label_smoothing`` (ops/loss
 ``-mix_prob`` (mixup / CutMix of the byte-image batches, ops/image_batch.py; needs ``-data_root``),
 ``-ema_decay`` / ``-ema_warmup`` (exponential moving average of the weights, ops/ema.py), ``-optimizer`` /
 ``-adam_beta1`` / ``-adam_beta2`` / ``-adam_eps`` / ``-decay_1d`` (fused AdamW behind the gradient sync,
-ops/adamw.py).
+ops/adamw.py), ``-topk_ratio`` (the fraction of the parameters ``-grad_sync topk`` sends, parallel/topk.py).
 """
 from __future__ import annotations
 
@@ -40,7 +40,8 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-model", type=str, default=None)
     p.add_argument("-num_classes", type=int, default=None)
     p.add_argument("-grad_sync", type=str, default=None,
-                   choices=[None, "powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref"])
+                   choices=[None, "powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref",
+                            "topk"])
     p.add_argument("-rank_r", type=int, default=None, help="PowerSGD compression rank")
     p.add_argument("-batch", type=int, default=None, help="global batch")
     p.add_argument("-lr", type=float, default=None)
@@ -97,6 +98,8 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-adam_eps", type=float, default=None, help="AdamW eps > 0 (default 1e-8)")
     p.add_argument("-decay_1d", type=int, default=None, choices=[None, 0, 1],
                    help="AdamW: 0 exempts biases and LayerNorm / BatchNorm weights from the decay (default 1)")
+    p.add_argument("-topk_ratio", type=float, default=None,
+                   help="grad_sync topk: fraction of the parameters each rank sends per step, in (0, 1] (default 0.01)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -114,7 +117,7 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay",
         "max_grad_norm": "max_grad_norm", "label_smoothing": "label_smoothing", "mix": "mix",
         "mix_prob": "mix_prob", "ema_decay": "ema_decay", "optimizer": "optimizer", "adam_beta1": "adam_beta1",
-        "adam_beta2": "adam_beta2", "adam_eps": "adam_eps"}
+        "adam_beta2": "adam_beta2", "adam_eps": "adam_eps", "topk_ratio": "topk_ratio"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
