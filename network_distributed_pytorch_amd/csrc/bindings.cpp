@@ -1640,6 +1640,51 @@ void topk_update(torch::Tensor x, torch::Tensor b, torch::Tensor gathered, int64
   check_launch("launch_topk_update");
 }
 
+// scaled-sign compression (signsgd.hip): flat fp32 arenas, the int32 [nb][2] block table SignCore built
+// and uploaded, out = int32 [nb * 65], gathered = int32 [world][nb * 65].  No allocation, no sync:
+// capture-safe.
+void sign_check(const torch::Tensor& a, const torch::Tensor& b, const torch::Tensor& table, int64_t nb,
+                const char* who) {
+  const int64_t n = a.numel();
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), who, ": 1 <= n < 2^31 required");
+  TORCH_CHECK(nb >= 1 && nb <= n, who, ": 1 <= nb <= n required, got nb = ", nb);
+  for (const torch::Tensor* t : {&a, &b}) {
+    check_f32(*t, who);
+    TORCH_CHECK(t->numel() == n && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, who,
+                ": both arenas must have ", n, " elements and be 16-byte aligned");
+  }
+  check_dev(table, who);
+  TORCH_CHECK(table.scalar_type() == torch::kInt32 && table.numel() == 2 * nb && table.is_contiguous(), who,
+              ": the table is contiguous int32 [nb][2]");
+}
+
+// t: contiguous int32 of exactly `numel` elements
+const int32_t* sign_i32(const torch::Tensor& t, int64_t numel, const char* who, const char* what) {
+  check_dev(t, who);
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.numel() == numel && t.is_contiguous(), who, ": ", what,
+              " must be contiguous int32 of ", numel, " elements");
+  return t.data_ptr<int32_t>();
+}
+
+void sign_pack(torch::Tensor g, torch::Tensor e, torch::Tensor table, int64_t nb, torch::Tensor out) {
+  sign_check(g, e, table, nb, "sign_pack");
+  auto* o = const_cast<int32_t*>(sign_i32(out, nb * ndp::kSignWords, "sign_pack", "out [nb * 65]"));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0, "sign_pack: out must be 16-byte aligned");
+  ndp::launch_sign_pack(g.data_ptr<float>(), e.data_ptr<float>(), e.numel(), table.data_ptr<int32_t>(), nb, o,
+                        cur_stream());
+  check_launch("launch_sign_pack");
+}
+
+void sign_update(torch::Tensor x, torch::Tensor b, torch::Tensor table, int64_t nb, torch::Tensor gathered,
+                 int64_t world, double lr, double lam, c10::optional<torch::Tensor> hyper) {
+  sign_check(x, b, table, nb, "sign_update");
+  TORCH_CHECK(world >= 1 && world < (1 << 24), "sign_update: 1 <= world < 2^24");
+  const int32_t* gp = sign_i32(gathered, world * nb * ndp::kSignWords, "sign_update", "gathered [world][nb * 65]");
+  ndp::launch_sign_update(x.data_ptr<float>(), b.data_ptr<float>(), x.numel(), table.data_ptr<int32_t>(), nb, gp,
+                          (int)world, (float)lr, (float)lam, hyper_ptr(hyper), cur_stream());
+  check_launch("launch_sign_update");
+}
+
 // batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
 // [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
 // shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
@@ -2121,6 +2166,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_update", &topk_update, py::arg("x"), py::arg("b"), py::arg("gathered"), py::arg("k"), py::arg("world"),
         py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
   m.def("topk_scratch_words", &ndp::topk_scratch_words);
+  m.def("sign_pack", &sign_pack, py::arg("g"), py::arg("e"), py::arg("table"), py::arg("nb"), py::arg("out"));
+  m.def("sign_update", &sign_update, py::arg("x"), py::arg("b"), py::arg("table"), py::arg("nb"), py::arg("gathered"),
+        py::arg("world"), py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));

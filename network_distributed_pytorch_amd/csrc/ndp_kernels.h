@@ -426,6 +426,22 @@ void launch_topk_select(const float* g, float* e, int64_t n, int64_t k, uint32_t
 // device block [lr, weight_decay, 0, 0], or null (lr by value, no decay).
 void launch_topk_update(float* x, float* b, int64_t n, const int32_t* gathered, int64_t k, int world, float lr,
                         float lam, const float* hyper, hipStream_t s);
+
+// ---- scaled-sign compression with error feedback (signsgd.hip) --------------------------------
+// Flat fp32 arenas of n < 2^31 elements, 16-byte aligned.  table: int32 [nb][2] = (off_j, len_j) with
+// off_j a multiple of 16, 1 <= len_j <= kSignBlock and off_j + len_j <= n (nb >= 1 blocks; the caller
+// built it and vouches for it).  A wire buffer is int32 [nb * kSignWords]: nb * 64 sign words, then
+// nb words bits(s_j); the bit layout is in signsgd.hip's header.
+constexpr int kSignBlock = 2048;                 // elements per block and workgroup
+constexpr int kSignWords = kSignBlock / 32 + 1;  // wire words per block
+// m = g + e, its signs and per-block mean magnitude into out, e = m - c.
+void launch_sign_pack(const float* g, float* e, int64_t n, const int32_t* table, int64_t nb, int32_t* out,
+                      hipStream_t s);
+// gathered: int32 [world][nb * kSignWords], one wire buffer per rank; x, b updated in place by the element
+// rule with o = (sum over ranks in rank order of c) / world.  hyper: the device block
+// [lr, weight_decay, 0, 0], or null (lr by value, no decay).
+void launch_sign_update(float* x, float* b, int64_t n, const int32_t* table, int64_t nb, const int32_t* gathered,
+                        int world, float lr, float lam, const float* hyper, hipStream_t s);
 }  // namespace ndp
 
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------

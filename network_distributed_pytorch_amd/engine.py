@@ -406,6 +406,8 @@ def run_task(config) -> Dict[str, Any]:
         extra = {"overlap": config.get("overlap")}
     elif config["grad_sync"] == "topk":
         extra = {"overlap": config.get("overlap"), "topk_ratio": float(config.get("topk_ratio", 0.01))}
+    elif config["grad_sync"] == "signsgd":
+        extra = {"overlap": config.get("overlap")}
     max_grad_norm = float(config.get("max_grad_norm") or 0.0)
     if max_grad_norm > 0:  # off: build_grad_sync is called exactly as before
         extra["max_grad_norm"] = max_grad_norm

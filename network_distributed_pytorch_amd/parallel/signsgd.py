@@ -1,0 +1,171 @@
+"""Scaled-sign gradient compression with error feedback as a :class:`GradSync` (``grad_sync="signsgd"``).
+
+Every rank sends one bit per coordinate of ``m = g + e`` (its sign) and one fp32 magnitude per block
+of 2048 elements of a tensor (the block's mean ``|m|``), feeds ``m - c`` back through the error memory
+``e``, all-gathers the bit buffers and applies momentum SGD to the decompressed average
+(ops/signsgd.py has the rule; EF-SignSGD of Karimireddy et al. 2019, the PowerSGD paper's "Sign+Norm";
+the momentum sits behind the decompression, as in PowerSGD's Algorithm 2, so the compressors compare).
+
+* Arenas ``x`` / ``g`` / ``buf`` / ``e`` laid out like the top-k arm's (reverse parameter order, each
+  parameter at a 16-element-aligned offset, padding zero and never touched by the two kernels).
+  Parameters are re-pointed into ``x``; the native backwards write into ``g`` (ops/gradarena.py) and
+  one :class:`SegPlan` flatten copies the gradients that did not land there.
+* The block table (each parameter cut into blocks of 2048, its last one ragged) is fixed at
+  construction: every buffer and the collective have a static size, so the step can be captured.
+* One step = [clip this rank's ``g``] + flatten + 1 pack launch, ONE all-gather of ``int32[65 nb]``
+  per rank (none at world size 1), 1 update launch, the EMA tail.  ``bytes_per_step = 260 nb``: a
+  fixed ratio of about 31 with no knob.
+* No backward overlap here: the blocks are per tensor, so a tensor could be packed as soon as its
+  gradient is final, but that is out of scope (``overlap=True`` raises).
+"""
+from __future__ import annotations
+
+from typing import List, Optional
+
+import torch
+
+from ..ops import SegPlan, capturing, gradarena, gradfinish
+from ..ops.hyper import HyperState
+from ..ops.signsgd import SignCore
+from .comm import Communicator
+from .sync import GradSync
+
+__all__ = ["SignSync"]
+
+
+class SignSync(HyperState, GradSync):
+    _arm = "signsgd arm"
+
+    def __init__(self, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
+                 momentum: float = 0.9, broadcast_params: bool = True, overlap: Optional[bool] = None,
+                 weight_decay: float = 0.0, max_grad_norm: float = 0.0):
+        assert weight_decay >= 0, "weight_decay >= 0"
+        if overlap:
+            raise ValueError("signsgd: overlap=True is not available (the per-tensor blocks would allow packing a "
+                             "tensor as soon as its gradient is final, but that is out of scope here)")
+        self.model = model
+        self.comm = comm if comm is not None else Communicator()
+        self.momentum = float(momentum)
+        self.params: List[torch.nn.Parameter] = [p for p in model.parameters() if p.requires_grad]
+        self.device = self.params[0].device
+        self._init_hyper(float(lr), float(weight_decay), block=self.device.type == "cuda")
+        offs, o = {}, 0
+        for p in reversed(self.params):
+            offs[id(p)] = o
+            o += (p.numel() + 15) // 16 * 16
+        self.numel, self.offsets = o, offs
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.x, self.g, self.buf, self.e = (torch.zeros(o, **f32) for _ in range(4))
+        with torch.no_grad():
+            for p in self.params:
+                v = self.x[offs[id(p)]: offs[id(p)] + p.numel()].view_as(p)
+                v.copy_(p.data)
+                p.data = v
+                p.grad = None
+        if broadcast_params:
+            self.comm.broadcast(self.x, src=0)
+        if self.device.type == "cuda":
+            for p in self.params:
+                gradarena.register(p, self.g, offs[id(p)])
+        self.world = self.comm.world_size if self.comm.active else 1
+        self.core = SignCore(self.device, [(offs[id(p)], p.numel()) for p in self.params], o, self.world)
+        self._seg = SegPlan([], self.device, capacity=len(self.params))
+        self.step_count = 0
+        self._init_clip(max_grad_norm, self.device, capacity=1, blocks=(o + 2047) // 2048)
+        if self.clip is not None:
+            self.clip.bind([self.g])
+
+    @property
+    def flat_weights(self) -> torch.Tensor:
+        return self.x
+
+    @property
+    def bytes_per_step(self) -> int:
+        return 4 * self.core.words
+
+    @property
+    def collectives_per_step(self) -> int:
+        return 1 if self.comm.active else 0
+
+    def collective_payloads(self):
+        """Bytes this rank contributes to the step's one all-gather (link-model input)."""
+        return [4 * self.core.words]
+
+    def check_errors(self):
+        self.comm.check()
+
+    # -- the three phases --------------------------------------------------------------------------
+    @torch.no_grad()
+    def phase_pack(self):
+        gradfinish.flush()  # deferred conv grad-W sums / folds
+        specs = []
+        for p in self.params:
+            o = self.offsets[id(p)]
+            dst = self.g[o: o + p.numel()]
+            if p.grad is None:  # unused parameter: zero gradient, in place
+                p.grad = dst.view_as(p)
+                p.grad.zero_()
+            if p.grad.data_ptr() != dst.data_ptr():
+                specs.append((p.grad.reshape(-1), dst, 1, 0, 1.0))
+        self._seg.set(specs)
+        self._seg.run()  # one flatten launch (only the gradients that did not land in the arena)
+        if self.clip is not None:  # this rank's own gradient, before m = g + e
+            self.clip.bind([self.g])
+            self.clip.run(self.max_grad_norm)
+        self.core.compress(self.g, self.e)
+
+    @torch.no_grad()
+    def phase_gather(self):
+        if self.comm.has_traffic:
+            self.comm.all_gather_into(self.core.gathered, self.core.out)
+
+    @torch.no_grad()
+    def phase_update(self):
+        self.core.update(self.x, self.buf, self.core.gathered, self.lr, self.momentum, self.weight_decay,
+                         self._hyper_arg())
+        self._after_update()  # the EMA reads the weights the update wrote: same stream, behind it
+        self.count_step()
+
+    def phases(self):
+        return [(self.phase_pack, False), (self.phase_gather, True), (self.phase_update, False)]
+
+    def zero_grad(self, set_to_none: bool = True):
+        for p in self.params:
+            p.grad = None
+        gradarena.release(self.params)
+
+    def step(self) -> int:
+        self.phase_pack()
+        self.phase_gather()
+        self.phase_update()
+        return 8 * self.bytes_per_step
+
+    def count_step(self):
+        if not capturing():
+            self.step_count += 1
+
+    # -- state ---------------------------------------------------------------------------------------
+    def snapshot(self):
+        return {"x": self.x.clone(), "buf": self.buf.clone(), "e": self.e.clone(), "step_count": self.step_count,
+                **self._snapshot_extras()}
+
+    def restore(self, snap):
+        self.x.copy_(snap["x"])
+        self.buf.copy_(snap["buf"])
+        self.e.copy_(snap["e"])
+        self.step_count = snap["step_count"]
+        self._restore_extras(snap)
+
+    def state_dict(self):
+        return {"error_memory": self.e.detach().cpu().clone(), "momentum_buffer": self.buf.detach().cpu().clone(),
+                "lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay,
+                "block": self.core.block}
+
+    def load_state_dict(self, sd):
+        if int(sd["block"]) != self.core.block:
+            raise ValueError(f"signsgd arm: the checkpoint was written with block = {sd['block']}, this sync has "
+                             f"block = {self.core.block}")
+        self.e.copy_(sd["error_memory"])
+        self.buf.copy_(sd["momentum_buffer"])
+        self.momentum = float(sd["momentum"])
+        self._load_hyper(float(sd["lr"]), float(sd.get("weight_decay", 0.0)))

@@ -16,6 +16,8 @@
                    (ddp_guide_cifar10/ddp_init.py:57-62,111,124-125).
 ``topk``           exact global top-k of ``g + e`` with error feedback (:class:`TopKSync`): 5 select
                    launches, one all-gather of ``(idx, val)``, one decompress + momentum + SGD launch.
+``signsgd``        scaled sign of ``g + e`` with error feedback (:class:`SignSync`): 1 pack launch (one
+                   bit per element, one fp32 magnitude per block of 2048), one all-gather, 1 update launch.
 =================  ===========================================================================
 
 Every strategy has ``set_hyper(lr, weight_decay)``: the learning rate and the L2 weight decay of

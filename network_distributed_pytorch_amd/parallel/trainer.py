@@ -11,6 +11,7 @@
 ``local-sgd-nesterov``  :class:`LocalOptimizer`, no communication
 ``local-adamw``         :class:`LocalOptimizer`, no communication
 ``topk``                :class:`TopKSync`: exact global top-k with error feedback, one all-gather (parallel/topk.py)
+``signsgd``             :class:`SignSync`: scaled sign with error feedback, one all-gather (parallel/signsgd.py)
 ======================  =====================================================================
 """
 from __future__ import annotations
@@ -23,10 +24,12 @@ from ..ops.adamw import FusedAdamW, check_adam_args
 from .comm import Communicator
 from .ddp import BucketedDataParallel, average_gradients
 from .powersgd import PowerSGDOptimizer, PowerSGDReducer, powersgd_bytes_per_step
+from .signsgd import SignSync
 from .sync import GradSync
 from .topk import TopKSync
 
-__all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "TopKSync", "ADAMW_SYNCS"]
+__all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "TopKSync", "SignSync",
+           "ADAMW_SYNCS"]
 
 ADAMW_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # the arms that take optimizer="adamw"
 
@@ -206,7 +209,8 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
             raise ValueError(f"grad sync {kind!r} has no AdamW: the fused PowerSGD update kernels decompress, feed "
                              f"back and step in one register-pinned pass (an Adam variant of them is future work), "
                              f"the top-k update kernel is momentum SGD only and "
-                             f"the local optimisers are fixed recipes; use one of {', '.join(ADAMW_SYNCS)}")
+                             f"the local optimisers are fixed recipes; use one of {', '.join(ADAMW_SYNCS)} "
+                             f"(the scaled-sign update kernel of 'signsgd' is momentum SGD only as well)")
         b1, b2, eps = check_adam_args(betas, eps)
         adam = {"optimizer": "adamw", "betas": (b1, b2), "eps": eps, "decay_1d": bool(decay_1d)}
     if kind == "powersgd":
@@ -224,6 +228,8 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
     if kind == "topk":
         return TopKSync(model, comm, lr=lr, momentum=momentum, topk_ratio=topk_ratio, overlap=kw.get("overlap"),
                         **clip)
+    if kind == "signsgd":
+        return SignSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), **clip)
     raise ValueError(f"unknown grad sync {kind!r}")
 
 
