@@ -1685,6 +1685,36 @@ void sign_update(torch::Tensor x, torch::Tensor b, torch::Tensor table, int64_t 
   check_launch("launch_sign_update");
 }
 
+// block-quantised compression (quant.hip): the arenas and the block table of the scaled-sign arm,
+// bits in {2, 4, 8}, out = int32 [quant_row_words(nb, bits)], gathered = int32 [world] rows of it.  No
+// allocation, no sync: capture-safe.
+void quant_check_bits(int64_t bits, const char* who) {
+  TORCH_CHECK(bits == 2 || bits == 4 || bits == 8, who, ": bits must be 2, 4 or 8, got ", bits);
+}
+
+void quant_pack(torch::Tensor g, torch::Tensor e, torch::Tensor table, int64_t nb, int64_t bits, torch::Tensor out) {
+  sign_check(g, e, table, nb, "quant_pack");
+  quant_check_bits(bits, "quant_pack");
+  auto* o = const_cast<int32_t*>(sign_i32(out, ndp::quant_row_words(nb, (int)bits), "quant_pack", "out [row_words]"));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0, "quant_pack: out must be 16-byte aligned");
+  ndp::launch_quant_pack(g.data_ptr<float>(), e.data_ptr<float>(), e.numel(), table.data_ptr<int32_t>(), nb, (int)bits,
+                         o, cur_stream());
+  check_launch("launch_quant_pack");
+}
+
+void quant_update(torch::Tensor x, torch::Tensor b, torch::Tensor table, int64_t nb, int64_t bits,
+                  torch::Tensor gathered, int64_t world, double lr, double lam, c10::optional<torch::Tensor> hyper) {
+  sign_check(x, b, table, nb, "quant_update");
+  quant_check_bits(bits, "quant_update");
+  TORCH_CHECK(world >= 1 && world < (1 << 24), "quant_update: 1 <= world < 2^24");
+  const int32_t* gp = sign_i32(gathered, world * ndp::quant_row_words(nb, (int)bits), "quant_update",
+                               "gathered [world][row_words]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(gp) % 16 == 0, "quant_update: gathered must be 16-byte aligned");
+  ndp::launch_quant_update(x.data_ptr<float>(), b.data_ptr<float>(), x.numel(), table.data_ptr<int32_t>(), nb,
+                           (int)bits, gp, (int)world, (float)lr, (float)lam, hyper_ptr(hyper), cur_stream());
+  check_launch("launch_quant_update");
+}
+
 // batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
 // [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
 // shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
@@ -2169,6 +2199,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sign_pack", &sign_pack, py::arg("g"), py::arg("e"), py::arg("table"), py::arg("nb"), py::arg("out"));
   m.def("sign_update", &sign_update, py::arg("x"), py::arg("b"), py::arg("table"), py::arg("nb"), py::arg("gathered"),
         py::arg("world"), py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
+  m.def("quant_pack", &quant_pack, py::arg("g"), py::arg("e"), py::arg("table"), py::arg("nb"), py::arg("bits"),
+        py::arg("out"));
+  m.def("quant_update", &quant_update, py::arg("x"), py::arg("b"), py::arg("table"), py::arg("nb"), py::arg("bits"),
+        py::arg("gathered"), py::arg("world"), py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));

@@ -442,6 +442,22 @@ void launch_sign_pack(const float* g, float* e, int64_t n, const int32_t* table,
 // [lr, weight_decay, 0, 0], or null (lr by value, no decay).
 void launch_sign_update(float* x, float* b, int64_t n, const int32_t* table, int64_t nb, const int32_t* gathered,
                         int world, float lr, float lam, const float* hyper, hipStream_t s);
+
+// ---- block-quantised compression with error feedback (quant.hip) --------------------------------
+// The arenas and the block table of the scaled-sign arm.  bits is 2, 4 or 8; a code is bits wide and
+// block j owns the 64 * bits code words [64 bits j, 64 bits (j + 1)) of a rank's row, element t at bit
+// (t bits) & 31 of word (t bits) >> 5 of them.  A row is int32 [quant_row_words(nb, bits)]: the code
+// words, nb scale words bits(s_j), zero padding up to a multiple of 4 words (every row of the gathered
+// buffer starts 16-byte aligned).
+constexpr int64_t quant_row_words(int64_t nb, int bits) { return (nb * (64 * bits + 1) + 3) & ~int64_t(3); }
+// m = g + e, its absmax-scaled codes and the per-block scale into out (a whole row, padding included),
+// e = m - c.  A bits outside {2, 4, 8} launches nothing (the binding has refused it).
+void launch_quant_pack(const float* g, float* e, int64_t n, const int32_t* table, int64_t nb, int bits, int32_t* out,
+                       hipStream_t s);
+// gathered: int32 [world][quant_row_words(nb, bits)], one row per rank; x, b updated in place by the
+// element rule with o = (sum over ranks in rank order of (u - L) s) / world.  hyper as for launch_sign_update.
+void launch_quant_update(float* x, float* b, int64_t n, const int32_t* table, int64_t nb, int bits,
+                         const int32_t* gathered, int world, float lr, float lam, const float* hyper, hipStream_t s);
 }  // namespace ndp
 
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------

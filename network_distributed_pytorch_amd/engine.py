@@ -83,6 +83,8 @@ def default_config(**over) -> Dict[str, Any]:
         optimizer="sgd", adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, decay_1d=True,
         # grad_sync="topk" (parallel/topk.py): the fraction of the parameters each rank sends per step
         topk_ratio=0.01,
+        # grad_sync="quant" (parallel/quant.py): bits per coordinate, 2 (ternary), 4 or 8
+        quant_bits=4,
     )
     cfg.update(over)
     return cfg
@@ -408,6 +410,8 @@ def run_task(config) -> Dict[str, Any]:
         extra = {"overlap": config.get("overlap"), "topk_ratio": float(config.get("topk_ratio", 0.01))}
     elif config["grad_sync"] == "signsgd":
         extra = {"overlap": config.get("overlap")}
+    elif config["grad_sync"] == "quant":
+        extra = {"overlap": config.get("overlap"), "quant_bits": int(config.get("quant_bits", 4))}
     max_grad_norm = float(config.get("max_grad_norm") or 0.0)
     if max_grad_norm > 0:  # off: build_grad_sync is called exactly as before
         extra["max_grad_norm"] = max_grad_norm

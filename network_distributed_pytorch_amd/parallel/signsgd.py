@@ -68,12 +68,16 @@ class SignSync(HyperState, GradSync):
             for p in self.params:
                 gradarena.register(p, self.g, offs[id(p)])
         self.world = self.comm.world_size if self.comm.active else 1
-        self.core = SignCore(self.device, [(offs[id(p)], p.numel()) for p in self.params], o, self.world)
+        self.core = self._build_core([(offs[id(p)], p.numel()) for p in self.params], o)
         self._seg = SegPlan([], self.device, capacity=len(self.params))
         self.step_count = 0
         self._init_clip(max_grad_norm, self.device, capacity=1, blocks=(o + 2047) // 2048)
         if self.clip is not None:
             self.clip.bind([self.g])
+
+    def _build_core(self, segments, n):
+        """The compressor over the arenas (parallel/quant.py builds another one here)."""
+        return SignCore(self.device, segments, n, self.world)
 
     @property
     def flat_weights(self) -> torch.Tensor:
@@ -163,7 +167,7 @@ class SignSync(HyperState, GradSync):
 
     def load_state_dict(self, sd):
         if int(sd["block"]) != self.core.block:
-            raise ValueError(f"signsgd arm: the checkpoint was written with block = {sd['block']}, this sync has "
+            raise ValueError(f"{self._arm}: the checkpoint was written with block = {sd['block']}, this sync has "
                              f"block = {self.core.block}")
         self.e.copy_(sd["error_memory"])
         self.buf.copy_(sd["momentum_buffer"])

@@ -18,6 +18,9 @@
                    launches, one all-gather of ``(idx, val)``, one decompress + momentum + SGD launch.
 ``signsgd``        scaled sign of ``g + e`` with error feedback (:class:`SignSync`): 1 pack launch (one
                    bit per element, one fp32 magnitude per block of 2048), one all-gather, 1 update launch.
+``quant``          2/4/8-bit absmax-scaled codes of ``g + e`` with error feedback (:class:`QuantSync`): 1 pack
+                   launch (``quant_bits`` per element, one fp32 scale per block of 2048), one all-gather, 1
+                   update launch.
 =================  ===========================================================================
 
 Every strategy has ``set_hyper(lr, weight_decay)``: the learning rate and the L2 weight decay of

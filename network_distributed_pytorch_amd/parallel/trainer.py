@@ -12,6 +12,7 @@
 ``local-adamw``         :class:`LocalOptimizer`, no communication
 ``topk``                :class:`TopKSync`: exact global top-k with error feedback, one all-gather (parallel/topk.py)
 ``signsgd``             :class:`SignSync`: scaled sign with error feedback, one all-gather (parallel/signsgd.py)
+``quant``               :class:`QuantSync`: 2/4/8-bit block quantisation with error feedback, one all-gather (parallel/quant.py)
 ======================  =====================================================================
 """
 from __future__ import annotations
@@ -24,12 +25,13 @@ from ..ops.adamw import FusedAdamW, check_adam_args
 from .comm import Communicator
 from .ddp import BucketedDataParallel, average_gradients
 from .powersgd import PowerSGDOptimizer, PowerSGDReducer, powersgd_bytes_per_step
+from .quant import QuantSync
 from .signsgd import SignSync
 from .sync import GradSync
 from .topk import TopKSync
 
 __all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "TopKSync", "SignSync",
-           "ADAMW_SYNCS"]
+           "QuantSync", "ADAMW_SYNCS"]
 
 ADAMW_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # the arms that take optimizer="adamw"
 
@@ -191,7 +193,7 @@ def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
 def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                     momentum: float = 0.9, rank: int = 4, bucket_mb: Optional[float] = None, seed: int = 714,
                     max_grad_norm: float = 0.0, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
-                    decay_1d: bool = True, topk_ratio: float = 0.01, **kw):
+                    decay_1d: bool = True, topk_ratio: float = 0.01, quant_bits: int = 4, **kw):
     comm = comm if comm is not None else Communicator()
     clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
     adam = {}  # optimizer="sgd": every constructor call as before
@@ -210,7 +212,8 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
                              f"back and step in one register-pinned pass (an Adam variant of them is future work), "
                              f"the top-k update kernel is momentum SGD only and "
                              f"the local optimisers are fixed recipes; use one of {', '.join(ADAMW_SYNCS)} "
-                             f"(the scaled-sign update kernel of 'signsgd' is momentum SGD only as well)")
+                             f"(the scaled-sign update kernel of 'signsgd' and the block-quantised one of 'quant' are momentum "
+                             f"SGD only as well)")
         b1, b2, eps = check_adam_args(betas, eps)
         adam = {"optimizer": "adamw", "betas": (b1, b2), "eps": eps, "decay_1d": bool(decay_1d)}
     if kind == "powersgd":
@@ -230,6 +233,9 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
                         **clip)
     if kind == "signsgd":
         return SignSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), **clip)
+    if kind == "quant":
+        return QuantSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), quant_bits=quant_bits,
+                         **clip)
     raise ValueError(f"unknown grad sync {kind!r}")
 
 

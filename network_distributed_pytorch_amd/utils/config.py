@@ -24,7 +24,7 @@ class ConfigError(ValueError):
 
 
 GRAD_SYNCS = ("powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref", "local-sgd-nesterov",
-              "local-adamw", "topk", "signsgd")
+              "local-adamw", "topk", "signsgd", "quant")
 PSGD_ENGINE_SYNCS = ("powersgd", "powersgd-adamw")  # the fused native engine (parallel/powersgd.py)
 TASKS = ("cifar", "imdb", "mlp")
 GRAPH_MODES = ("auto", "full", "piecewise", "none")
@@ -119,6 +119,8 @@ class TrainConfig:
     decay_1d: bool = True  # False: biases, LayerNorm / BatchNorm weights (tensors of <= 1 dimension) do not decay
     # grad_sync="topk" (parallel/topk.py): the fraction of the parameters each rank sends per step
     topk_ratio: float = 0.01  # k = max(1, ceil(topk_ratio * parameters)), 0 < ratio <= 1
+    # grad_sync="quant" (parallel/quant.py): bits per coordinate, 2 (ternary), 4 or 8
+    quant_bits: int = 4
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -215,7 +217,7 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         c["optimizer"] = "adamw"
     elif c["optimizer"] == "adamw" and c["grad_sync"] not in ADAMW_GRAD_SYNCS:
         raise ConfigError(f"optimizer='adamw' is not available with grad_sync={c['grad_sync']!r} (the fused PowerSGD "
-                          f"engine, top-k, scaled sign and the local optimisers have no AdamW); "
+                          f"engine, top-k, scaled sign, block quantisation and the local optimisers have no AdamW); "
                           f"allowed: {list(ADAMW_GRAD_SYNCS)}")
     if c["grad_sync"] == "topk" and not 0 < c["topk_ratio"] <= 1:  # NaN fails the comparison too
         raise ConfigError(f"topk_ratio = {c['topk_ratio']} must lie in (0, 1]")
@@ -223,6 +225,10 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError("grad_sync='topk' has no backward overlap: the global selection needs every gradient")
     if c["grad_sync"] == "signsgd" and c["overlap"]:
         raise ConfigError("grad_sync='signsgd' has no backward overlap (per-tensor packing is out of scope)")
+    if c["grad_sync"] == "quant" and c["quant_bits"] not in (2, 4, 8):
+        raise ConfigError(f"quant_bits = {c['quant_bits']} must be 2, 4 or 8")
+    if c["grad_sync"] == "quant" and c["overlap"]:
+        raise ConfigError("grad_sync='quant' has no backward overlap (per-tensor packing is out of scope)")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too
         raise ConfigError(f"max_grad_norm = {c['max_grad_norm']} must be >= 0 (0 = off, inf = measure only)")
     if c["max_grad_norm"] > 0 and c["grad_sync"] in PSGD_ENGINE_SYNCS and c["overlap"]:

@@ -17,7 +17,8 @@ norm, ops/gradclip.py; ``inf`` only measures it), ``-label_smoothing`` (ops/loss
 ``-mix_prob`` (mixup / CutMix of the byte-image batches, ops/image_batch.py; needs ``-data_root``),
 ``-ema_decay`` / ``-ema_warmup`` (exponential moving average of the weights, ops/ema.py), ``-optimizer`` /
 ``-adam_beta1`` / ``-adam_beta2`` / ``-adam_eps`` / ``-decay_1d`` (fused AdamW behind the gradient sync,
-ops/adamw.py), ``-topk_ratio`` (the fraction of the parameters ``-grad_sync topk`` sends, parallel/topk.py).
+ops/adamw.py), ``-topk_ratio`` (the fraction of the parameters ``-grad_sync topk`` sends, parallel/topk.py),
+``-quant_bits`` (the code width of ``-grad_sync quant``, parallel/quant.py).
 """
 from __future__ import annotations
 
@@ -41,7 +42,7 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
     p.add_argument("-num_classes", type=int, default=None)
     p.add_argument("-grad_sync", type=str, default=None,
                    choices=[None, "powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref",
-                            "topk", "signsgd"])
+                            "topk", "signsgd", "quant"])
     p.add_argument("-rank_r", type=int, default=None, help="PowerSGD compression rank")
     p.add_argument("-batch", type=int, default=None, help="global batch")
     p.add_argument("-lr", type=float, default=None)
@@ -100,6 +101,8 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
                    help="AdamW: 0 exempts biases and LayerNorm / BatchNorm weights from the decay (default 1)")
     p.add_argument("-topk_ratio", type=float, default=None,
                    help="grad_sync topk: fraction of the parameters each rank sends per step, in (0, 1] (default 0.01)")
+    p.add_argument("-quant_bits", type=int, default=None, choices=[None, 2, 4, 8],
+                   help="grad_sync quant: bits per coordinate (default 4; 2 is ternary)")
     p.add_argument("-trace", action="store_true", help="per-phase HIP-event timings into the JSONL log")
     p.add_argument("-quiet", action="store_true")
     return p
@@ -117,7 +120,8 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "lr_milestones": "lr_milestones", "lr_gamma": "lr_gamma", "weight_decay": "weight_decay",
         "max_grad_norm": "max_grad_norm", "label_smoothing": "label_smoothing", "mix": "mix",
         "mix_prob": "mix_prob", "ema_decay": "ema_decay", "optimizer": "optimizer", "adam_beta1": "adam_beta1",
-        "adam_beta2": "adam_beta2", "adam_eps": "adam_eps", "topk_ratio": "topk_ratio"}
+        "adam_beta2": "adam_beta2", "adam_eps": "adam_eps", "topk_ratio": "topk_ratio",
+        "quant_bits": "quant_bits"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):

@@ -44,13 +44,13 @@ STAGES = ("pack", "update")
 
 
 class Arm:
-    def __init__(self, kind, config, batch, device, seq_len):
-        self.kind = kind
+    def __init__(self, kind, config, batch, device, seq_len, label=None, **sync_kw):
+        self.kind, self.label = kind, label or kind
         model_name, rank = CONFIGS[config]
         bert = model_name == "distilbert"
         torch.manual_seed(0)
         self.model = model = build_model(model_name, 2 if bert else 1000).to(device)
-        self.sync = build_grad_sync(kind, model, lr=5e-5 if bert else 1e-3, momentum=0.9, rank=rank)
+        self.sync = build_grad_sync(kind, model, lr=5e-5 if bert else 1e-3, momentum=0.9, rank=rank, **sync_kw)
         if bert:
             from network_distributed_pytorch_amd.utils.data import SyntheticIMDb
 
@@ -79,81 +79,92 @@ class Arm:
         self.runner.join()
 
 
-def bench_steps(args, device):
+def bench_steps(args, device, specs=None):
+    """``specs``: ``(label, kind, sync keywords)`` per arm; default: ``args.arms``."""
+    specs = specs or [(kind, kind, {}) for kind in args.arms]
     results = []
     for config in args.configs:
         bert = CONFIGS[config][0] == "distilbert"
         for batch in ([args.bert_batch] if bert else args.batch):
-            arms = [Arm(kind, config, batch, device, args.seq_len) for kind in args.arms]
+            arms = [Arm(kind, config, batch, device, args.seq_len, label, **kw) for label, kind, kw in specs]
             for arm in arms:
                 arm.run(args.warmup)
             torch.cuda.synchronize()
-            times = {arm.kind: [] for arm in arms}
+            times = {arm.label: [] for arm in arms}
             for _ in range(args.rounds):  # the arms alternate
                 for arm in arms:
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
                     arm.run(args.steps)
                     torch.cuda.synchronize()
-                    times[arm.kind].append(1e3 * (time.perf_counter() - t0) / args.steps)
+                    times[arm.label].append(1e3 * (time.perf_counter() - t0) / args.steps)
             for arm in arms:
-                t = times[arm.kind]
+                t = times[arm.label]
                 arm.sync.check_errors()
-                results.append({"config": config, "batch": batch, "grad_sync": arm.kind,
+                results.append({"config": config, "batch": batch, "grad_sync": arm.label,
                                 "ms_per_step_mean": statistics.mean(t), "ms_per_step_min": min(t),
                                 "ms_per_step_max": max(t), "rounds": len(t), "steps_per_round": args.steps,
                                 "graph_mode": arm.runner.mode, "bytes_per_step": arm.sync.bytes_per_step,
-                                **({"blocks": arm.sync.core.nb} if arm.kind == "signsgd" else {})})
+                                **({"blocks": arm.sync.core.nb} if arm.kind in ("signsgd", "quant") else {})})
                 print(json.dumps(results[-1]), flush=True)
             del arms
             torch.cuda.empty_cache()
     return results
 
 
+def model_segments(config):
+    """``(segments, n, numel)`` of a configuration's parameters laid out as its sync lays them out."""
+    model_name = CONFIGS[config][0]
+    params = list(build_model(model_name, 2 if model_name == "distilbert" else 1000).parameters())
+    segs, n = [], 0
+    for p in reversed(params):
+        segs.append((n, p.numel()))
+        n += (p.numel() + 15) // 16 * 16
+    return segs, n, sum(c for _, c in segs)
+
+
+def time_launches(core, n, world, reps, device):
+    """Mean HIP-event interval in us of ``core``'s pack and update launch over Gaussian arenas."""
+    g, e, x, b = torch.randn(n, device=device) * 1e-2, torch.zeros(n, device=device), \
+        torch.randn(n, device=device), torch.zeros(n, device=device)
+
+    def rep(events=None):
+        if events is not None:
+            events[0].record()
+        out = core.compress(g, e)
+        if events is not None:
+            events[1].record()
+        if world > 1:  # the other ranks' rows: copies of this rank's, outside the timed intervals
+            core.gathered.copy_(out.expand(world, -1))
+        if events is not None:
+            events[2].record()
+        core.update(x, b, core.gathered, 1e-3, 0.9)
+        if events is not None:
+            events[3].record()
+    for _ in range(10):
+        rep()
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(reps)]
+    torch.cuda.synchronize()
+    for ev in evs:
+        rep(ev)
+    torch.cuda.synchronize()
+    span = {"pack": (0, 1), "update": (2, 3)}
+    return {name: 1e3 * statistics.mean(ev[a].elapsed_time(ev[z]) for ev in evs) for name, (a, z) in span.items()}
+
+
 def bench_kernels(args, device):
     """The two launches alone over flat fp32 arenas laid out like each configuration's sync lays them out."""
     results = []
     for config in args.configs:
-        model_name = CONFIGS[config][0]
-        params = list(build_model(model_name, 2 if model_name == "distilbert" else 1000).parameters())
-        segs, n = [], 0
-        for p in reversed(params):
-            segs.append((n, p.numel()))
-            n += (p.numel() + 15) // 16 * 16
-        numel = sum(c for _, c in segs)
+        segs, n, numel = model_segments(config)
         core = SignCore(device, segs, n, args.world)
-        g, e, x, b = torch.randn(n, device=device) * 1e-2, torch.zeros(n, device=device), \
-            torch.randn(n, device=device), torch.zeros(n, device=device)
-
-        def rep(events=None):
-            if events is not None:
-                events[0].record()
-            out = core.compress(g, e)
-            if events is not None:
-                events[1].record()
-            if args.world > 1:  # the other ranks' rows: copies of this rank's, outside the timed intervals
-                core.gathered.copy_(out.expand(args.world, -1))
-            if events is not None:
-                events[2].record()
-            core.update(x, b, core.gathered, 1e-3, 0.9)
-            if events is not None:
-                events[3].record()
-        for _ in range(10):
-            rep()
-        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.reps)]
-        torch.cuda.synchronize()
-        for ev in evs:
-            rep(ev)
-        torch.cuda.synchronize()
+        us = time_launches(core, n, args.world, args.reps, device)
         wire = 4 * core.words
         need = {"pack": 12 * numel + wire, "update": 16 * numel + args.world * wire}
-        span = {"pack": (0, 1), "update": (2, 3)}
         for name in STAGES:
-            a, z = span[name]
-            us = 1e3 * statistics.mean(ev[a].elapsed_time(ev[z]) for ev in evs)
             results.append({"config": config, "numel": numel, "n": n, "blocks": core.nb, "world": args.world,
-                            "launch": name, "us": us, "bytes_needed": need[name],
-                            "gb_per_s": need[name] / us / 1e3, "wire_bytes": wire, "reps": args.reps})
+                            "launch": name, "us": us[name], "bytes_needed": need[name],
+                            "gb_per_s": need[name] / us[name] / 1e3, "wire_bytes": wire, "reps": args.reps})
             print(json.dumps(results[-1]), flush=True)
     return results
 
