@@ -46,6 +46,8 @@ __device__ __forceinline__ AdamScalars adam_launch_scalars(float b1pow, float b2
                                                            float beta2, float eps, float& p1, float& p2) {
   p1 = __fmul_rn(b1pow, beta1);
   p2 = __fmul_rn(b2pow, beta2);
+  asm volatile("" : "+v"(p1));  // 1 - p is a subtraction of a ROUNDED product (a caller whose only other
+  asm volatile("" : "+v"(p2));  // use of p sits in the block's last writer had it fused into an fma)
   float lw = __fmul_rn(lr, wd);
   asm volatile("" : "+v"(lw));
   AdamScalars S;

@@ -1715,6 +1715,75 @@ void quant_update(torch::Tensor x, torch::Tensor b, torch::Tensor table, int64_t
   check_launch("launch_quant_update");
 }
 
+// AdamW in the flat-arena compressors: the update launches above with a second-moment arena v (as
+// large and as aligned as x), the AdamBlock as 4 int32 words and arrive_ctr_words(grid) zeroed int32
+// tickets (re-armed).  Every range the SGD update bindings refuse is refused here.  No allocation, no
+// sync: capture-safe.
+ndp::EfAdamArgs ef_adam_args(const char* who, const torch::Tensor& x, const torch::Tensor& v,
+                             const torch::Tensor& block, const torch::Tensor& ctr, int64_t grid, double beta1,
+                             double beta2, double eps) {
+  check_f32(v, who);
+  TORCH_CHECK(v.numel() == x.numel() && reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0, who,
+              ": v must have ", x.numel(), " elements and be 16-byte aligned");
+  TORCH_CHECK((float)beta1 >= 0.0f && (float)beta1 < 1.0f && (float)beta2 >= 0.0f && (float)beta2 < 1.0f, who,
+              ": betas must be in [0, 1)");
+  TORCH_CHECK((float)eps > 0.0f, who, ": eps must be > 0 as fp32");
+  return ndp::EfAdamArgs{block4_ptr<ndp::AdamBlock>(block, who), ticket_ptr(ctr, grid, who), (float)beta1,
+                         (float)beta2, (float)eps};
+}
+
+void sign_update_adam(torch::Tensor x, torch::Tensor m, torch::Tensor v, torch::Tensor table, torch::Tensor decays,
+                      int64_t nb, torch::Tensor gathered, int64_t world, double lr, c10::optional<torch::Tensor> hyper,
+                      torch::Tensor block, torch::Tensor ctr, double beta1, double beta2, double eps) {
+  sign_check(x, m, table, nb, "sign_update_adam");
+  TORCH_CHECK(world >= 1 && world < (1 << 24), "sign_update_adam: 1 <= world < 2^24");
+  const int32_t* gp =
+      sign_i32(gathered, world * nb * ndp::kSignWords, "sign_update_adam", "gathered [world][nb * 65]");
+  const int32_t* dp = sign_i32(decays, nb, "sign_update_adam", "decays [nb]");
+  const ndp::EfAdamArgs a = ef_adam_args("sign_update_adam", x, v, block, ctr, nb, beta1, beta2, eps);
+  ndp::launch_sign_update_adam(x.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), x.numel(),
+                               table.data_ptr<int32_t>(), dp, nb, gp, (int)world, (float)lr, hyper_ptr(hyper), a,
+                               cur_stream());
+  check_launch("launch_sign_update_adam");
+}
+
+void quant_update_adam(torch::Tensor x, torch::Tensor m, torch::Tensor v, torch::Tensor table, torch::Tensor decays,
+                       int64_t nb, int64_t bits, torch::Tensor gathered, int64_t world, double lr,
+                       c10::optional<torch::Tensor> hyper, torch::Tensor block, torch::Tensor ctr, double beta1,
+                       double beta2, double eps) {
+  sign_check(x, m, table, nb, "quant_update_adam");
+  quant_check_bits(bits, "quant_update_adam");
+  TORCH_CHECK(world >= 1 && world < (1 << 24), "quant_update_adam: 1 <= world < 2^24");
+  const int32_t* gp = sign_i32(gathered, world * ndp::quant_row_words(nb, (int)bits), "quant_update_adam",
+                               "gathered [world][row_words]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(gp) % 16 == 0, "quant_update_adam: gathered must be 16-byte aligned");
+  const int32_t* dp = sign_i32(decays, nb, "quant_update_adam", "decays [nb]");
+  const ndp::EfAdamArgs a = ef_adam_args("quant_update_adam", x, v, block, ctr, nb, beta1, beta2, eps);
+  ndp::launch_quant_update_adam(x.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), x.numel(),
+                                table.data_ptr<int32_t>(), dp, nb, (int)bits, gp, (int)world, (float)lr,
+                                hyper_ptr(hyper), a, cur_stream());
+  check_launch("launch_quant_update_adam");
+}
+
+void topk_update_adam(torch::Tensor x, torch::Tensor m, torch::Tensor v, torch::Tensor gathered, int64_t k,
+                      int64_t world, torch::Tensor runs, double lr, c10::optional<torch::Tensor> hyper,
+                      torch::Tensor block, torch::Tensor ctr, double beta1, double beta2, double eps) {
+  const int64_t n = x.numel();
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), "topk_update_adam: 1 <= n < 2^31 required");
+  TORCH_CHECK(k >= 1 && k <= n && world >= 1 && world < (1 << 24),
+              "topk_update_adam: 1 <= k <= n and 1 <= world < 2^24");
+  topk_check_arena(x, "x", n); topk_check_arena(m, "m", n); topk_check_arena(v, "v", n);
+  const int32_t* gp = topk_check_i32(gathered, "gathered", world * 2 * k);
+  const int64_t nr = runs.numel() / 2;
+  TORCH_CHECK(nr >= 1 && nr <= n, "topk_update_adam: 1 <= runs <= n required");
+  const int32_t* rp = sign_i32(runs, 2 * nr, "topk_update_adam", "runs [nr][2]");
+  const int64_t grid = (n + ndp::kTopkTile - 1) / ndp::kTopkTile;
+  const ndp::EfAdamArgs a = ef_adam_args("topk_update_adam", x, v, block, ctr, grid, beta1, beta2, eps);
+  ndp::launch_topk_update_adam(x.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), n, gp, k, (int)world,
+                               rp, nr, (float)lr, hyper_ptr(hyper), a, cur_stream());
+  check_launch("launch_topk_update_adam");
+}
+
 // batch assembly from byte images (image_batch.hip): out [>= B, C, 32, 32] fp32 and out_target
 // [>= B] get B rows, the first m gathered from src / labels by idx, the rest padding.  scale /
 // shift: C fp32-representable values each.  No allocation, no sync: capture-safe.
@@ -2203,6 +2272,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"));
   m.def("quant_update", &quant_update, py::arg("x"), py::arg("b"), py::arg("table"), py::arg("nb"), py::arg("bits"),
         py::arg("gathered"), py::arg("world"), py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
+  m.def("sign_update_adam", &sign_update_adam, py::arg("x"), py::arg("m"), py::arg("v"), py::arg("table"),
+        py::arg("decays"), py::arg("nb"), py::arg("gathered"), py::arg("world"), py::arg("lr"), py::arg("hyper"),
+        py::arg("block"), py::arg("ctr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"));
+  m.def("quant_update_adam", &quant_update_adam, py::arg("x"), py::arg("m"), py::arg("v"), py::arg("table"),
+        py::arg("decays"), py::arg("nb"), py::arg("bits"), py::arg("gathered"), py::arg("world"), py::arg("lr"),
+        py::arg("hyper"), py::arg("block"), py::arg("ctr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"));
+  m.def("topk_update_adam", &topk_update_adam, py::arg("x"), py::arg("m"), py::arg("v"), py::arg("gathered"),
+        py::arg("k"), py::arg("world"), py::arg("runs"), py::arg("lr"), py::arg("hyper"), py::arg("block"),
+        py::arg("ctr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"));
   m.def("image_batch", &image_batch, py::arg("src"), py::arg("labels"), py::arg("idx"), py::arg("out"),
         py::arg("out_target"), py::arg("m"), py::arg("B"), py::arg("scale"), py::arg("shift"), py::arg("pad"),
         py::arg("flip_on"), py::arg("seed"), py::arg("epoch"), py::arg("pad_target"), py::arg("err"));

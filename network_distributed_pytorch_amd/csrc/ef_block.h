@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "adam_block.h"
 #include "hyper.h"
 
 namespace ndp {
@@ -80,6 +81,85 @@ __device__ __forceinline__ float sign_step(float a, float x, float& b, int N, fl
   asm volatile("" : "+v"(bl));  // the build's -ffp-contract=fast would fuse the product into the add
   b = fadd_scalar(bl, d);
   return __fmaf_rn(-lr, fadd_scalar(d, b), x);
+}
+
+// ---- AdamW behind the rank-ordered sum (sign_update_adam_kernel, quant_update_adam_kernel) --------
+// The SGD update kernels' thread map and decode with the element rule of adamw_elem.h in the place of
+// sign_step: g := o, div = 1, decay per block.  The arena b holds the first moment m, a third arena
+// of the same layout the second moment v; both are touched once per step, so their quads go through
+// non-temporal loads and stores (x keeps plain ones: the next forward reads it).  The step-dependent
+// scalars come from the AdamBlock by the protocol of adam_block.h: one barrier and 8 bytes of LDS are
+// all these kernels have over the SGD ones.
+constexpr int kEfThreads = 256, kEfRounds = 2;
+
+__device__ __forceinline__ Quad load_quad_nt(const float* __restrict__ src, int i, int n) {
+  Quad q = {{0.f, 0.f, 0.f, 0.f}, 0};
+  if (i + 4 <= n) {
+    const sign_f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const sign_f32x4*>(src + i));
+    q.v[0] = t[0]; q.v[1] = t[1]; q.v[2] = t[2]; q.v[3] = t[3];
+    q.nv = 4;
+  } else if (i < n) {
+    q.nv = n - i;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < q.nv) q.v[j] = __builtin_nontemporal_load(src + i + j);
+  }
+  return q;
+}
+
+__device__ __forceinline__ void store_quad_nt(float* __restrict__ dst, int i, const Quad& q) {
+  if (q.nv == 4) {
+    sign_f32x4 t;
+    t[0] = q.v[0]; t[1] = q.v[1]; t[2] = q.v[2]; t[3] = q.v[3];
+    __builtin_nontemporal_store(t, reinterpret_cast<sign_f32x4*>(dst + i));
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < q.nv) __builtin_nontemporal_store(q.v[j], dst + i + j);
+  }
+}
+
+// a thread's two quads of x, m and v of its block
+struct EfAdamRegs {
+  Quad x[kEfRounds], m[kEfRounds], v[kEfRounds];
+};
+
+// xb / mb / vb: the block's first element in the three arenas.  Six loads in flight on return.
+__device__ __forceinline__ EfAdamRegs ef_adam_load(const float* __restrict__ xb, const float* __restrict__ mb,
+                                                   const float* __restrict__ vb, int tid, int len) {
+  EfAdamRegs R;
+#pragma unroll
+  for (int h = 0; h < kEfRounds; ++h) {
+    R.x[h] = load_quad(xb, h * 4 * kEfThreads + 4 * tid, len);
+    R.m[h] = load_quad_nt(mb, h * 4 * kEfThreads + 4 * tid, len);
+    R.v[h] = load_quad_nt(vb, h * 4 * kEfThreads + 4 * tid, len);
+  }
+  return R;
+}
+
+// Behind the decode: the workgroup's one barrier, the launch's scalars from what adam_block_read left
+// in pow_sh, o = acc / N, the element rule, the stores, and the block's ticket.  steps: thread 0's.
+__device__ __forceinline__ void ef_adam_tail(float* __restrict__ xb, float* __restrict__ mb, float* __restrict__ vb,
+                                             int tid, EfAdamRegs& R, const float (&acc)[kEfRounds][4], int N, Hyper hy,
+                                             bool decays, const float* pow_sh, float beta1, float beta2, float eps,
+                                             unsigned* ctr, AdamBlock* block, unsigned steps) {
+  block_barrier();
+  float p1, p2;
+  AdamScalars S = adam_launch_scalars(pow_sh[0], pow_sh[1], hy.lr, hy.wd, beta1, beta2, eps, p1, p2);
+  S.decay = hy.wd != 0.f && decays;
+  const float fN = (float)N;
+#pragma unroll
+  for (int h = 0; h < kEfRounds; ++h) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float o = N != 1 ? __fdiv_rn(acc[h][c], fN) : acc[h][c];
+      adamw_elem(R.x[h].v[c], o, R.m[h].v[c], R.v[h].v[c], S);
+    }
+    store_quad(xb, h * 4 * kEfThreads + 4 * tid, R.x[h]);
+    store_quad_nt(mb, h * 4 * kEfThreads + 4 * tid, R.m[h]);
+    store_quad_nt(vb, h * 4 * kEfThreads + 4 * tid, R.v[h]);
+  }
+  adam_block_advance(ctr, block, p1, p2, steps);
 }
 
 }  // namespace ndp

@@ -458,6 +458,30 @@ void launch_quant_pack(const float* g, float* e, int64_t n, const int32_t* table
 // element rule with o = (sum over ranks in rank order of (u - L) s) / world.  hyper as for launch_sign_update.
 void launch_quant_update(float* x, float* b, int64_t n, const int32_t* table, int64_t nb, int bits,
                          const int32_t* gathered, int world, float lr, float lam, const float* hyper, hipStream_t s);
+
+// ---- AdamW in the flat-arena compressors (signsgd.hip, quant.hip, topk.hip) ----------------------
+// The three update launches above with the AdamW element rule (adamw.hip's header; g := the
+// decompressed average o, div = 1) in the place of momentum SGD: m is the arm's momentum arena, v a
+// second-moment arena of the same layout.  block / ctr as for launch_adamw_step, ctr sized by the
+// launch's grid (nb workgroups; ceil(n / kTopkTile) for top-k): the block becomes {p1, p2, steps + 1, 0}
+// once per launch.  hyper: the device block [lr, weight_decay, 0, 0], or null (lr by value, no decay).
+struct EfAdamArgs {
+  AdamBlock* block;
+  unsigned* ctr;
+  float beta1, beta2, eps;
+};
+// decays: int32 [nb], whether the tensor of block j takes the weight decay
+void launch_sign_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* table, const int32_t* decays,
+                             int64_t nb, const int32_t* gathered, int world, float lr, const float* hyper,
+                             EfAdamArgs a, hipStream_t s);
+void launch_quant_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* table, const int32_t* decays,
+                              int64_t nb, int bits, const int32_t* gathered, int world, float lr, const float* hyper,
+                              EfAdamArgs a, hipStream_t s);
+// runs: int32 [nr][2] = (start, decays), start ascending multiples of 16 from runs[0].start = 0: the
+// elements [start_i, start_{i+1}) take the weight decay or not
+void launch_topk_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* gathered, int64_t k, int world,
+                             const int32_t* runs, int64_t nr, float lr, const float* hyper, EfAdamArgs a,
+                             hipStream_t s);
 }  // namespace ndp
 
 // ---- batch assembly from byte images (image_batch.hip) ------------------------------------

@@ -42,6 +42,10 @@
 //     acc = 0;  for r = 0 .. N-1:  acc = fadd(acc, fmul((float)(u_r - L), s_r))     (rank order)
 //   then sign_step (ef_block.h): o = acc / N when N != 1, decay, momentum, SGD.  No LDS.
 //
+// quant_update_adam:  the same loads and decode (quant_accumulate), then AdamW (adamw_elem.h) on o in the
+//   place of sign_step; b is the first moment, a third arena the second.  It alone has a barrier, 8 bytes
+//   of LDS and a ticket: the AdamBlock protocol of adam_block.h (ef_block.h: ef_adam_tail).
+//
 // The rule's adds and subtractions are single scalar instructions and both kernels are compiled
 // without packed fp32 operations, as in signsgd.hip; every product feeds such an instruction, so the
 // build's -ffp-contract=fast has nothing to fuse it with.
@@ -58,6 +62,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kRounds = kSignBlock / (4 * kThreads);  // float4 rounds per thread and block
 static_assert(kRounds == 2, "thread map and wire layout");
+static_assert(kRounds == kEfRounds && kThreads == kEfThreads, "ef_block.h's AdamW pieces use the same thread map");
 constexpr unsigned kInfBits = 0x7f800000u, kNanBits = 0x7fc00000u;
 
 // DPP controls: quad_perm [1,0,3,2] (lane ^ 1), quad_perm [2,3,0,1] (lane ^ 2), and the mirrors of
@@ -177,26 +182,20 @@ __device__ __forceinline__ RankCodes load_rank(const int32_t* __restrict__ codes
   return r;
 }
 
+// acc = 0;  for r = 0 .. N-1:  acc = fadd(acc, fmul((float)(u_r - L), s_r)) for the lane's 8 elements of
+// block j: the decode both update kernels share.  Rank r + 1's words are requested before rank r's are
+// consumed.
 template <int BITS>
-__global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_kernel(
-    float* __restrict__ x, float* __restrict__ b, const int* __restrict__ table, int nb,
-    const int32_t* __restrict__ gathered, int N, float lr_arg, float lam, const float* __restrict__ hyper) {
+__device__ __forceinline__ void quant_accumulate(const int32_t* __restrict__ gathered, int nb, int j, int tid, int N,
+                                                 float (&acc)[kRounds][4]) {
   constexpr int L = (1 << (BITS - 1)) - 1;
-  const Hyper hy = load_hyper(hyper, lr_arg);
-  const int j = blockIdx.x;
-  const int off = table[2 * j], len = table[2 * j + 1];
-  const int tid = threadIdx.x;
-  float* __restrict__ xb = x + off;
-  float* __restrict__ bb = b + off;
-  Quad xq[kRounds], bq[kRounds];
-#pragma unroll
-  for (int h = 0; h < kRounds; ++h) {
-    xq[h] = load_quad(xb, h * 4 * kThreads + 4 * tid, len);
-    bq[h] = load_quad(bb, h * 4 * kThreads + 4 * tid, len);
-  }
   const size_t row_words = (size_t)quant_row_words(nb, BITS);
   const unsigned shift = (unsigned)(4 * BITS * tid) & 31u;  // the quad's place in its word
-  float acc[kRounds][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[h][c] = 0.f;
+  }
   const int32_t* __restrict__ codes = gathered + (size_t)j * (64 * BITS) + ((tid * BITS) >> 3);
   const int32_t* __restrict__ scales = gathered + (size_t)nb * (64 * BITS) + j;
   RankCodes cur = load_rank<BITS>(codes, scales, 0);
@@ -215,6 +214,26 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_kerne
     }
     cur = nxt;
   }
+}
+
+template <int BITS>
+__global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_kernel(
+    float* __restrict__ x, float* __restrict__ b, const int* __restrict__ table, int nb,
+    const int32_t* __restrict__ gathered, int N, float lr_arg, float lam, const float* __restrict__ hyper) {
+  const Hyper hy = load_hyper(hyper, lr_arg);
+  const int j = blockIdx.x;
+  const int off = table[2 * j], len = table[2 * j + 1];
+  const int tid = threadIdx.x;
+  float* __restrict__ xb = x + off;
+  float* __restrict__ bb = b + off;
+  Quad xq[kRounds], bq[kRounds];
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+    xq[h] = load_quad(xb, h * 4 * kThreads + 4 * tid, len);
+    bq[h] = load_quad(bb, h * 4 * kThreads + 4 * tid, len);
+  }
+  float acc[kRounds][4];
+  quant_accumulate<BITS>(gathered, nb, j, tid, N, acc);
   const float fN = (float)N;
 #pragma unroll
   for (int h = 0; h < kRounds; ++h) {
@@ -226,7 +245,46 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_kerne
   }
 }
 
+// quant_update with AdamW behind the decoded average (ef_block.h: ef_adam_load / ef_adam_tail).
+// decays: int32 [nb], whether block j's tensor takes the weight decay.
+// Resources (hipcc --offload-arch=gfx950 -O3 -ffp-contract=fast, -Rpass-analysis=kernel-resource-usage), the
+// same at 2, 4 and 8 bits: 57 VGPRs, 0 AGPRs, 46 SGPRs, no scratch (0 bytes/lane, no spills), 8 B of LDS,
+// occupancy 8 waves/SIMD (quant_update_kernel: 38-39 VGPRs, 32-34 SGPRs, no LDS, occupancy 8).
+template <int BITS>
+__global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_adam_kernel(
+    float* __restrict__ x, float* __restrict__ m, float* __restrict__ v, const int* __restrict__ table,
+    const int* __restrict__ decays, int nb, const int32_t* __restrict__ gathered, int N, float lr_arg,
+    const float* __restrict__ hyper, AdamBlock* block, unsigned* ctr, float beta1, float beta2, float eps) {
+  __shared__ float pow_sh[2];
+  const unsigned steps = adam_block_read(block, pow_sh);
+  const Hyper hy = load_hyper(hyper, lr_arg);
+  const int j = blockIdx.x;
+  const int off = table[2 * j], len = table[2 * j + 1];
+  const bool dec = decays[j] != 0;
+  const int tid = threadIdx.x;
+  EfAdamRegs R = ef_adam_load(x + off, m + off, v + off, tid, len);
+  float acc[kRounds][4];
+  quant_accumulate<BITS>(gathered, nb, j, tid, N, acc);
+  ef_adam_tail(x + off, m + off, v + off, tid, R, acc, N, hy, dec, pow_sh, beta1, beta2, eps, ctr, block, steps);
+}
+
+template <int BITS>
+void launch_update_adam(float* x, float* m, float* v, const int32_t* table, const int32_t* decays, int nb,
+                        const int32_t* gathered, int world, float lr, const float* hyper, EfAdamArgs a, hipStream_t s) {
+  hipLaunchKernelGGL(quant_update_adam_kernel<BITS>, dim3((unsigned)nb), dim3(kThreads), 0, s, x, m, v, table, decays,
+                     nb, gathered, world, lr, hyper, a.block, a.ctr, a.beta1, a.beta2, a.eps);
+}
+
 }  // namespace
+
+void launch_quant_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* table, const int32_t* decays,
+                              int64_t nb, int bits, const int32_t* gathered, int world, float lr, const float* hyper,
+                              EfAdamArgs a, hipStream_t s) {
+  if (n <= 0 || n >= (1LL << 31) || nb < 1 || world < 1) return;  // the binding has refused these
+  if (bits == 2) launch_update_adam<2>(x, m, v, table, decays, (int)nb, gathered, world, lr, hyper, a, s);
+  if (bits == 4) launch_update_adam<4>(x, m, v, table, decays, (int)nb, gathered, world, lr, hyper, a, s);
+  if (bits == 8) launch_update_adam<8>(x, m, v, table, decays, (int)nb, gathered, world, lr, hyper, a, s);
+}
 
 void launch_quant_pack(const float* g, float* e, int64_t n, const int32_t* table, int64_t nb, int bits, int32_t* out,
                        hipStream_t s) {

@@ -38,6 +38,10 @@
 //   No LDS: every rank's contribution to an element sits at the same place of its row.  lr / wd come
 //   from the nullable hyper block (hyper.h).
 //
+// sign_update_adam:  the same loads and decode (sign_accumulate), then AdamW (adamw_elem.h) on o in the
+//   place of the momentum rule; b is the first moment, a third arena the second.  It alone has a barrier,
+//   8 bytes of LDS and a ticket: the AdamBlock protocol of adam_block.h (ef_block.h: ef_adam_tail).
+//
 // The rule's adds and subtractions are single scalar instructions (fadd_scalar / fsub_scalar): the
 // build's -ffp-contract=fast has nothing to fuse them with, and the compiler cannot pair neighbouring
 // components into packed fp32 instructions, which this file does without.  They, the quad access and
@@ -55,6 +59,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kRounds = kSignBlock / (4 * kThreads);  // float4 rounds per thread and block
 static_assert(kRounds == 2 && kSignWords == kSignBlock / 32 + 1, "thread map and wire layout");
+static_assert(kRounds == kEfRounds && kThreads == kEfThreads, "ef_block.h's AdamW pieces use the same thread map");
 
 __device__ __forceinline__ float with_sign(unsigned mag, unsigned sign_bit31) {
   return __builtin_bit_cast(float, mag | sign_bit31);
@@ -154,24 +159,16 @@ __device__ __forceinline__ RankBits load_rank(const int32_t* __restrict__ row, i
   return r;
 }
 
-__global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void sign_update_kernel(
-    float* __restrict__ x, float* __restrict__ b, const int* __restrict__ table, int nb,
-    const int32_t* __restrict__ gathered, int N, float lr_arg, float lam, const float* __restrict__ hyper) {
-  const Hyper hy = load_hyper(hyper, lr_arg);
-  const int j = blockIdx.x;
-  const int off = table[2 * j], len = table[2 * j + 1];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* __restrict__ xb = x + off;
-  float* __restrict__ bb = b + off;
-  Quad xq[kRounds], bq[kRounds];
+// acc = 0;  for r = 0 .. N-1:  acc = fadd(acc, c_r) for the lane's 8 elements of block j: the decode both
+// update kernels share.  Rank r + 1's masks and scale are requested before rank r's are consumed.
+__device__ __forceinline__ void sign_accumulate(const int32_t* __restrict__ gathered, int nb, int j, int wave,
+                                                int lane, int N, float (&acc)[kRounds][4]) {
+  const size_t row_words = (size_t)nb * kSignWords;
 #pragma unroll
   for (int h = 0; h < kRounds; ++h) {
-    xq[h] = load_quad(xb, h * 4 * kThreads + 4 * tid, len);
-    bq[h] = load_quad(bb, h * 4 * kThreads + 4 * tid, len);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[h][c] = 0.f;
   }
-  const size_t row_words = (size_t)nb * kSignWords;
-  float acc[kRounds][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   RankBits cur = load_rank(gathered, nb, j, wave);
   for (int r = 0; r < N; ++r) {
     RankBits nxt = cur;
@@ -188,6 +185,26 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void sign_update_kernel
     }
     cur = nxt;
   }
+}
+
+__global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void sign_update_kernel(
+    float* __restrict__ x, float* __restrict__ b, const int* __restrict__ table, int nb,
+    const int32_t* __restrict__ gathered, int N, float lr_arg, float lam, const float* __restrict__ hyper) {
+  const Hyper hy = load_hyper(hyper, lr_arg);
+  const int j = blockIdx.x;
+  const int off = table[2 * j], len = table[2 * j + 1];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float* __restrict__ xb = x + off;
+  float* __restrict__ bb = b + off;
+  Quad xq[kRounds], bq[kRounds];
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+    xq[h] = load_quad(xb, h * 4 * kThreads + 4 * tid, len);
+    bq[h] = load_quad(bb, h * 4 * kThreads + 4 * tid, len);
+  }
+  float acc[kRounds][4];
+  sign_accumulate(gathered, nb, j, wave, lane, N, acc);
   const float fN = (float)N;
 #pragma unroll
   for (int h = 0; h < kRounds; ++h) {
@@ -199,7 +216,38 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void sign_update_kernel
   }
 }
 
+// sign_update with AdamW behind the decompressed average (ef_block.h: ef_adam_load / ef_adam_tail).
+// decays: int32 [nb], whether block j's tensor takes the weight decay.
+// Resources (hipcc --offload-arch=gfx950 -O3 -ffp-contract=fast, -Rpass-analysis=kernel-resource-usage):
+// 57 VGPRs, 0 AGPRs, 70 SGPRs, no scratch (0 bytes/lane, no spills), 8 B of LDS, occupancy 8 waves/SIMD
+// (sign_update_kernel: 36 VGPRs, 60 SGPRs, no LDS, occupancy 8).
+__global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void sign_update_adam_kernel(
+    float* __restrict__ x, float* __restrict__ m, float* __restrict__ v, const int* __restrict__ table,
+    const int* __restrict__ decays, int nb, const int32_t* __restrict__ gathered, int N, float lr_arg,
+    const float* __restrict__ hyper, AdamBlock* block, unsigned* ctr, float beta1, float beta2, float eps) {
+  __shared__ float pow_sh[2];
+  const unsigned steps = adam_block_read(block, pow_sh);
+  const Hyper hy = load_hyper(hyper, lr_arg);
+  const int j = blockIdx.x;
+  const int off = table[2 * j], len = table[2 * j + 1];
+  const bool dec = decays[j] != 0;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  EfAdamRegs R = ef_adam_load(x + off, m + off, v + off, tid, len);
+  float acc[kRounds][4];
+  sign_accumulate(gathered, nb, j, wave, lane, N, acc);
+  ef_adam_tail(x + off, m + off, v + off, tid, R, acc, N, hy, dec, pow_sh, beta1, beta2, eps, ctr, block, steps);
+}
+
 }  // namespace
+
+void launch_sign_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* table, const int32_t* decays,
+                             int64_t nb, const int32_t* gathered, int world, float lr, const float* hyper,
+                             EfAdamArgs a, hipStream_t s) {
+  if (n <= 0 || n >= (1LL << 31) || nb < 1 || world < 1) return;  // the binding has refused these
+  hipLaunchKernelGGL(sign_update_adam_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, x, m, v, table, decays,
+                     (int)nb, gathered, world, lr, hyper, a.block, a.ctr, a.beta1, a.beta2, a.eps);
+}
 
 void launch_sign_pack(const float* g, float* e, int64_t n, const int32_t* table, int64_t nb, int32_t* out,
                       hipStream_t s) {

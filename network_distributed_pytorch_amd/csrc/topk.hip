@@ -48,6 +48,7 @@
 // hyper block (hyper.h).  A tile without entries still runs the momentum rule.
 #include <hip/hip_runtime.h>
 
+#include "adam_block.h"
 #include "arrival.h"
 #include "hyper.h"
 #include "ndp_kernels.h"
@@ -371,21 +372,12 @@ __device__ __forceinline__ float topk_step(float a, float x, float& b, int N, fl
   return __fmaf_rn(-lr, __fadd_rn(d, b), x);
 }
 
-__global__ __launch_bounds__(kThreads) void topk_update_kernel(float* __restrict__ x, float* __restrict__ b, int64_t n,
-                                                               const int32_t* __restrict__ gathered, int k, int N,
-                                                               float lr_arg, float lam, const float* __restrict__ hyper) {
-  __shared__ float acc[kTopkTile];
-  __shared__ int bnd[2 * kRankRound];
-  const Hyper hy = load_hyper(hyper, lr_arg);
+// acc[0 .. kTopkTile) = per element the rank-ordered sum of the values the ranks selected in the tile
+// [tile_lo, tile_hi): the decompression both update kernels share.  bnd: 2 kRankRound words of LDS.
+// Ends behind a barrier (N >= 1): acc is complete in every thread's view.
+__device__ __forceinline__ void topk_accumulate(float* acc, int* bnd, const int32_t* __restrict__ gathered, int k,
+                                                int N, int tile_lo, int tile_hi) {
   const int tid = threadIdx.x;
-  const int64_t lo = (int64_t)blockIdx.x * kTopkTile;
-  const int tile_lo = (int)lo, tile_hi = (int)min(lo + kTopkTile, n);
-  Quad xq[2], bq[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    xq[h] = load_quad(x, lo + h * 4 * kThreads + 4 * tid, n);
-    bq[h] = load_quad(b, lo + h * 4 * kThreads + 4 * tid, n);
-  }
 #pragma unroll
   for (int i = 0; i < kTopkTile / kThreads; ++i) acc[tid + i * kThreads] = 0.f;
   for (int r0 = 0; r0 < N; r0 += kRankRound) {
@@ -404,6 +396,24 @@ __global__ __launch_bounds__(kThreads) void topk_update_kernel(float* __restrict
       __syncthreads();  // rank order
     }
   }
+}
+
+__global__ __launch_bounds__(kThreads) void topk_update_kernel(float* __restrict__ x, float* __restrict__ b, int64_t n,
+                                                               const int32_t* __restrict__ gathered, int k, int N,
+                                                               float lr_arg, float lam, const float* __restrict__ hyper) {
+  __shared__ float acc[kTopkTile];
+  __shared__ int bnd[2 * kRankRound];
+  const Hyper hy = load_hyper(hyper, lr_arg);
+  const int tid = threadIdx.x;
+  const int64_t lo = (int64_t)blockIdx.x * kTopkTile;
+  const int tile_lo = (int)lo, tile_hi = (int)min(lo + kTopkTile, n);
+  Quad xq[2], bq[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    xq[h] = load_quad(x, lo + h * 4 * kThreads + 4 * tid, n);
+    bq[h] = load_quad(b, lo + h * 4 * kThreads + 4 * tid, n);
+  }
+  topk_accumulate(acc, bnd, gathered, k, N, tile_lo, tile_hi);
   const float fN = (float)N;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -414,6 +424,100 @@ __global__ __launch_bounds__(kThreads) void topk_update_kernel(float* __restrict
     store_quad(x, lo + t0, xq[h]);
     store_quad(b, lo + t0, bq[h]);
   }
+}
+
+__device__ __forceinline__ Quad load_quad_nt(const float* __restrict__ src, int64_t i, int64_t n) {
+  Quad q = {{0.f, 0.f, 0.f, 0.f}, 0};
+  if (i + 4 <= n) {
+    const topk_f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const topk_f32x4*>(src + i));
+    q.v[0] = t[0]; q.v[1] = t[1]; q.v[2] = t[2]; q.v[3] = t[3];
+    q.nv = 4;
+  } else if (i < n) {
+    q.nv = (int)(n - i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < q.nv) q.v[j] = __builtin_nontemporal_load(src + i + j);
+  }
+  return q;
+}
+
+__device__ __forceinline__ void store_quad_nt(float* __restrict__ dst, int64_t i, const Quad& q) {
+  if (q.nv == 4) {
+    topk_f32x4 t;
+    t[0] = q.v[0]; t[1] = q.v[1]; t[2] = q.v[2]; t[3] = q.v[3];
+    __builtin_nontemporal_store(t, reinterpret_cast<topk_f32x4*>(dst + i));
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (j < q.nv) __builtin_nontemporal_store(q.v[j], dst + i + j);
+  }
+}
+
+// topk_update with AdamW (adamw_elem.h: g := o, div = 1) behind the decompressed average: the same
+// owner-computes tile, then the element rule over x (plain loads and stores), the first moment m (the
+// SGD arm's momentum arena) and the second moment v (both touched once per step: non-temporal).
+//   Decay.  A tile can span several tensors.  runs is int32 [nr][2] = (start, decays), start ascending
+//   from runs[0].start = 0 and every start a multiple of 16 (tensors are padded to 16 elements, so a
+//   float4 never straddles two runs; neighbours that decay alike are one run).  One thread finds the
+//   run of the tile's first element by bisection, behind the loads already in flight and ahead of the
+//   rank loop's first barrier; every thread walks on from there to the run of each of its two quads:
+//   no per-element stream, and with few runs per tile no step at all.
+//   The AdamBlock.  adam_block.h's protocol: thread 0 reads it ahead of the rank loop's barriers, the
+//   scalars are formed behind them, thread 0 draws the ticket behind its stores.
+//   Resources (hipcc --offload-arch=gfx950 -O3 -ffp-contract=fast, -Rpass-analysis=kernel-resource-usage):
+//   60 VGPRs, 0 AGPRs, 61 SGPRs, no scratch (0 bytes/lane, no spills), 9228 B of LDS (the tile, the
+//   bounds, 12 B for the block's products and the first run), occupancy 8 waves/SIMD
+//   (topk_update_kernel: 41 VGPRs, 48 SGPRs, 9216 B, occupancy 8).
+__global__ __launch_bounds__(kThreads) void topk_update_adam_kernel(
+    float* __restrict__ x, float* __restrict__ m, float* __restrict__ v, int64_t n,
+    const int32_t* __restrict__ gathered, int k, int N, const int* __restrict__ runs, int nr, float lr_arg,
+    const float* __restrict__ hyper, AdamBlock* block, unsigned* ctr, float beta1, float beta2, float eps) {
+  __shared__ float acc[kTopkTile];
+  __shared__ int bnd[2 * kRankRound];
+  __shared__ float pow_sh[2];
+  __shared__ int run0;
+  const unsigned steps = adam_block_read(block, pow_sh);
+  const Hyper hy = load_hyper(hyper, lr_arg);
+  const int tid = threadIdx.x;
+  const int64_t lo = (int64_t)blockIdx.x * kTopkTile;
+  const int tile_lo = (int)lo, tile_hi = (int)min(lo + kTopkTile, n);
+  Quad xq[2], mq[2], vq[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    xq[h] = load_quad(x, lo + h * 4 * kThreads + 4 * tid, n);
+    mq[h] = load_quad_nt(m, lo + h * 4 * kThreads + 4 * tid, n);
+    vq[h] = load_quad_nt(v, lo + h * 4 * kThreads + 4 * tid, n);
+  }
+  if (tid == kThreads - 1) {  // the last run with start <= tile_lo (run 0 starts at 0)
+    int a = 0, b = nr;
+    while (b - a > 1) {
+      const int mid = a + ((b - a) >> 1);
+      if (runs[2 * mid] <= tile_lo) a = mid;
+      else b = mid;
+    }
+    run0 = a;
+  }
+  topk_accumulate(acc, bnd, gathered, k, N, tile_lo, tile_hi);  // N >= 1: at least two barriers
+  float p1, p2;
+  AdamScalars S = adam_launch_scalars(pow_sh[0], pow_sh[1], hy.lr, hy.wd, beta1, beta2, eps, p1, p2);
+  const float fN = (float)N;
+  int r = run0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int t0 = h * 4 * kThreads + 4 * tid;
+    while (r + 1 < nr && runs[2 * (r + 1)] <= tile_lo + t0) ++r;
+    S.decay = hy.wd != 0.f && runs[2 * r + 1] != 0;
+    const topk_f32x4 a = *reinterpret_cast<const topk_f32x4*>(acc + t0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float o = N != 1 ? __fdiv_rn(a[j], fN) : a[j];
+      adamw_elem(xq[h].v[j], o, mq[h].v[j], vq[h].v[j], S);
+    }
+    store_quad(x, lo + t0, xq[h]);
+    store_quad_nt(m, lo + t0, mq[h]);
+    store_quad_nt(v, lo + t0, vq[h]);
+  }
+  adam_block_advance(ctr, block, p1, p2, steps);
 }
 
 }  // namespace
@@ -443,6 +547,15 @@ void launch_topk_update(float* x, float* b, int64_t n, const int32_t* gathered, 
   if (n <= 0) return;
   hipLaunchKernelGGL(topk_update_kernel, dim3((unsigned)((n + kTopkTile - 1) / kTopkTile)), dim3(kThreads), 0, s, x,
                      b, n, gathered, (int)k, world, lr, lam, hyper);
+}
+
+void launch_topk_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* gathered, int64_t k, int world,
+                             const int32_t* runs, int64_t nr, float lr, const float* hyper, EfAdamArgs a,
+                             hipStream_t s) {
+  if (n <= 0 || world < 1 || nr < 1) return;  // the binding has refused these
+  hipLaunchKernelGGL(topk_update_adam_kernel, dim3((unsigned)((n + kTopkTile - 1) / kTopkTile)), dim3(kThreads), 0, s,
+                     x, m, v, n, gathered, (int)k, world, runs, (int)nr, lr, hyper, a.block, a.ctr, a.beta1, a.beta2,
+                     a.eps);
 }
 
 }  // namespace ndp

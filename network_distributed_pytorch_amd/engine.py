@@ -406,11 +406,11 @@ def run_task(config) -> Dict[str, Any]:
             graph_mode = "none"  # the per-step query re-draw is host-side (not capturable)
     elif config["grad_sync"] == "dense":
         extra = {"overlap": config.get("overlap")}
-    elif config["grad_sync"] == "topk":
+    elif config["grad_sync"] in ("topk", "topk-adamw"):
         extra = {"overlap": config.get("overlap"), "topk_ratio": float(config.get("topk_ratio", 0.01))}
-    elif config["grad_sync"] == "signsgd":
+    elif config["grad_sync"] in ("signsgd", "signsgd-adamw"):
         extra = {"overlap": config.get("overlap")}
-    elif config["grad_sync"] == "quant":
+    elif config["grad_sync"] in ("quant", "quant-adamw"):
         extra = {"overlap": config.get("overlap"), "quant_bits": int(config.get("quant_bits", 4))}
     max_grad_norm = float(config.get("max_grad_norm") or 0.0)
     if max_grad_norm > 0:  # off: build_grad_sync is called exactly as before

@@ -43,7 +43,7 @@ from . import _UPLOADS, StateBlock, capturing, upload
 from ._ext import ext
 from .hyper import HyperState
 
-__all__ = ["FusedAdamW", "AdamWCore", "adamw_scalars", "check_adam_args"]
+__all__ = ["FusedAdamW", "AdamWCore", "AdamState", "adamw_scalars", "check_adam_args"]
 
 F = np.float32
 
@@ -108,6 +108,48 @@ def _twin_(x, g, m, v, S, beta1, beta2, eps, div, decays: bool) -> None:
     x.copy_(torch.sub(x1, u))
     m.copy_(mn)
     v.copy_(vn)
+
+
+class AdamState:
+    """The 16-byte block ``{b1pow, b2pow, steps}`` and, on a device, the two-level arrival tickets of
+    an update launch of up to ``max_blocks`` workgroups that steps with the rule above behind its own
+    decompression (``update_adam`` of ops/topk.py, ops/signsgd.py, ops/quant.py): allocated here,
+    before any capture.  On CPU the block is a dict and :meth:`twin_step` is the launch."""
+
+    def __init__(self, device, max_blocks: int):
+        self.device = torch.device(device)
+        self.state = StateBlock(self.device, ("b1pow", "b2pow", "steps"), (1.0, 1.0, 0))
+        self.dev = self.state.dev  # the kernel's argument (None on CPU)
+        self.ctr = None
+        if self.device.type == "cuda":
+            assert not capturing(), "the AdamW block and tickets are built before capture"
+            self.ctr = torch.zeros(ext().arrive_ctr_words(max(int(max_blocks), 1)), dtype=torch.int32,
+                                   device=self.device)
+
+    def twin_step(self, x, m, v, parts, lr, wd, beta1, beta2, eps) -> None:
+        """One launch on flat CPU arenas: ``parts`` of ``(index, o, decays)``, the elements
+        ``x[index]`` stepping with ``g := o`` and ``div = 1``; then the block advances."""
+        st = self.state.read()
+        S = adamw_scalars(st["b1pow"], st["b2pow"], lr, wd, beta1, beta2)
+        with torch.no_grad():
+            for index, o, dec in parts:
+                xs, ms, vs = x[index], m[index], v[index]
+                _twin_(xs, o, ms, vs, S, beta1, beta2, eps, 1.0, bool(dec) and F(wd) != F(0.0))
+                x[index], m[index], v[index] = xs, ms, vs
+        self.state.write({"b1pow": float(S["p1"]), "b2pow": float(S["p2"]), "steps": st["steps"] + 1})
+
+    def read(self) -> Dict[str, Any]:
+        """``{"b1pow", "b2pow", "steps"}``: a host sync on a device."""
+        return self.state.read()
+
+    def write(self, st: Dict[str, Any]) -> None:
+        self.state.write({"b1pow": float(F(st["b1pow"])), "b2pow": float(F(st["b2pow"])), "steps": st["steps"]})
+
+    def snapshot(self):
+        return self.state.snapshot()
+
+    def restore(self, snap) -> None:
+        self.state.restore(snap)
 
 
 class AdamWCore:

@@ -110,6 +110,17 @@ class QuantCore(SignCore):
             ext().quant_update(x, b, self.table, nb, bits, gathered, N, float(lr), float(lam), hyper)
             return
         idx, valid = self._twin_index()
+        o = self._decode(gathered)
+        lr, lam, wd = (float(np.float32(v)) for v in (lr, lam, wd))
+        xv, bv = x[idx], b[idx]
+        d = fmaf32(wd, xv, o) if wd != 0 else o
+        bv = bv * lam + d
+        xv = fmaf32(-lr, d + bv, xv)
+        x[idx[valid]], b[idx[valid]] = xv[valid], bv[valid]
+
+    def _decode(self, gathered: torch.Tensor) -> torch.Tensor:
+        """The twin's ``o`` of step 7, ``[nb, G]``: the rank-ordered sum of the decoded codes, over ``N``."""
+        N, nb, bits = self.world, self.nb, self.bits
         rows = gathered.view(N, self.words)
         shifts = (torch.arange(32 // bits) * bits).to(torch.int32)
         o = torch.zeros(nb, G)
@@ -117,11 +128,8 @@ class QuantCore(SignCore):
             u = ((rows[r, : self.code_words].view(nb, 64 * bits, 1) >> shifts) & (2 ** bits - 1)).view(nb, G)
             scale = rows[r, self.code_words: self.code_words + nb].view(torch.float32).view(nb, 1)
             o = o + (u - self.levels).float() * scale
-        if N != 1:
-            o = o / float(N)
-        lr, lam, wd = (float(np.float32(v)) for v in (lr, lam, wd))
-        xv, bv = x[idx], b[idx]
-        d = fmaf32(wd, xv, o) if wd != 0 else o
-        bv = bv * lam + d
-        xv = fmaf32(-lr, d + bv, xv)
-        x[idx[valid]], b[idx[valid]] = xv[valid], bv[valid]
+        return o / float(N) if N != 1 else o
+
+    def _native_update_adam(self, x, m, v, gathered, lr, hyper, block, decays, beta1, beta2, eps):
+        ext().quant_update_adam(x, m, v, self.table, decays, self.nb, self.bits, gathered, self.world, float(lr), hyper,
+                                block.dev, block.ctr, float(beta1), float(beta2), float(eps))

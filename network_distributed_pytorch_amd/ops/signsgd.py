@@ -73,11 +73,13 @@ class SignCore:
         if self.world < 1:
             raise ValueError(f"signsgd: world >= 1 required, got {world}")
         table, end = [], 0
-        for off, numel in sorted((int(o), int(c)) for o, c in segments):
+        self._block_seg = []  # per block, the position of its segment in `segments` as given
+        for off, numel, s in sorted((int(o), int(c), s) for s, (o, c) in enumerate(segments)):
             if off % 16 or numel < 1 or off < end or off + numel > self.n:
                 raise ValueError(f"signsgd: segment ({off}, {numel}) must start at a multiple of 16, be non-empty, "
                                  f"follow the segment before it (which ends at {end}) and end within n = {self.n}")
             table += [(off + t, min(G, numel - t)) for t in range(0, numel, G)]
+            self._block_seg += [s] * ((numel + G - 1) // G)
             end = off + numel
         if not table:
             raise ValueError("signsgd: no segments")
@@ -153,6 +155,17 @@ class SignCore:
             ext().sign_update(x, b, self.table, nb, gathered, N, float(lr), float(lam), hyper)
             return
         idx, valid = self._twin_index()
+        o = self._decode(gathered)
+        lr, lam, wd = (float(np.float32(v)) for v in (lr, lam, wd))
+        xv, bv = x[idx], b[idx]
+        d = fmaf32(wd, xv, o) if wd != 0 else o
+        bv = bv * lam + d
+        xv = fmaf32(-lr, d + bv, xv)
+        x[idx[valid]], b[idx[valid]] = xv[valid], bv[valid]
+
+    def _decode(self, gathered: torch.Tensor) -> torch.Tensor:
+        """The twin's ``o`` of step 8, ``[nb, G]``: the rank-ordered sum of the ``c_r``, over ``N``."""
+        N, nb = self.world, self.nb
         rows = gathered.view(N, self.words)
         o = torch.zeros(nb, G)
         for r in range(N):
@@ -161,11 +174,43 @@ class SignCore:
             bit = bit.permute(0, 1, 2, 4, 3).reshape(nb, G)
             mag = (rows[r, nb * 64:] & _MAG).view(nb, 1)
             o = o + (mag | (bit * _SIGN)).view(torch.float32)
-        if N != 1:
-            o = o / float(N)
-        lr, lam, wd = (float(np.float32(v)) for v in (lr, lam, wd))
-        xv, bv = x[idx], b[idx]
-        d = fmaf32(wd, xv, o) if wd != 0 else o
-        bv = bv * lam + d
-        xv = fmaf32(-lr, d + bv, xv)
-        x[idx[valid]], b[idx[valid]] = xv[valid], bv[valid]
+        return o / float(N) if N != 1 else o
+
+    # ---- AdamW behind the decompressed average ---------------------------------------------------
+    adam_grid = property(lambda self: self.nb, doc="workgroups of the update_adam launch (sizes the tickets)")
+
+    def block_decays(self, flags: Sequence[bool]) -> torch.Tensor:
+        """``int32[nb]`` on the core's device: per block, whether its tensor takes the weight decay;
+        ``flags`` one per segment, in the order the segments were given.  Built before any capture."""
+        flags = [bool(f) for f in flags]
+        if len(flags) != max(self._block_seg) + 1:
+            raise ValueError(f"{type(self).__name__}: {len(flags)} decay flags for {max(self._block_seg) + 1} segments")
+        return torch.tensor([int(flags[s]) for s in self._block_seg], dtype=torch.int32).to(self.device)
+
+    def _native_update_adam(self, x, m, v, gathered, lr, hyper, block, decays, beta1, beta2, eps):
+        ext().sign_update_adam(x, m, v, self.table, decays, self.nb, gathered, self.world, float(lr), hyper,
+                               block.dev, block.ctr, float(beta1), float(beta2), float(eps))
+
+    def update_adam(self, x: torch.Tensor, m: torch.Tensor, v: torch.Tensor, gathered: torch.Tensor, lr: float,
+                    wd: float, beta1: float, beta2: float, eps: float, block, decays: torch.Tensor,
+                    hyper: Optional[torch.Tensor] = None) -> None:
+        """The update with AdamW (ops/adamw.py's rule, ``g := o``, ``div = 1``) behind the decompressed
+        average ``o``: ``m`` / ``v`` the moments, ``block`` the :class:`ops.adamw.AdamState` (advanced
+        once), ``decays`` from :meth:`block_decays`.  ``hyper`` as for :meth:`update`."""
+        self._check(x, m, v)
+        if gathered.dtype != torch.int32 or gathered.numel() != self.world * self.words or not gathered.is_contiguous():
+            raise ValueError(f"{type(self).__name__}.update_adam: gathered must be contiguous int32 "
+                             f"[{self.world}, {self.words}]")
+        if decays.dtype != torch.int32 or decays.numel() != self.nb or decays.device != self.device:
+            raise ValueError(f"{type(self).__name__}.update_adam: decays must be int32 [{self.nb}] on {self.device}")
+        if self.device.type == "cuda":
+            if hyper is None and wd != 0.0:
+                raise ValueError(f"{type(self).__name__}.update_adam: weight decay on the device goes through the "
+                                 f"hyper block")
+            self._native_update_adam(x, m, v, gathered, lr, hyper, block, decays, beta1, beta2, eps)
+            return
+        idx, valid = self._twin_index()
+        o = self._decode(gathered)
+        dec = decays.bool().view(-1, 1)
+        block.twin_step(x, m, v, [(idx[valid & dec], o[valid & dec], True), (idx[valid & ~dec], o[valid & ~dec], False)],
+                        lr, wd, beta1, beta2, eps)

@@ -121,14 +121,60 @@ class TopKCore:
                 raise ValueError("TopKCore.update: weight decay on the device goes through the hyper block")
             ext().topk_update(x, b, gathered, k, N, float(lr), float(lam), hyper)
             return
+        o = self._decode(gathered)
+        lr, lam, wd = (float(np.float32(v)) for v in (lr, lam, wd))
+        d = fmaf32(wd, x, o) if wd != 0 else o
+        b.copy_(b * lam + d)
+        x.copy_(fmaf32(-lr, d + b, x))
+
+    def _decode(self, gathered: torch.Tensor) -> torch.Tensor:
+        """The twin's ``o`` of step 5, ``[n]``: the rank-ordered sum of the selected values, over ``N``."""
+        N, k = self.world, self.k
         rows = gathered.view(N, 2 * k)
         o = torch.zeros(self.n, dtype=torch.float32)
         for r in range(N):
             idx = rows[r, :k].long()
             o[idx] = o[idx] + rows[r, k:].view(torch.float32)
-        if N != 1:
-            o = o / float(N)
-        lr, lam, wd = (float(np.float32(v)) for v in (lr, lam, wd))
-        d = fmaf32(wd, x, o) if wd != 0 else o
-        b.copy_(b * lam + d)
-        x.copy_(fmaf32(-lr, d + b, x))
+        return o / float(N) if N != 1 else o
+
+    # ---- AdamW behind the decompressed average ---------------------------------------------------
+    adam_grid = property(lambda self: (self.n + 2047) // 2048,
+                         doc="workgroups of the update_adam launch (sizes the tickets)")
+
+    def decay_runs(self, segments) -> torch.Tensor:
+        """``int32[nr, 2] = (start, decays)`` on the core's device from ``segments`` of ``(offset,
+        decays)``, one per tensor, offsets multiples of 16: sorted, the first run starting at 0 and
+        neighbours that decay alike merged (a tensor's padding belongs to its run).  Built before any
+        capture."""
+        runs = []
+        for off, dec in sorted((int(o), int(bool(d))) for o, d in segments):
+            if off % 16 or not 0 <= off < self.n:
+                raise ValueError(f"top-k: a tensor at offset {off} (multiples of 16 within n = {self.n} required)")
+            if not runs or runs[-1][1] != dec:
+                runs.append((off if runs else 0, dec))
+        if not runs:
+            raise ValueError("top-k: no segments")
+        return torch.tensor(runs, dtype=torch.int32).to(self.device)
+
+    def update_adam(self, x: torch.Tensor, m: torch.Tensor, v: torch.Tensor, gathered: torch.Tensor, lr: float,
+                    wd: float, beta1: float, beta2: float, eps: float, block, decays: torch.Tensor,
+                    hyper: Optional[torch.Tensor] = None) -> None:
+        """Step 5 with AdamW (ops/adamw.py's rule, ``g := o``, ``div = 1``) behind the decompressed
+        average ``o``: ``m`` / ``v`` the moments, ``block`` the :class:`ops.adamw.AdamState` (advanced
+        once), ``decays`` from :meth:`decay_runs`.  ``hyper`` as for :meth:`update`."""
+        self._check(x, m, v)
+        N, k = self.world, self.k
+        if gathered.dtype != torch.int32 or gathered.numel() != N * 2 * k or not gathered.is_contiguous():
+            raise ValueError(f"TopKCore.update_adam: gathered must be contiguous int32 [{N}, {2 * k}]")
+        if decays.dtype != torch.int32 or decays.dim() != 2 or decays.shape[1] != 2 or decays.device != self.device:
+            raise ValueError(f"TopKCore.update_adam: decays must be int32 [runs, 2] on {self.device}")
+        if self.device.type == "cuda":
+            if hyper is None and wd != 0.0:
+                raise ValueError("TopKCore.update_adam: weight decay on the device goes through the hyper block")
+            ext().topk_update_adam(x, m, v, gathered, k, N, decays, float(lr), hyper, block.dev, block.ctr,
+                                   float(beta1), float(beta2), float(eps))
+            return
+        o = self._decode(gathered)
+        run = torch.bucketize(torch.arange(self.n), decays[:, 0].long().contiguous(), right=True) - 1
+        dec = decays[run.clamp_(min=0), 1].bool()
+        block.twin_step(x, m, v, [(dec, o[dec], True), (~dec, o[~dec], False)], lr, wd, beta1, beta2, eps)

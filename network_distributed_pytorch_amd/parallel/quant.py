@@ -9,7 +9,9 @@ TernGrad of Wen et al. 2017, here with deterministic rounding and error feedback
 Arenas, block table, phases, clipping, EMA tail and state are :class:`SignSync`'s; only the core
 differs.  One step = [clip] + flatten + 1 pack launch, ONE all-gather of ``int32[row_words]`` per rank
 (none at world size 1), 1 update launch, the EMA tail.  ``bytes_per_step = 4 * row_words``, about
-``32 / quant_bits`` times below dense.  No backward overlap and no AdamW, as in the scaled-sign arm.
+``32 / quant_bits`` times below dense.  No backward overlap, as in the scaled-sign arm;
+``optimizer="adamw"`` (``adam``: ``optimizer`` / ``betas`` / ``eps`` / ``decay_1d``) as there too
+(parallel/ef_adam.py).
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ class QuantSync(SignSync):
 
     def __init__(self, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                  momentum: float = 0.9, broadcast_params: bool = True, overlap: Optional[bool] = None,
-                 weight_decay: float = 0.0, max_grad_norm: float = 0.0, quant_bits: int = 4):
+                 weight_decay: float = 0.0, max_grad_norm: float = 0.0, quant_bits: int = 4, **adam):
         if quant_bits not in QUANT_BITS:
             raise ValueError(f"quant: quant_bits must be one of {QUANT_BITS}, got {quant_bits!r}")
         if overlap:
@@ -37,7 +39,7 @@ class QuantSync(SignSync):
                              "of scope here, as in the signsgd arm)")
         self.bits = int(quant_bits)
         super().__init__(model, comm, lr=lr, momentum=momentum, broadcast_params=broadcast_params,
-                         weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+                         weight_decay=weight_decay, max_grad_norm=max_grad_norm, **adam)
 
     def _build_core(self, segments, n):
         return QuantCore(self.device, segments, n, self.world, self.bits)

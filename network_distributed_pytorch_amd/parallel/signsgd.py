@@ -28,17 +28,19 @@ from ..ops import SegPlan, capturing, gradarena, gradfinish
 from ..ops.hyper import HyperState
 from ..ops.signsgd import SignCore
 from .comm import Communicator
+from .ef_adam import EfAdam
 from .sync import GradSync
 
 __all__ = ["SignSync"]
 
 
-class SignSync(HyperState, GradSync):
+class SignSync(EfAdam, HyperState, GradSync):
     _arm = "signsgd arm"
 
     def __init__(self, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                  momentum: float = 0.9, broadcast_params: bool = True, overlap: Optional[bool] = None,
-                 weight_decay: float = 0.0, max_grad_norm: float = 0.0):
+                 weight_decay: float = 0.0, max_grad_norm: float = 0.0, optimizer: str = "sgd",
+                 betas=(0.9, 0.999), eps: float = 1e-8, decay_1d: bool = True):
         assert weight_decay >= 0, "weight_decay >= 0"
         if overlap:
             raise ValueError("signsgd: overlap=True is not available (the per-tensor blocks would allow packing a "
@@ -48,7 +50,8 @@ class SignSync(HyperState, GradSync):
         self.momentum = float(momentum)
         self.params: List[torch.nn.Parameter] = [p for p in model.parameters() if p.requires_grad]
         self.device = self.params[0].device
-        self._init_hyper(float(lr), float(weight_decay), block=self.device.type == "cuda")
+        self._init_hyper(float(lr), float(weight_decay), block=self.device.type == "cuda",
+                         on=self._init_optimizer(optimizer, betas, eps, decay_1d))
         offs, o = {}, 0
         for p in reversed(self.params):
             offs[id(p)] = o
@@ -69,6 +72,7 @@ class SignSync(HyperState, GradSync):
                 gradarena.register(p, self.g, offs[id(p)])
         self.world = self.comm.world_size if self.comm.active else 1
         self.core = self._build_core([(offs[id(p)], p.numel()) for p in self.params], o)
+        self._alloc_adam(lambda: self.core.block_decays([self._decays(p) for p in self.params]))
         self._seg = SegPlan([], self.device, capacity=len(self.params))
         self.step_count = 0
         self._init_clip(max_grad_norm, self.device, capacity=1, blocks=(o + 2047) // 2048)
@@ -125,8 +129,7 @@ class SignSync(HyperState, GradSync):
 
     @torch.no_grad()
     def phase_update(self):
-        self.core.update(self.x, self.buf, self.core.gathered, self.lr, self.momentum, self.weight_decay,
-                         self._hyper_arg())
+        self._update()
         self._after_update()  # the EMA reads the weights the update wrote: same stream, behind it
         self.count_step()
 
@@ -151,25 +154,27 @@ class SignSync(HyperState, GradSync):
     # -- state ---------------------------------------------------------------------------------------
     def snapshot(self):
         return {"x": self.x.clone(), "buf": self.buf.clone(), "e": self.e.clone(), "step_count": self.step_count,
-                **self._snapshot_extras()}
+                **self._adam_snapshot(), **self._snapshot_extras()}
 
     def restore(self, snap):
         self.x.copy_(snap["x"])
         self.buf.copy_(snap["buf"])
         self.e.copy_(snap["e"])
         self.step_count = snap["step_count"]
+        self._adam_restore(snap)
         self._restore_extras(snap)
 
     def state_dict(self):
-        return {"error_memory": self.e.detach().cpu().clone(), "momentum_buffer": self.buf.detach().cpu().clone(),
+        return {"error_memory": self.e.detach().cpu().clone(), **self._moments_state_dict(),
                 "lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay,
                 "block": self.core.block}
 
     def load_state_dict(self, sd):
+        self._check_optimizer_state(sd)
         if int(sd["block"]) != self.core.block:
             raise ValueError(f"{self._arm}: the checkpoint was written with block = {sd['block']}, this sync has "
                              f"block = {self.core.block}")
         self.e.copy_(sd["error_memory"])
-        self.buf.copy_(sd["momentum_buffer"])
+        self._load_moments(sd)
         self.momentum = float(sd["momentum"])
         self._load_hyper(float(sd["lr"]), float(sd.get("weight_decay", 0.0)))

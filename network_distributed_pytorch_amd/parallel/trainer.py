@@ -13,6 +13,9 @@
 ``topk``                :class:`TopKSync`: exact global top-k with error feedback, one all-gather (parallel/topk.py)
 ``signsgd``             :class:`SignSync`: scaled sign with error feedback, one all-gather (parallel/signsgd.py)
 ``quant``               :class:`QuantSync`: 2/4/8-bit block quantisation with error feedback, one all-gather (parallel/quant.py)
+``topk-adamw``          :class:`TopKSync` with ``optimizer="adamw"``: AdamW in its update launch (parallel/ef_adam.py)
+``signsgd-adamw``       :class:`SignSync` with ``optimizer="adamw"``
+``quant-adamw``         :class:`QuantSync` with ``optimizer="adamw"``
 ======================  =====================================================================
 """
 from __future__ import annotations
@@ -31,9 +34,11 @@ from .sync import GradSync
 from .topk import TopKSync
 
 __all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "TopKSync", "SignSync",
-           "QuantSync", "ADAMW_SYNCS"]
+           "QuantSync", "ADAMW_SYNCS", "EF_ADAMW_SYNCS"]
 
 ADAMW_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # the arms that take optimizer="adamw"
+# the flat-arena compressors with AdamW in their update launch: the kind is the optimiser choice
+EF_ADAMW_SYNCS = {"topk-adamw": "topk", "signsgd-adamw": "signsgd", "quant-adamw": "quant"}
 
 
 class PowerSGDSync(PowerSGDOptimizer):
@@ -197,14 +202,18 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
     comm = comm if comm is not None else Communicator()
     clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
     adam = {}  # optimizer="sgd": every constructor call as before
-    if kind == "powersgd-adamw":
+    if kind == "powersgd-adamw" or kind in EF_ADAMW_SYNCS:
         # the kind is the optimiser choice (as local-adamw): optimizer "sgd" here means "unspecified"
         if optimizer not in ("sgd", "adamw"):
             raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
         b1, b2, eps = check_adam_args(betas, eps)
+    if kind in EF_ADAMW_SYNCS:
+        kind = EF_ADAMW_SYNCS[kind]
+        adam = {"optimizer": "adamw", "betas": (b1, b2), "eps": eps, "decay_1d": bool(decay_1d)}
+    elif kind == "powersgd-adamw":
         return PowerSGDSync(model, comm, lr, momentum, rank, seed=seed, optimizer="adamw", betas=(b1, b2),
                             eps_adam=eps, decay_1d=bool(decay_1d), **clip, **kw)
-    if optimizer != "sgd":
+    elif optimizer != "sgd":
         if optimizer != "adamw":
             raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
         if kind not in ADAMW_SYNCS:
@@ -213,7 +222,7 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
                              f"the top-k update kernel is momentum SGD only and "
                              f"the local optimisers are fixed recipes; use one of {', '.join(ADAMW_SYNCS)} "
                              f"(the scaled-sign update kernel of 'signsgd' and the block-quantised one of 'quant' are momentum "
-                             f"SGD only as well)")
+                             f"SGD only as well; their AdamW is a kind of its own: {', '.join(EF_ADAMW_SYNCS)})")
         b1, b2, eps = check_adam_args(betas, eps)
         adam = {"optimizer": "adamw", "betas": (b1, b2), "eps": eps, "decay_1d": bool(decay_1d)}
     if kind == "powersgd":
@@ -230,12 +239,12 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
         return LocalOptimizer(model, kind, lr, momentum, **clip)
     if kind == "topk":
         return TopKSync(model, comm, lr=lr, momentum=momentum, topk_ratio=topk_ratio, overlap=kw.get("overlap"),
-                        **clip)
+                        **clip, **adam)
     if kind == "signsgd":
-        return SignSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), **clip)
+        return SignSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), **clip, **adam)
     if kind == "quant":
         return QuantSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), quant_bits=quant_bits,
-                         **clip)
+                         **clip, **adam)
     raise ValueError(f"unknown grad sync {kind!r}")
 
 

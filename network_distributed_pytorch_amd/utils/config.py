@@ -24,7 +24,7 @@ class ConfigError(ValueError):
 
 
 GRAD_SYNCS = ("powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref", "local-sgd-nesterov",
-              "local-adamw", "topk", "signsgd", "quant")
+              "local-adamw", "topk", "signsgd", "quant", "topk-adamw", "signsgd-adamw", "quant-adamw")
 PSGD_ENGINE_SYNCS = ("powersgd", "powersgd-adamw")  # the fused native engine (parallel/powersgd.py)
 TASKS = ("cifar", "imdb", "mlp")
 GRAPH_MODES = ("auto", "full", "piecewise", "none")
@@ -36,6 +36,8 @@ MIXES = ("none", "mixup", "cutmix", "mixup_cutmix")  # ops/image_batch.py: image
 LR_SCHEDULES = ("constant", "step", "cosine")  # utils/schedule.py
 OPTIMIZERS = ("sgd", "adamw")
 ADAMW_GRAD_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # parallel/trainer.py ADAMW_SYNCS
+# the flat-arena compressors with AdamW in their update launch (parallel/trainer.py EF_ADAMW_SYNCS)
+EF_ADAMW_GRAD_SYNCS = {"topk-adamw": "topk", "signsgd-adamw": "signsgd", "quant-adamw": "quant"}
 
 
 @dataclasses.dataclass
@@ -213,21 +215,23 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
             raise ConfigError(f"{key} = {c[key]} must lie in [0, 1)")
     if not np.float32(c["adam_eps"]) > 0 or not np.isfinite(c["adam_eps"]):
         raise ConfigError(f"adam_eps = {c['adam_eps']} must be a finite number > 0 (as fp32)")
-    if c["grad_sync"] == "powersgd-adamw":  # the kind is the optimiser choice, as local-adamw
+    if c["grad_sync"] == "powersgd-adamw" or c["grad_sync"] in EF_ADAMW_GRAD_SYNCS:  # the kind is the optimiser choice
         c["optimizer"] = "adamw"
     elif c["optimizer"] == "adamw" and c["grad_sync"] not in ADAMW_GRAD_SYNCS:
         raise ConfigError(f"optimizer='adamw' is not available with grad_sync={c['grad_sync']!r} (the fused PowerSGD "
-                          f"engine, top-k, scaled sign, block quantisation and the local optimisers have no AdamW); "
+                          f"engine, top-k, scaled sign, block quantisation and the local optimisers have no AdamW; the first four "
+                          f"have it as kinds of their own: powersgd-adamw, {', '.join(EF_ADAMW_GRAD_SYNCS)}); "
                           f"allowed: {list(ADAMW_GRAD_SYNCS)}")
-    if c["grad_sync"] == "topk" and not 0 < c["topk_ratio"] <= 1:  # NaN fails the comparison too
+    base = EF_ADAMW_GRAD_SYNCS.get(c["grad_sync"], c["grad_sync"])  # the compressor of an -adamw kind
+    if base == "topk" and not 0 < c["topk_ratio"] <= 1:  # NaN fails the comparison too
         raise ConfigError(f"topk_ratio = {c['topk_ratio']} must lie in (0, 1]")
-    if c["grad_sync"] == "topk" and c["overlap"]:
+    if base == "topk" and c["overlap"]:
         raise ConfigError("grad_sync='topk' has no backward overlap: the global selection needs every gradient")
-    if c["grad_sync"] == "signsgd" and c["overlap"]:
+    if base == "signsgd" and c["overlap"]:
         raise ConfigError("grad_sync='signsgd' has no backward overlap (per-tensor packing is out of scope)")
-    if c["grad_sync"] == "quant" and c["quant_bits"] not in (2, 4, 8):
+    if base == "quant" and c["quant_bits"] not in (2, 4, 8):
         raise ConfigError(f"quant_bits = {c['quant_bits']} must be 2, 4 or 8")
-    if c["grad_sync"] == "quant" and c["overlap"]:
+    if base == "quant" and c["overlap"]:
         raise ConfigError("grad_sync='quant' has no backward overlap (per-tensor packing is out of scope)")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too
         raise ConfigError(f"max_grad_norm = {c['max_grad_norm']} must be >= 0 (0 = off, inf = measure only)")
