@@ -1597,6 +1597,62 @@ void adamw_step(torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, 
   check_launch("launch_adamw_step");
 }
 
+// LAMB / LARS (layerwise.hip) over a make_adamw_table table with one row per parameter tensor, built
+// against exactly these m / v arenas (LARS: m is the momentum arena, v and block are None): partial:
+// float64 of >= 2 * n_blocks, ctr: arrive_ctr_words(n_blocks) zeroed int32 (re-armed), trust: float32
+// of >= n_entries, hyper: the device block [lr, weight_decay, 0, 0].  No allocation, no sync: capture-safe.
+ndp::LwArgs lw_args(const char* who, bool lamb, const torch::Tensor& hyper, const torch::Tensor& m, const OptT& v,
+                    const OptT& block, double beta1, double beta2, double eps, double mu, double coef, double eps_l,
+                    double div) {
+  check_f32(m, "m");
+  TORCH_CHECK((float)div >= 1.0f, who, ": div must be >= 1");
+  ndp::LwArgs a{};
+  a.m = m.data_ptr<float>();
+  a.hyper = hyper_ptr(c10::optional<torch::Tensor>(hyper));
+  a.div = (float)div;
+  if (lamb) {
+    TORCH_CHECK(v.has_value() && block.has_value(), who, ": LAMB needs the second-moment arena and the block");
+    check_f32(*v, "v");
+    TORCH_CHECK(m.numel() == v->numel(), who, ": the moment arenas differ in size");
+    TORCH_CHECK((float)beta1 >= 0.0f && (float)beta1 < 1.0f && (float)beta2 >= 0.0f && (float)beta2 < 1.0f, who,
+                ": betas must be in [0, 1)");
+    TORCH_CHECK((float)eps > 0.0f, who, ": eps must be > 0 as fp32");
+    a.v = v->data_ptr<float>();
+    a.block = block4_ptr<ndp::AdamBlock>(*block, who);
+    a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
+  } else {
+    TORCH_CHECK((float)coef > 0.0f && (float)eps_l > 0.0f, who, ": lars_coef and lars_eps must be > 0 as fp32");
+    a.mu = (float)mu; a.coef = (float)coef; a.eps_l = (float)eps_l;
+  }
+  return a;
+}
+
+void lw_norm(bool lamb, torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
+             torch::Tensor partial, torch::Tensor ctr, torch::Tensor trust, torch::Tensor hyper, torch::Tensor m,
+             OptT v, OptT block, double beta1, double beta2, double eps, double mu, double coef, double eps_l,
+             double div) {
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "lw_norm");
+  check_dev(partial, "partial"); check_f32(trust, "trust");
+  TORCH_CHECK(partial.scalar_type() == torch::kFloat64 && partial.numel() >= 2 * n_blocks,
+              "lw_norm: partial must be float64 of >= 2 * n_blocks elements");
+  TORCH_CHECK(trust.numel() >= n_entries, "lw_norm: trust must hold one float per table entry");
+  const ndp::LwArgs a = lw_args("lw_norm", lamb, hyper, m, v, block, beta1, beta2, eps, mu, coef, eps_l, div);
+  ndp::launch_lw_norm(lamb, t.entries, t.prefix, t.n_entries, t.n_blocks, partial.data_ptr<double>(),
+                      ticket_ptr(ctr, n_blocks, "lw_norm"), trust.data_ptr<float>(), a, cur_stream());
+  check_launch("launch_lw_norm");
+}
+
+void lw_apply(bool lamb, torch::Tensor entries, torch::Tensor prefix, int64_t n_entries, int64_t n_blocks,
+              torch::Tensor trust, torch::Tensor hyper, torch::Tensor m, OptT v, OptT block, double beta1,
+              double beta2, double eps, double mu, double coef, double eps_l, double div) {
+  const SegArgs t = seg_args(entries, prefix, n_entries, n_blocks, "lw_apply");
+  check_f32(trust, "trust");
+  TORCH_CHECK(trust.numel() >= n_entries, "lw_apply: trust must hold one float per table entry");
+  const ndp::LwArgs a = lw_args("lw_apply", lamb, hyper, m, v, block, beta1, beta2, eps, mu, coef, eps_l, div);
+  ndp::launch_lw_apply(lamb, t.entries, t.prefix, t.n_entries, t.n_blocks, trust.data_ptr<float>(), a, cur_stream());
+  check_launch("launch_lw_apply");
+}
+
 // top-k sparsification (topk.hip): flat fp32 arenas, int32 scratch of >= topk_scratch_words(n) zeroed
 // words, an int32[8] block and out = int32 [2k].  No allocation, no sync: capture-safe.
 void topk_check_arena(const torch::Tensor& t, const char* name, int64_t n) {
@@ -2260,6 +2316,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step", &adamw_step, py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
         py::arg("ctr"), py::arg("block"), py::arg("hyper"), py::arg("m"), py::arg("v"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("div"));
+  m.def("lw_norm", &lw_norm, py::arg("lamb"), py::arg("ent"), py::arg("prefix"), py::arg("n_ent"), py::arg("n_blocks"),
+        py::arg("partial"), py::arg("ctr"), py::arg("trust"), py::arg("hyper"), py::arg("m"), py::arg("v"),
+        py::arg("block"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("mu"), py::arg("coef"),
+        py::arg("eps_l"), py::arg("div"));
+  m.def("lw_apply", &lw_apply, py::arg("lamb"), py::arg("ent"), py::arg("prefix"), py::arg("n_ent"),
+        py::arg("n_blocks"), py::arg("trust"), py::arg("hyper"), py::arg("m"), py::arg("v"), py::arg("block"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("mu"), py::arg("coef"), py::arg("eps_l"),
+        py::arg("div"));
   m.def("topk_select", &topk_select, py::arg("g"), py::arg("e"), py::arg("k"), py::arg("scratch"), py::arg("block"),
         py::arg("out"), py::arg("stage") = -1);
   m.def("topk_update", &topk_update, py::arg("x"), py::arg("b"), py::arg("gathered"), py::arg("k"), py::arg("world"),

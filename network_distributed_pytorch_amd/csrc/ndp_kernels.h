@@ -374,6 +374,27 @@ void launch_adamw_step(const SegEntry* entries, const int64_t* block_prefix, int
                        unsigned* ctr, AdamBlock* block, const float* hyper, float* m, float* v, float beta1,
                        float beta2, float eps, float div, hipStream_t s);
 
+// ---- LAMB and LARS: layer-wise trust-ratio optimisers (layerwise.hip) -------------------------
+// The same table with ONE entry per parameter tensor (the entry index is the tensor index; pad bit
+// 0 = the tensor neither decays nor adapts), in two launches per step: lw_norm forms the per-tensor
+// fp64 sums and trust[t] (fp32, one per entry), lw_apply writes the weights.  partial: 2 * n_blocks
+// fp64 scratch, ctr: arrive_ctr_words(n_blocks) zeroed uint32 (re-armed by lw_norm), hyper: the
+// device block [lr, weight_decay, 0, 0] (never null).  LAMB: m / v are the two moment arenas and
+// block the AdamBlock, which lw_norm advances.  LARS: m is the momentum arena; v and block are unused.
+struct LwArgs {
+  float* m;
+  float* v;
+  AdamBlock* block;  // LAMB only
+  const float* hyper;
+  float beta1, beta2, eps;  // LAMB
+  float mu, coef, eps_l;    // LARS: momentum, lars_coef (eta), lars_eps
+  float div;
+};
+void launch_lw_norm(bool lamb, const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
+                    double* partial, unsigned* ctr, float* trust, const LwArgs& a, hipStream_t s);
+void launch_lw_apply(bool lamb, const SegEntry* entries, const int64_t* block_prefix, int n_entries, int64_t n_blocks,
+                     const float* trust, const LwArgs& a, hipStream_t s);
+
 // ---- AdamW inside the PowerSGD update pass (powersgd.hip) -----------------------------------
 // The wide update launch (16 x 256 tiles, plan rank <= kUWideMaxRank, full layout only) with the
 // element rule above in the place of momentum SGD: g := the decompressed value, div = 1, every

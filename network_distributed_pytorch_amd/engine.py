@@ -85,6 +85,8 @@ def default_config(**over) -> Dict[str, Any]:
         topk_ratio=0.01,
         # grad_sync="quant" (parallel/quant.py): bits per coordinate, 2 (ternary), 4 or 8
         quant_bits=4,
+        # grad_sync="dense-lars" (ops/layerwise.py): trust coefficient and denominator eps
+        lars_coef=0.001, lars_eps=1e-8,
     )
     cfg.update(over)
     return cfg
@@ -406,6 +408,12 @@ def run_task(config) -> Dict[str, Any]:
             graph_mode = "none"  # the per-step query re-draw is host-side (not capturable)
     elif config["grad_sync"] == "dense":
         extra = {"overlap": config.get("overlap")}
+    elif config["grad_sync"] == "dense-lamb":
+        extra = {"overlap": config.get("overlap"), "betas": (float(config["adam_beta1"]), float(config["adam_beta2"])),
+                 "eps": float(config["adam_eps"]), "decay_1d": bool(config.get("decay_1d", True))}
+    elif config["grad_sync"] == "dense-lars":
+        extra = {"overlap": config.get("overlap"), "lars_coef": float(config.get("lars_coef", 0.001)),
+                 "lars_eps": float(config.get("lars_eps", 1e-8)), "decay_1d": bool(config.get("decay_1d", True))}
     elif config["grad_sync"] in ("topk", "topk-adamw"):
         extra = {"overlap": config.get("overlap"), "topk_ratio": float(config.get("topk_ratio", 0.01))}
     elif config["grad_sync"] in ("signsgd", "signsgd-adamw"):
@@ -516,6 +524,14 @@ def run_task(config) -> Dict[str, Any]:
         if runner is not None:
             runner.join()
         return {"optimizer": optimizer, "adam_steps": sync.adam_stats()["steps"]}
+    layerwise = config["grad_sync"] in ("dense-lamb", "dense-lars")
+
+    def trust_record():
+        # host read of the trust ratios; after a replay their last write may sit on the side stream
+        if runner is not None:
+            runner.join()
+        t = sync.trust_ratios()
+        return {"trust_min": float(t.min()), "trust_max": float(t.max())}
     t_start = time.perf_counter()
     samples = 0
     last_log = (time.perf_counter(), comm.stats.payload_bytes, comm.stats.wire_bytes, step)
@@ -617,6 +633,8 @@ def run_task(config) -> Dict[str, Any]:
             epoch_rec.update(ema_record())
         if optimizer != "sgd":
             epoch_rec.update(adam_record())
+        if layerwise:
+            epoch_rec.update(trust_record())
         if config.get("verbose", True):
             print_epoch(rank, epoch, mean)
             print(">>>>> Rank ", rank, ", epoch ", epoch, " Finished...\n", flush=True)

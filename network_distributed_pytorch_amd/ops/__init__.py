@@ -44,6 +44,8 @@ __all__ = [
     "ema_decay_at",
     "FusedAdamW",
     "adamw_scalars",
+    "FusedLamb",
+    "FusedLars",
 ]
 
 
@@ -365,3 +367,4 @@ from .image_batch import (crop_flip_draw, hash4, image_batch, image_mix_batch, i
 from .gradclip import GradClip, clip_grad_norm_  # noqa: E402  (global-norm clipping, csrc/gradclip.hip)
 from .ema import WeightEma, ema_decay_at  # noqa: E402  (weight EMA, csrc/ema.hip)
 from .adamw import FusedAdamW, adamw_scalars  # noqa: E402  (fused AdamW, csrc/adamw.hip)
+from .layerwise import FusedLamb, FusedLars  # noqa: E402  (LAMB / LARS, csrc/layerwise.hip)

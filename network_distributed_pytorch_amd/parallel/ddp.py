@@ -44,6 +44,13 @@ backward-overlapped MI355X arm.
   bias corrections live in the kernel's device block, so the captured step serves every step.
   The kernel always reads ``lr`` / ``weight_decay`` from the hyper block; ``momentum`` is ignored.
   Bucketing, overlap, stream mode and the order clip -> update -> EMA are the SGD arm's.
+  ``optimizer="lamb"`` / ``"lars"`` (the kinds ``dense-lamb`` / ``dense-lars`` of ``build_grad_sync``) put
+  the two launches of the layer-wise trust-ratio optimisers (ops/layerwise.py, csrc/layerwise.hip) in
+  the same place, over the same arenas with ``div = world_size``: the table has ONE entry per parameter
+  (the padding between parameters belongs to none and stays zero), ``buf`` is LAMB's first moment or
+  LARS's momentum buffer, ``v`` LAMB's second moment, and ``decay_1d=False`` exempts tensors of at most
+  one dimension from the decay AND the adaptation.  Every rank computes the norms on the same
+  all-reduced arena, so the replicas stay identical; wire bytes and collectives are unchanged.
 """
 from __future__ import annotations
 
@@ -54,6 +61,7 @@ import torch
 from ..ops import SegPlan, capturing, gradarena, gradfinish, sgd_momentum_
 from ..ops.adamw import AdamWCore, check_adam_args
 from ..ops.hyper import HyperState
+from ..ops.layerwise import LayerwiseCore, check_lars_args
 from .comm import Communicator, all_reduce, world_size
 from .sync import GradSync
 
@@ -85,14 +93,16 @@ class BucketedDataParallel(HyperState, GradSync):
                  momentum: float = 0.9, bucket_mb: Optional[float] = None, broadcast_params: bool = True,
                  overlap: Optional[bool] = None, weight_decay: float = 0.0,
                  max_grad_norm: float = 0.0, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
-                 decay_1d: bool = True):
+                 decay_1d: bool = True, lars_coef: float = 0.001, lars_eps: float = 1e-8):
         assert weight_decay >= 0, "weight_decay >= 0"
-        if optimizer not in ("sgd", "adamw"):
-            raise ValueError(f"dense arm: unknown optimizer {optimizer!r} (sgd, adamw)")
+        if optimizer not in ("sgd", "adamw", "lamb", "lars"):
+            raise ValueError(f"dense arm: unknown optimizer {optimizer!r} (sgd, adamw, lamb, lars)")
         self.optimizer = optimizer
         self.decay_1d = bool(decay_1d)
-        if optimizer == "adamw":
+        if optimizer in ("adamw", "lamb"):
             self.beta1, self.beta2, self.eps = check_adam_args(betas, eps)
+        if optimizer == "lars":
+            self.lars_coef, self.lars_eps = check_lars_args(lars_coef, lars_eps)
         bucket_mb = DEFAULT_BUCKET_MB if bucket_mb is None else float(bucket_mb)
         self.model = model
         self.comm = comm if comm is not None else Communicator()
@@ -102,7 +112,7 @@ class BucketedDataParallel(HyperState, GradSync):
         # device block [lr, weight_decay, 0, 0], allocated before any capture; the SGD kernel reads it
         # once set_hyper() was called or a decay is on, else lr goes by value
         self._init_hyper(float(lr), float(weight_decay), block=self.device.type == "cuda",
-                         on=True if optimizer == "adamw" else None)  # the AdamW kernel has no by-value lr
+                         on=None if optimizer == "sgd" else True)  # only the SGD kernel has a by-value lr
         order = list(reversed(self.params))
         offs, o = {}, 0
         for p in order:
@@ -185,12 +195,32 @@ class BucketedDataParallel(HyperState, GradSync):
             self.adam = AdamWCore(self.device, self.buf, self.v, len(runs),
                                   sum((e - s + 2047) // 2048 for s, e, _ in runs))
             self._bind_adam()
+        # LAMB / LARS: one table entry per parameter (arena order), LAMB's second-moment arena
+        self.lw: Optional[LayerwiseCore] = None
+        if optimizer in ("lamb", "lars"):
+            self.v = torch.zeros(o, **f32) if optimizer == "lamb" else None
+            self.lw_rows = [(offs[id(p)], p.numel(), self.decay_1d or p.dim() > 1) for p in order]
+            hp = (dict(beta1=self.beta1, beta2=self.beta2, eps=self.eps) if optimizer == "lamb" else
+                  dict(mu=self.momentum, coef=self.lars_coef, eps_l=self.lars_eps))
+            self.lw = LayerwiseCore(self.device, optimizer, self.buf, self.v, len(order),
+                                    sum((n + 2047) // 2048 for _, n, _ in self.lw_rows), **hp)
+            self._bind_lw()
+
+    def _bind_lw(self):
+        self.lw.bind([(self.g[s: s + n], self.x[s: s + n], s, ad) for s, n, ad in self.lw_rows])
+
+    def trust_ratios(self) -> Optional[torch.Tensor]:
+        """The last step's trust ratio of every parameter, in ``self.params`` order, on the CPU (a host
+        sync), or None unless the optimiser is LAMB or LARS."""
+        return self.lw.trust_ratios().flip(0) if self.lw is not None else None
 
     def _bind_adam(self):
         self.adam.bind([(self.g[s:e], self.x[s:e], s, dec) for s, e, dec in self.adam_runs])
 
     def adam_stats(self) -> Optional[Dict[str, Any]]:
         """``{"b1pow", "b2pow", "steps"}`` of the AdamW block (a host sync), or None with SGD."""
+        if self.lw is not None:
+            return self.lw.read()
         return self.adam.read() if self.adam is not None else None
 
     @property
@@ -292,6 +322,11 @@ class BucketedDataParallel(HyperState, GradSync):
 
             def update():  # lr / decay: the CPU twin's; the kernel reads hy
                 adam.run(self.lr, self.weight_decay, b1, b2, eps, n, hy)
+        elif self.lw is not None:
+            self._bind_lw()  # a no-op unless the device tables were restored (upload_epoch)
+
+            def update():  # two launches: norms and trust ratios, then the weights
+                self.lw.run(self.lr, self.weight_decay, n, hy)
         else:
             lr, mu, wd = self.lr, self.momentum, self.weight_decay
 
@@ -357,6 +392,8 @@ class BucketedDataParallel(HyperState, GradSync):
     def snapshot(self):
         return {"x": self.x.clone(), "buf": self.buf.clone(), "step_count": self.step_count,
                 **({"v": self.v.clone(), "adam": self.adam.snapshot()} if self.adam is not None else {}),
+                **({"v": self.v.clone() if self.v is not None else None, "lw": self.lw.snapshot()}
+                   if self.lw is not None else {}),
                 **self._snapshot_extras()}
 
     def restore(self, snap):
@@ -366,6 +403,10 @@ class BucketedDataParallel(HyperState, GradSync):
         if self.adam is not None:
             self.v.copy_(snap["v"])
             self.adam.restore(snap["adam"])
+        if self.lw is not None:
+            if self.v is not None:
+                self.v.copy_(snap["v"])
+            self.lw.restore(snap["lw"])
         self._restore_extras(snap)
 
     def count_step(self):
@@ -379,8 +420,15 @@ class BucketedDataParallel(HyperState, GradSync):
                     "exp_avg_sq": self.v.detach().cpu().clone(), "b1pow": st["b1pow"], "b2pow": st["b2pow"],
                     "steps": st["steps"], "lr": self.lr, "weight_decay": self.weight_decay,
                     "betas": (self.beta1, self.beta2), "eps": self.eps, "momentum": self.momentum}
-        return {"momentum_buffer": self.buf.detach().cpu().clone(), "lr": self.lr, "momentum": self.momentum,
+        base = {"momentum_buffer": self.buf.detach().cpu().clone(), "lr": self.lr, "momentum": self.momentum,
                 "weight_decay": self.weight_decay}
+        if self.optimizer == "lamb":  # "momentum_buffer" is the first moment
+            return {"optimizer": "lamb", **base, "exp_avg_sq": self.v.detach().cpu().clone(), **self.lw.read(),
+                    "betas": (self.beta1, self.beta2), "eps": self.eps, "trust": self.lw.trust_ratios()}
+        if self.optimizer == "lars":
+            return {"optimizer": "lars", **base, "lars_coef": self.lars_coef, "lars_eps": self.lars_eps,
+                    "trust": self.lw.trust_ratios()}
+        return base
 
     def load_state_dict(self, sd):
         theirs = sd.get("optimizer", "sgd")  # a checkpoint without "optimizer" is an SGD checkpoint
@@ -391,5 +439,12 @@ class BucketedDataParallel(HyperState, GradSync):
         if self.adam is not None:
             self.v.copy_(sd["exp_avg_sq"])
             self.adam.write(sd)
+        if self.lw is not None:
+            if self.v is not None:
+                self.v.copy_(sd["exp_avg_sq"])
+            self.lw.write(sd)
+            self.lw.trust[: len(self.lw_rows)].copy_(sd["trust"])
         self.momentum = float(sd["momentum"])
+        if self.optimizer == "lars":
+            self.lw.mu = self.momentum
         self._load_hyper(float(sd["lr"]), float(sd.get("weight_decay", 0.0)))

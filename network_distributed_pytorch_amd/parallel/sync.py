@@ -21,6 +21,9 @@
 ``quant``          2/4/8-bit absmax-scaled codes of ``g + e`` with error feedback (:class:`QuantSync`): 1 pack
                    launch (``quant_bits`` per element, one fp32 scale per block of 2048), one all-gather, 1
                    update launch.
+``dense-lamb``     ``dense`` with LAMB (ops/layerwise.py) in the place of the SGD launch: two launches, per-tensor
+                   fp64 norms and trust ratios, then the weights.
+``dense-lars``     ``dense`` with LARS in the same place.
 =================  ===========================================================================
 
 Every strategy has ``set_hyper(lr, weight_decay)``: the learning rate and the L2 weight decay of
@@ -45,6 +48,10 @@ launch, snapshot and state dict is what it is without.
 returns the step count.  ``powersgd`` and the local optimisers raise: the fused engine's Adam variant is
 its own kind, ``powersgd-adamw`` (the kind is the optimiser choice, as ``local-adamw``).  With ``optimizer="sgd"``
 every constructor call is exactly what it is without these arguments.
+
+``dense-lamb`` / ``dense-lars`` are optimiser choices of their own (``optimizer`` must stay unspecified): LAMB takes
+``betas`` / ``eps``, LARS ``momentum`` / ``lars_coef`` / ``lars_eps``, both ``decay_1d``; ``trust_ratios()`` returns the
+last step's per-parameter trust ratios (a host sync).
 """
 from __future__ import annotations
 

@@ -16,6 +16,8 @@
 ``topk-adamw``          :class:`TopKSync` with ``optimizer="adamw"``: AdamW in its update launch (parallel/ef_adam.py)
 ``signsgd-adamw``       :class:`SignSync` with ``optimizer="adamw"``
 ``quant-adamw``         :class:`QuantSync` with ``optimizer="adamw"``
+``dense-lamb``          :class:`_DenseSync` with LAMB in the place of its SGD launch (ops/layerwise.py)
+``dense-lars``          :class:`_DenseSync` with LARS in the place of its SGD launch
 ======================  =====================================================================
 """
 from __future__ import annotations
@@ -25,6 +27,7 @@ from typing import Optional
 import torch
 
 from ..ops.adamw import FusedAdamW, check_adam_args
+from ..ops.layerwise import check_lars_args
 from .comm import Communicator
 from .ddp import BucketedDataParallel, average_gradients
 from .powersgd import PowerSGDOptimizer, PowerSGDReducer, powersgd_bytes_per_step
@@ -34,11 +37,13 @@ from .sync import GradSync
 from .topk import TopKSync
 
 __all__ = ["build_grad_sync", "ReferencePowerSGDLoop", "ReferenceDenseLoop", "PowerSGDSync", "TopKSync", "SignSync",
-           "QuantSync", "ADAMW_SYNCS", "EF_ADAMW_SYNCS"]
+           "QuantSync", "ADAMW_SYNCS", "EF_ADAMW_SYNCS", "LAYERWISE_SYNCS"]
 
 ADAMW_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # the arms that take optimizer="adamw"
 # the flat-arena compressors with AdamW in their update launch: the kind is the optimiser choice
 EF_ADAMW_SYNCS = {"topk-adamw": "topk", "signsgd-adamw": "signsgd", "quant-adamw": "quant"}
+# the dense arm with a layer-wise trust-ratio optimiser: the kind is the optimiser choice
+LAYERWISE_SYNCS = {"dense-lamb": "lamb", "dense-lars": "lars"}
 
 
 class PowerSGDSync(PowerSGDOptimizer):
@@ -198,9 +203,23 @@ def _set_param_groups(opt: torch.optim.Optimizer, lr, weight_decay):
 def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicator] = None, lr: float = 1e-3,
                     momentum: float = 0.9, rank: int = 4, bucket_mb: Optional[float] = None, seed: int = 714,
                     max_grad_norm: float = 0.0, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
-                    decay_1d: bool = True, topk_ratio: float = 0.01, quant_bits: int = 4, **kw):
+                    decay_1d: bool = True, topk_ratio: float = 0.01, quant_bits: int = 4, lars_coef: float = 0.001,
+                    lars_eps: float = 1e-8, **kw):
     comm = comm if comm is not None else Communicator()
     clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
+    if kind in LAYERWISE_SYNCS:
+        # the kind is the optimiser choice; ``optimizer`` keeps its two values and "sgd" means "unspecified"
+        if optimizer != "sgd":
+            raise ValueError(f"grad sync {kind!r} is its own optimiser choice ({LAYERWISE_SYNCS[kind]}): "
+                             f"optimizer={optimizer!r} cannot be combined with it")
+        if kind == "dense-lamb":
+            b1, b2, eps = check_adam_args(betas, eps)
+            hp = {"betas": (b1, b2), "eps": eps}
+        else:
+            coef, eps_l = check_lars_args(lars_coef, lars_eps)
+            hp = {"lars_coef": coef, "lars_eps": eps_l}
+        return _DenseSync(model, comm, lr, momentum, bucket_mb, overlap=kw.get("overlap"), **clip,
+                          optimizer=LAYERWISE_SYNCS[kind], decay_1d=bool(decay_1d), **hp)
     adam = {}  # optimizer="sgd": every constructor call as before
     if kind == "powersgd-adamw" or kind in EF_ADAMW_SYNCS:
         # the kind is the optimiser choice (as local-adamw): optimizer "sgd" here means "unspecified"

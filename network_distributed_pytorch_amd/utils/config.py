@@ -24,7 +24,8 @@ class ConfigError(ValueError):
 
 
 GRAD_SYNCS = ("powersgd", "powersgd-adamw", "powersgd-ref", "powersgd-api", "dense", "dense-ref", "local-sgd-nesterov",
-              "local-adamw", "topk", "signsgd", "quant", "topk-adamw", "signsgd-adamw", "quant-adamw")
+              "local-adamw", "topk", "signsgd", "quant", "topk-adamw", "signsgd-adamw", "quant-adamw", "dense-lamb",
+              "dense-lars")
 PSGD_ENGINE_SYNCS = ("powersgd", "powersgd-adamw")  # the fused native engine (parallel/powersgd.py)
 TASKS = ("cifar", "imdb", "mlp")
 GRAPH_MODES = ("auto", "full", "piecewise", "none")
@@ -38,6 +39,7 @@ OPTIMIZERS = ("sgd", "adamw")
 ADAMW_GRAD_SYNCS = ("dense", "dense-ref", "powersgd-ref", "powersgd-api")  # parallel/trainer.py ADAMW_SYNCS
 # the flat-arena compressors with AdamW in their update launch (parallel/trainer.py EF_ADAMW_SYNCS)
 EF_ADAMW_GRAD_SYNCS = {"topk-adamw": "topk", "signsgd-adamw": "signsgd", "quant-adamw": "quant"}
+LAYERWISE_GRAD_SYNCS = ("dense-lamb", "dense-lars")  # the dense arm with LAMB / LARS (parallel/trainer.py LAYERWISE_SYNCS)
 
 
 @dataclasses.dataclass
@@ -123,6 +125,10 @@ class TrainConfig:
     topk_ratio: float = 0.01  # k = max(1, ceil(topk_ratio * parameters)), 0 < ratio <= 1
     # grad_sync="quant" (parallel/quant.py): bits per coordinate, 2 (ternary), 4 or 8
     quant_bits: int = 4
+    # grad_sync="dense-lars" (ops/layerwise.py): the trust coefficient eta and the eps of its denominator;
+    # adam_beta1 / adam_beta2 / adam_eps / decay_1d serve grad_sync="dense-lamb"
+    lars_coef: float = 0.001
+    lars_eps: float = 1e-8
 
 
 _FIELDS = {f.name: f for f in dataclasses.fields(TrainConfig)}
@@ -215,6 +221,12 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
             raise ConfigError(f"{key} = {c[key]} must lie in [0, 1)")
     if not np.float32(c["adam_eps"]) > 0 or not np.isfinite(c["adam_eps"]):
         raise ConfigError(f"adam_eps = {c['adam_eps']} must be a finite number > 0 (as fp32)")
+    for key in ("lars_coef", "lars_eps"):  # as fp32, what the kernel receives; NaN fails the comparison too
+        if not np.float32(c[key]) > 0 or not np.isfinite(np.float32(c[key])):
+            raise ConfigError(f"{key} = {c[key]} must be a finite number > 0 (as fp32)")
+    if c["grad_sync"] in LAYERWISE_GRAD_SYNCS and c["optimizer"] != "sgd":
+        raise ConfigError(f"grad_sync={c['grad_sync']!r} is its own optimiser choice: optimizer={c['optimizer']!r} "
+                          "cannot be combined with it")
     if c["grad_sync"] == "powersgd-adamw" or c["grad_sync"] in EF_ADAMW_GRAD_SYNCS:  # the kind is the optimiser choice
         c["optimizer"] = "adamw"
     elif c["optimizer"] == "adamw" and c["grad_sync"] not in ADAMW_GRAD_SYNCS:
