@@ -1748,26 +1748,39 @@ void quant_check_bits(int64_t bits, const char* who) {
   TORCH_CHECK(bits == 2 || bits == 4 || bits == 8, who, ": bits must be 2, 4 or 8, got ", bits);
 }
 
-void quant_pack(torch::Tensor g, torch::Tensor e, torch::Tensor table, int64_t nb, int64_t bits, torch::Tensor out) {
+// rotate: "none" or "hadamard" (the rotation of full blocks, quant.hip); seed: its signs, a uint32
+bool quant_rotate_arg(const std::string& rotate, int64_t seed, const char* who) {
+  TORCH_CHECK(rotate == "none" || rotate == "hadamard", who, ": rotate must be 'none' or 'hadamard', got '", rotate,
+              "'");
+  TORCH_CHECK(seed >= 0 && seed <= 0xFFFFFFFFLL, who, ": 0 <= seed < 2^32 required, got ", seed);
+  return rotate == "hadamard";
+}
+
+void quant_pack(torch::Tensor g, torch::Tensor e, torch::Tensor table, int64_t nb, int64_t bits, torch::Tensor out,
+                const std::string& rotate, int64_t seed) {
   sign_check(g, e, table, nb, "quant_pack");
   quant_check_bits(bits, "quant_pack");
+  const bool rot = quant_rotate_arg(rotate, seed, "quant_pack");
   auto* o = const_cast<int32_t*>(sign_i32(out, ndp::quant_row_words(nb, (int)bits), "quant_pack", "out [row_words]"));
   TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0, "quant_pack: out must be 16-byte aligned");
   ndp::launch_quant_pack(g.data_ptr<float>(), e.data_ptr<float>(), e.numel(), table.data_ptr<int32_t>(), nb, (int)bits,
-                         o, cur_stream());
+                         o, rot, (uint32_t)seed, cur_stream());
   check_launch("launch_quant_pack");
 }
 
 void quant_update(torch::Tensor x, torch::Tensor b, torch::Tensor table, int64_t nb, int64_t bits,
-                  torch::Tensor gathered, int64_t world, double lr, double lam, c10::optional<torch::Tensor> hyper) {
+                  torch::Tensor gathered, int64_t world, double lr, double lam, c10::optional<torch::Tensor> hyper,
+                  const std::string& rotate, int64_t seed) {
   sign_check(x, b, table, nb, "quant_update");
   quant_check_bits(bits, "quant_update");
+  const bool rot = quant_rotate_arg(rotate, seed, "quant_update");
   TORCH_CHECK(world >= 1 && world < (1 << 24), "quant_update: 1 <= world < 2^24");
   const int32_t* gp = sign_i32(gathered, world * ndp::quant_row_words(nb, (int)bits), "quant_update",
                                "gathered [world][row_words]");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(gp) % 16 == 0, "quant_update: gathered must be 16-byte aligned");
   ndp::launch_quant_update(x.data_ptr<float>(), b.data_ptr<float>(), x.numel(), table.data_ptr<int32_t>(), nb,
-                           (int)bits, gp, (int)world, (float)lr, (float)lam, hyper_ptr(hyper), cur_stream());
+                           (int)bits, gp, (int)world, (float)lr, (float)lam, hyper_ptr(hyper), rot, (uint32_t)seed,
+                           cur_stream());
   check_launch("launch_quant_update");
 }
 
@@ -1806,9 +1819,10 @@ void sign_update_adam(torch::Tensor x, torch::Tensor m, torch::Tensor v, torch::
 void quant_update_adam(torch::Tensor x, torch::Tensor m, torch::Tensor v, torch::Tensor table, torch::Tensor decays,
                        int64_t nb, int64_t bits, torch::Tensor gathered, int64_t world, double lr,
                        c10::optional<torch::Tensor> hyper, torch::Tensor block, torch::Tensor ctr, double beta1,
-                       double beta2, double eps) {
+                       double beta2, double eps, const std::string& rotate, int64_t seed) {
   sign_check(x, m, table, nb, "quant_update_adam");
   quant_check_bits(bits, "quant_update_adam");
+  const bool rot = quant_rotate_arg(rotate, seed, "quant_update_adam");
   TORCH_CHECK(world >= 1 && world < (1 << 24), "quant_update_adam: 1 <= world < 2^24");
   const int32_t* gp = sign_i32(gathered, world * ndp::quant_row_words(nb, (int)bits), "quant_update_adam",
                                "gathered [world][row_words]");
@@ -1817,7 +1831,7 @@ void quant_update_adam(torch::Tensor x, torch::Tensor m, torch::Tensor v, torch:
   const ndp::EfAdamArgs a = ef_adam_args("quant_update_adam", x, v, block, ctr, nb, beta1, beta2, eps);
   ndp::launch_quant_update_adam(x.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), x.numel(),
                                 table.data_ptr<int32_t>(), dp, nb, (int)bits, gp, (int)world, (float)lr,
-                                hyper_ptr(hyper), a, cur_stream());
+                                hyper_ptr(hyper), a, rot, (uint32_t)seed, cur_stream());
   check_launch("launch_quant_update_adam");
 }
 
@@ -2333,15 +2347,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sign_update", &sign_update, py::arg("x"), py::arg("b"), py::arg("table"), py::arg("nb"), py::arg("gathered"),
         py::arg("world"), py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
   m.def("quant_pack", &quant_pack, py::arg("g"), py::arg("e"), py::arg("table"), py::arg("nb"), py::arg("bits"),
-        py::arg("out"));
+        py::arg("out"), py::arg("rotate") = "none", py::arg("seed") = 0);
   m.def("quant_update", &quant_update, py::arg("x"), py::arg("b"), py::arg("table"), py::arg("nb"), py::arg("bits"),
-        py::arg("gathered"), py::arg("world"), py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none());
+        py::arg("gathered"), py::arg("world"), py::arg("lr"), py::arg("lam"), py::arg("hyper") = py::none(),
+        py::arg("rotate") = "none", py::arg("seed") = 0);
   m.def("sign_update_adam", &sign_update_adam, py::arg("x"), py::arg("m"), py::arg("v"), py::arg("table"),
         py::arg("decays"), py::arg("nb"), py::arg("gathered"), py::arg("world"), py::arg("lr"), py::arg("hyper"),
         py::arg("block"), py::arg("ctr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"));
   m.def("quant_update_adam", &quant_update_adam, py::arg("x"), py::arg("m"), py::arg("v"), py::arg("table"),
         py::arg("decays"), py::arg("nb"), py::arg("bits"), py::arg("gathered"), py::arg("world"), py::arg("lr"),
-        py::arg("hyper"), py::arg("block"), py::arg("ctr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"));
+        py::arg("hyper"), py::arg("block"), py::arg("ctr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("rotate") = "none", py::arg("seed") = 0);
   m.def("topk_update_adam", &topk_update_adam, py::arg("x"), py::arg("m"), py::arg("v"), py::arg("gathered"),
         py::arg("k"), py::arg("world"), py::arg("runs"), py::arg("lr"), py::arg("hyper"), py::arg("block"),
         py::arg("ctr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"));

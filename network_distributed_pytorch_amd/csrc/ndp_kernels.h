@@ -473,12 +473,15 @@ void launch_sign_update(float* x, float* b, int64_t n, const int32_t* table, int
 constexpr int64_t quant_row_words(int64_t nb, int bits) { return (nb * (64 * bits + 1) + 3) & ~int64_t(3); }
 // m = g + e, its absmax-scaled codes and the per-block scale into out (a whole row, padding included),
 // e = m - c.  A bits outside {2, 4, 8} launches nothing (the binding has refused it).
+// rotate: the randomized Hadamard rotation of quant.hip's header on every full block (len_j == kSignBlock),
+// with the signs of `seed`; pack and update of one sync take the same (rotate, seed).
 void launch_quant_pack(const float* g, float* e, int64_t n, const int32_t* table, int64_t nb, int bits, int32_t* out,
-                       hipStream_t s);
+                       bool rotate, uint32_t seed, hipStream_t s);
 // gathered: int32 [world][quant_row_words(nb, bits)], one row per rank; x, b updated in place by the
 // element rule with o = (sum over ranks in rank order of (u - L) s) / world.  hyper as for launch_sign_update.
 void launch_quant_update(float* x, float* b, int64_t n, const int32_t* table, int64_t nb, int bits,
-                         const int32_t* gathered, int world, float lr, float lam, const float* hyper, hipStream_t s);
+                         const int32_t* gathered, int world, float lr, float lam, const float* hyper, bool rotate,
+                         uint32_t seed, hipStream_t s);
 
 // ---- AdamW in the flat-arena compressors (signsgd.hip, quant.hip, topk.hip) ----------------------
 // The three update launches above with the AdamW element rule (adamw.hip's header; g := the
@@ -497,7 +500,7 @@ void launch_sign_update_adam(float* x, float* m, float* v, int64_t n, const int3
                              EfAdamArgs a, hipStream_t s);
 void launch_quant_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* table, const int32_t* decays,
                               int64_t nb, int bits, const int32_t* gathered, int world, float lr, const float* hyper,
-                              EfAdamArgs a, hipStream_t s);
+                              EfAdamArgs a, bool rotate, uint32_t seed, hipStream_t s);
 // runs: int32 [nr][2] = (start, decays), start ascending multiples of 16 from runs[0].start = 0: the
 // elements [start_i, start_{i+1}) take the weight decay or not
 void launch_topk_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* gathered, int64_t k, int world,

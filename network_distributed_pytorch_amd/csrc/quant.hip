@@ -46,11 +46,39 @@
 //   place of sign_step; b is the first moment, a third arena the second.  It alone has a barrier, 8 bytes
 //   of LDS and a ticket: the AdamBlock protocol of adam_block.h (ef_block.h: ef_adam_tail).
 //
+// Randomized Hadamard rotation (the ROT = true instances; ROT = false is the code above, unchanged).  A block
+// is rotated iff len_j == 2048 (uniform per workgroup: the barrier below is taken by all 256 threads or by
+// none); a ragged block follows the plain rule.  For a rotated block:
+//   d_t = -1 iff bit t & 31 of counter_hash4(seed, j, t >> 5, TAG) is set, TAG = 0x48414452 ("HADR"); applying
+//         d_t flips the float's sign bit.  A lane needs two hashes, one per round: word 32 h + (tid >> 3),
+//         bits 4 (tid & 7) + c.
+//   W:    11 butterfly stages k = 0 .. 10 in that order; in stage k every pair (t, t | 2^k) with bit k of t
+//         clear becomes (fadd(a, b), fsub(a, b)), one IEEE fp32 operation each.  The natural-order Sylvester
+//         Hadamard matrix H[t][u] = (-1)^popcount(t & u), unnormalised: W(W(v)) = 2048 v.
+//   pack:   m = fadd(W(d o g), e): e of a rotated block lives in the rotated domain; everything behind m is
+//           the plain body (an overflow in the butterflies makes the block non-finite like an inf in g).
+//   update: acc as above, then a_t = d_t fmul(W(acc)_t, 2^-11) in the place of acc: one transform per block,
+//           not per rank, W being linear.
+// fwht2048 works on the 8 registers a thread holds, t = 1024 h + 4 tid + c = [h | wave(2) | lane(6) | c(2)]:
+//   stages 0-1 (c):    in registers.
+//   stages 2-7 (lane): the partner's value by quad_perm DPP (^1, ^2), ds_swizzle (^4), row_ror:8 DPP (^8) and
+//                      the gfx950 v_permlane16_swap / v_permlane32_swap (^16, ^32): no LDS round trip and no
+//                      address register, where ds_bpermute needs both.  The lane whose bit is clear forms
+//                      v + p, the other p - v; the latter is formed as fadd(p, -v), the same float, so one
+//                      v_add_f32 behind a sign-bit XOR (folded into v_bitop3 with the mask) serves both.
+//   stages 8-9 (wave): one 8 KB exchange and one barrier: every thread leaves its 8 values as two float4,
+//                      reads the other three waves' and forms stage 8 of its own pair and of the pair across,
+//                      then stage 9, with wave-uniform sign masks.
+//   stage 10 (h):      in registers.
+// The pack transforms g in front of m = g + e, all four quad loads requested first as in the plain kernel;
+// the update transforms between quant_accumulate and the step.
+//
 // The rule's adds and subtractions are single scalar instructions and both kernels are compiled
 // without packed fp32 operations, as in signsgd.hip; every product feeds such an instruction, so the
 // build's -ffp-contract=fast has nothing to fuse it with.
 #include <hip/hip_runtime.h>
 
+#include "counter_hash.h"
 #include "ef_block.h"
 #include "hyper.h"
 #include "ndp_kernels.h"
@@ -87,11 +115,125 @@ __device__ __forceinline__ unsigned wave_umax(unsigned a, int lane) {
   return a;
 }
 
-template <int BITS>
+// ---- the rotation of the ROT instances ---------------------------------------------------------------
+constexpr uint32_t kRotTag = 0x48414452u;  // "HADR": the fourth argument of the sign hash
+constexpr int kDppRor8 = 0x128;            // row_ror:8, lane ^ 8 within a row of 16
+constexpr int kSwizzleXor4 = 0x101F;       // ds_swizzle bit mode: and 0x1f, or 0, xor 4
+
+__device__ __forceinline__ float flip(float v, unsigned mask) { return __builtin_bit_cast(float, bits_of(v) ^ mask); }
+
+// the lane's sign bits of round h, bit c the sign of component c
+__device__ __forceinline__ void rot_signs(unsigned seed, int j, int tid, unsigned (&sg)[kRounds]) {
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h)
+    sg[h] = counter_hash4(seed, (uint32_t)j, (uint32_t)(32 * h + (tid >> 3)), kRotTag) >> (4 * (tid & 7));
+}
+__device__ __forceinline__ float rot_sign(float v, unsigned sg, int c) {
+  return flip(v, (sg << (31 - c)) & 0x80000000u);
+}
+
+// One butterfly stage across lanes (or waves) on a value: neg is the sign bit where this lane holds the
+// pair's high element, 0 where it holds the low one.  Low: fadd(own, partner).  High: fsub(partner, own),
+// formed as fadd(partner, -own): the same float, so one instruction serves both.
+__device__ __forceinline__ float lane_stage(float own, float partner, unsigned neg) {
+  return fadd_scalar(partner, flip(own, neg));
+}
+
+// Stage lane ^ 16 (ROWS = 16) or lane ^ 32 by v_permlane16_swap / v_permlane32_swap on two copies of x: the
+// instruction swaps the odd rows (the upper half) of its first operand with the even rows (the lower half)
+// of its second, so afterwards a holds the pair's low element and b its high one in every lane.  Written
+// as assembly with two registers of its own: given the same value twice, the compiler's builtin took
+// both results from one register.  The s_nop covers the VALU write of the copies before the swap reads them.
+template <int ROWS>
+__device__ __forceinline__ float swap_stage(float x, unsigned neg) {
+  float a = x, b = x;
+  if constexpr (ROWS == 16)
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  else
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return fadd_scalar(a, flip(b, neg));
+}
+
+// W of the header over the block, v[h][c] the element t = 1024 h + 4 tid + c: in place, unnormalised,
+// stage k pairing t with t | 2^k in the order k = 0 .. 10.  xch: 8 KB of LDS, [wave][h][lane] float4.
+// All 256 threads of the workgroup call it (one barrier).
+__device__ __forceinline__ void fwht2048(float (&v)[kRounds][4], int lane, int wave, sign_f32x4* xch) {
+  // stages 0, 1: the quad's components
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+    const float a0 = fadd_scalar(v[h][0], v[h][1]), a1 = fsub_scalar(v[h][0], v[h][1]);
+    const float a2 = fadd_scalar(v[h][2], v[h][3]), a3 = fsub_scalar(v[h][2], v[h][3]);
+    v[h][0] = fadd_scalar(a0, a2); v[h][2] = fsub_scalar(a0, a2);
+    v[h][1] = fadd_scalar(a1, a3); v[h][3] = fsub_scalar(a1, a3);
+  }
+  // stages 2 .. 7: lane ^ 1, 2 (quad_perm), 4 (ds_swizzle), 8 (row rotate), 16, 32 (row / half swaps)
+  const unsigned ul = (unsigned)lane;
+  const unsigned n1 = (ul << 31), n2 = (ul << 30) & 0x80000000u, n4 = (ul << 29) & 0x80000000u,
+                 n8 = (ul << 28) & 0x80000000u, n16 = (ul << 27) & 0x80000000u, n32 = (ul << 26) & 0x80000000u;
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float x = v[h][c];
+      x = lane_stage(x, __builtin_bit_cast(float, dpp<kDppXor1>(bits_of(x))), n1);
+      x = lane_stage(x, __builtin_bit_cast(float, dpp<kDppXor2>(bits_of(x))), n2);
+      x = lane_stage(x, __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_ds_swizzle((int)bits_of(x), kSwizzleXor4)),
+                     n4);
+      x = lane_stage(x, __builtin_bit_cast(float, dpp<kDppRor8>(bits_of(x))), n8);
+      x = swap_stage<16>(x, n16);
+      x = swap_stage<32>(x, n32);
+      v[h][c] = x;
+    }
+  }
+  // stages 8, 9: the wave.  One exchange: every thread leaves its 8 values, reads the other three
+  // waves' and forms stage 8 of its own pair and of the pair across, then stage 9
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+    sign_f32x4 t;
+    t[0] = v[h][0]; t[1] = v[h][1]; t[2] = v[h][2]; t[3] = v[h][3];
+    xch[(wave * kRounds + h) * 64 + lane] = t;
+  }
+  block_barrier();
+  const unsigned w0 = ((unsigned)wave & 1u) << 31, w1 = ((unsigned)wave & 2u) << 30;  // uniform
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+    const sign_f32x4 x1 = xch[((wave ^ 1) * kRounds + h) * 64 + lane];
+    const sign_f32x4 x2 = xch[((wave ^ 2) * kRounds + h) * 64 + lane];
+    const sign_f32x4 x3 = xch[((wave ^ 3) * kRounds + h) * 64 + lane];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float mine = lane_stage(v[h][c], x1[c], w0);  // stage 8 of wave, wave ^ 1
+      const float across = lane_stage(x2[c], x3[c], w0);  // stage 8 of wave ^ 2, wave ^ 3
+      v[h][c] = lane_stage(mine, across, w1);
+    }
+  }
+  // stage 10: the round
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const float a = v[0][c], b = v[1][c];
+    v[0][c] = fadd_scalar(a, b);
+    v[1][c] = fsub_scalar(a, b);
+  }
+}
+
+// the update's way back: acc (a rank-ordered sum in the rotated domain) becomes d o (W(acc) 2^-11)
+__device__ __forceinline__ void rot_inverse(float (&acc)[kRounds][4], unsigned seed, int j, int tid, sign_f32x4* xch) {
+  unsigned sg[kRounds];
+  rot_signs(seed, j, tid, sg);
+  fwht2048(acc, tid & 63, __builtin_amdgcn_readfirstlane(tid >> 6), xch);
+#pragma unroll
+  for (int h = 0; h < kRounds; ++h) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[h][c] = rot_sign(__fmul_rn(acc[h][c], 0x1p-11f), sg[h], c);
+  }
+}
+
+template <int BITS, bool ROT>
 __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_pack_kernel(const float* __restrict__ g,
                                                                                 float* __restrict__ e,
                                                                                 const int* __restrict__ table, int nb,
-                                                                                int32_t* __restrict__ out) {
+                                                                                int32_t* __restrict__ out,
+                                                                                unsigned seed) {
   constexpr int L = (1 << (BITS - 1)) - 1, W = 64 * BITS;
   __shared__ unsigned wa[4];
   const int j = blockIdx.x;
@@ -105,6 +247,25 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_pack_kernel(
   for (int h = 0; h < kRounds; ++h) m[h] = load_quad(eb, h * 4 * kThreads + 4 * tid, len);
 #pragma unroll
   for (int h = 0; h < kRounds; ++h) gq[h] = load_quad(gb, h * 4 * kThreads + 4 * tid, len);
+  if constexpr (ROT) {
+    __shared__ sign_f32x4 xch[4 * kRounds * 64];
+    if (len == kSignBlock) {  // uniform: a full block is rotated, g becomes y = W(d o g)
+      unsigned sg[kRounds];
+      rot_signs(seed, j, tid, sg);
+      float y[kRounds][4];
+#pragma unroll
+      for (int h = 0; h < kRounds; ++h) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) y[h][c] = rot_sign(gq[h].v[c], sg[h], c);
+      }
+      fwht2048(y, lane, wave, xch);
+#pragma unroll
+      for (int h = 0; h < kRounds; ++h) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gq[h].v[c] = y[h][c];
+      }
+    }
+  }
   unsigned a = 0u;
 #pragma unroll
   for (int h = 0; h < kRounds; ++h) {
@@ -216,10 +377,11 @@ __device__ __forceinline__ void quant_accumulate(const int32_t* __restrict__ gat
   }
 }
 
-template <int BITS>
+template <int BITS, bool ROT>
 __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_kernel(
     float* __restrict__ x, float* __restrict__ b, const int* __restrict__ table, int nb,
-    const int32_t* __restrict__ gathered, int N, float lr_arg, float lam, const float* __restrict__ hyper) {
+    const int32_t* __restrict__ gathered, int N, float lr_arg, float lam, const float* __restrict__ hyper,
+    unsigned seed) {
   const Hyper hy = load_hyper(hyper, lr_arg);
   const int j = blockIdx.x;
   const int off = table[2 * j], len = table[2 * j + 1];
@@ -234,6 +396,10 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_kerne
   }
   float acc[kRounds][4];
   quant_accumulate<BITS>(gathered, nb, j, tid, N, acc);
+  if constexpr (ROT) {
+    __shared__ sign_f32x4 xch[4 * kRounds * 64];
+    if (len == kSignBlock) rot_inverse(acc, seed, j, tid, xch);  // uniform: all 256 threads or none
+  }
   const float fN = (float)N;
 #pragma unroll
   for (int h = 0; h < kRounds; ++h) {
@@ -250,11 +416,15 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_kerne
 // Resources (hipcc --offload-arch=gfx950 -O3 -ffp-contract=fast, -Rpass-analysis=kernel-resource-usage), the
 // same at 2, 4 and 8 bits: 57 VGPRs, 0 AGPRs, 46 SGPRs, no scratch (0 bytes/lane, no spills), 8 B of LDS,
 // occupancy 8 waves/SIMD (quant_update_kernel: 38-39 VGPRs, 32-34 SGPRs, no LDS, occupancy 8).
-template <int BITS>
+// ROT instances (the same report; no spills, no scratch in any): quant_pack_kernel 50 VGPRs, 39 SGPRs, 8208 B of
+// LDS, occupancy 8 (ROT = false: 30 VGPRs, 39 SGPRs, 16 B); quant_update_kernel 62 / 62 / 64 VGPRs at 2 / 4 / 8
+// bits, 38 SGPRs, 8192 B, occupancy 8; quant_update_adam_kernel 76 VGPRs, 48 SGPRs, 8208 B, occupancy 6.
+template <int BITS, bool ROT>
 __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_adam_kernel(
     float* __restrict__ x, float* __restrict__ m, float* __restrict__ v, const int* __restrict__ table,
     const int* __restrict__ decays, int nb, const int32_t* __restrict__ gathered, int N, float lr_arg,
-    const float* __restrict__ hyper, AdamBlock* block, unsigned* ctr, float beta1, float beta2, float eps) {
+    const float* __restrict__ hyper, AdamBlock* block, unsigned* ctr, float beta1, float beta2, float eps,
+    unsigned seed) {
   __shared__ float pow_sh[2];
   const unsigned steps = adam_block_read(block, pow_sh);
   const Hyper hy = load_hyper(hyper, lr_arg);
@@ -265,46 +435,46 @@ __global__ __launch_bounds__(kThreads) NDP_NO_PACKED_F32 void quant_update_adam_
   EfAdamRegs R = ef_adam_load(x + off, m + off, v + off, tid, len);
   float acc[kRounds][4];
   quant_accumulate<BITS>(gathered, nb, j, tid, N, acc);
+  if constexpr (ROT) {
+    __shared__ sign_f32x4 xch[4 * kRounds * 64];
+    if (len == kSignBlock) rot_inverse(acc, seed, j, tid, xch);  // uniform
+  }
   ef_adam_tail(x + off, m + off, v + off, tid, R, acc, N, hy, dec, pow_sh, beta1, beta2, eps, ctr, block, steps);
 }
 
-template <int BITS>
-void launch_update_adam(float* x, float* m, float* v, const int32_t* table, const int32_t* decays, int nb,
-                        const int32_t* gathered, int world, float lr, const float* hyper, EfAdamArgs a, hipStream_t s) {
-  hipLaunchKernelGGL(quant_update_adam_kernel<BITS>, dim3((unsigned)nb), dim3(kThreads), 0, s, x, m, v, table, decays,
-                     nb, gathered, world, lr, hyper, a.block, a.ctr, a.beta1, a.beta2, a.eps);
-}
+// the launch of KERNEL<bits, rotate> (bits in {2, 4, 8}; another value launches nothing)
+#define NDP_QUANT_LAUNCH(KERNEL, bits, rotate, grid, s, ...)                                              \
+  do {                                                                                                    \
+    if ((bits) == 2 && !(rotate)) hipLaunchKernelGGL((KERNEL<2, false>), grid, dim3(kThreads), 0, s, __VA_ARGS__); \
+    if ((bits) == 4 && !(rotate)) hipLaunchKernelGGL((KERNEL<4, false>), grid, dim3(kThreads), 0, s, __VA_ARGS__); \
+    if ((bits) == 8 && !(rotate)) hipLaunchKernelGGL((KERNEL<8, false>), grid, dim3(kThreads), 0, s, __VA_ARGS__); \
+    if ((bits) == 2 && (rotate)) hipLaunchKernelGGL((KERNEL<2, true>), grid, dim3(kThreads), 0, s, __VA_ARGS__);   \
+    if ((bits) == 4 && (rotate)) hipLaunchKernelGGL((KERNEL<4, true>), grid, dim3(kThreads), 0, s, __VA_ARGS__);   \
+    if ((bits) == 8 && (rotate)) hipLaunchKernelGGL((KERNEL<8, true>), grid, dim3(kThreads), 0, s, __VA_ARGS__);   \
+  } while (0)
 
 }  // namespace
 
 void launch_quant_update_adam(float* x, float* m, float* v, int64_t n, const int32_t* table, const int32_t* decays,
                               int64_t nb, int bits, const int32_t* gathered, int world, float lr, const float* hyper,
-                              EfAdamArgs a, hipStream_t s) {
+                              EfAdamArgs a, bool rotate, uint32_t seed, hipStream_t s) {
   if (n <= 0 || n >= (1LL << 31) || nb < 1 || world < 1) return;  // the binding has refused these
-  if (bits == 2) launch_update_adam<2>(x, m, v, table, decays, (int)nb, gathered, world, lr, hyper, a, s);
-  if (bits == 4) launch_update_adam<4>(x, m, v, table, decays, (int)nb, gathered, world, lr, hyper, a, s);
-  if (bits == 8) launch_update_adam<8>(x, m, v, table, decays, (int)nb, gathered, world, lr, hyper, a, s);
+  NDP_QUANT_LAUNCH(quant_update_adam_kernel, bits, rotate, dim3((unsigned)nb), s, x, m, v, table, decays, (int)nb,
+                   gathered, world, lr, hyper, a.block, a.ctr, a.beta1, a.beta2, a.eps, seed);
 }
 
 void launch_quant_pack(const float* g, float* e, int64_t n, const int32_t* table, int64_t nb, int bits, int32_t* out,
-                       hipStream_t s) {
+                       bool rotate, uint32_t seed, hipStream_t s) {
   if (n <= 0 || n >= (1LL << 31) || nb < 1) return;  // the binding has refused these
-  const dim3 grid((unsigned)nb), block(kThreads);
-  if (bits == 2) hipLaunchKernelGGL(quant_pack_kernel<2>, grid, block, 0, s, g, e, table, (int)nb, out);
-  if (bits == 4) hipLaunchKernelGGL(quant_pack_kernel<4>, grid, block, 0, s, g, e, table, (int)nb, out);
-  if (bits == 8) hipLaunchKernelGGL(quant_pack_kernel<8>, grid, block, 0, s, g, e, table, (int)nb, out);
+  NDP_QUANT_LAUNCH(quant_pack_kernel, bits, rotate, dim3((unsigned)nb), s, g, e, table, (int)nb, out, seed);
 }
 
 void launch_quant_update(float* x, float* b, int64_t n, const int32_t* table, int64_t nb, int bits,
-                         const int32_t* gathered, int world, float lr, float lam, const float* hyper, hipStream_t s) {
+                         const int32_t* gathered, int world, float lr, float lam, const float* hyper, bool rotate,
+                         uint32_t seed, hipStream_t s) {
   if (n <= 0 || n >= (1LL << 31) || nb < 1 || world < 1) return;
-  const dim3 grid((unsigned)nb), block(kThreads);
-  if (bits == 2)
-    hipLaunchKernelGGL(quant_update_kernel<2>, grid, block, 0, s, x, b, table, (int)nb, gathered, world, lr, lam, hyper);
-  if (bits == 4)
-    hipLaunchKernelGGL(quant_update_kernel<4>, grid, block, 0, s, x, b, table, (int)nb, gathered, world, lr, lam, hyper);
-  if (bits == 8)
-    hipLaunchKernelGGL(quant_update_kernel<8>, grid, block, 0, s, x, b, table, (int)nb, gathered, world, lr, lam, hyper);
+  NDP_QUANT_LAUNCH(quant_update_kernel, bits, rotate, dim3((unsigned)nb), s, x, b, table, (int)nb, gathered, world, lr,
+                   lam, hyper, seed);
 }
 
 }  // namespace ndp

@@ -85,6 +85,10 @@ def default_config(**over) -> Dict[str, Any]:
         topk_ratio=0.01,
         # grad_sync="quant" (parallel/quant.py): bits per coordinate, 2 (ternary), 4 or 8
         quant_bits=4,
+        # "hadamard": quantise every full block behind a randomized Hadamard rotation with the signs of
+        # quant_rotate_seed (the same on every rank: it comes from the config only)
+        quant_rotate="none",
+        quant_rotate_seed=0,
         # grad_sync="dense-lars" (ops/layerwise.py): trust coefficient and denominator eps
         lars_coef=0.001, lars_eps=1e-8,
     )
@@ -420,6 +424,8 @@ def run_task(config) -> Dict[str, Any]:
         extra = {"overlap": config.get("overlap")}
     elif config["grad_sync"] in ("quant", "quant-adamw"):
         extra = {"overlap": config.get("overlap"), "quant_bits": int(config.get("quant_bits", 4))}
+        if config.get("quant_rotate", "none") != "none":  # none: build_grad_sync is called exactly as before
+            extra.update(quant_rotate=config["quant_rotate"], quant_rotate_seed=int(config.get("quant_rotate_seed", 0)))
     max_grad_norm = float(config.get("max_grad_norm") or 0.0)
     if max_grad_norm > 0:  # off: build_grad_sync is called exactly as before
         extra["max_grad_norm"] = max_grad_norm

@@ -30,6 +30,24 @@ elements outside every block are neither read nor written.  With ``b = bits``, `
    element rule of the other arms: ``d = (wd != 0) ? fmaf(wd, x, o) : o``;
    ``b' = fadd(fmul(b, lambda), d)``; ``x' = fmaf(-lr, fadd(d, b'), x)``.
 
+Randomized Hadamard rotation (``rotate="hadamard"``; DRIVE / EDEN of Vargaftik et al. 2021/22): one
+large coordinate sets a block's absmax and the rest of the block rounds to zero; behind ``y = W (d o m)``
+the coordinates are near-Gaussian whatever the block looked like.  A block is *rotated* iff
+``len_j == 2048``; a ragged block follows the rule above unchanged.  The wire row does not change by a
+bit.  For a rotated block:
+
+* Signs: ``d_t = -1`` iff bit ``t & 31`` of ``hash4(rotate_seed, j, t >> 5, 0x48414452)`` is set
+  (:func:`quant_rotate_signs`); applying ``d_t`` flips the float's sign bit.
+* ``W`` (:func:`quant_fwht`): 11 butterfly stages ``k = 0 .. 10`` in that order; in stage ``k`` every pair
+  ``(t, t | 2^k)`` with bit ``k`` of ``t`` clear becomes ``(fadd(a, b), fsub(a, b))``, each one IEEE fp32
+  operation.  It is the natural-order Sylvester Hadamard matrix ``H[t][u] = (-1)^popcount(t & u)``,
+  unnormalised: ``W(W(v)) = 2048 v``.
+* Step 1 becomes ``m = fadd(W(d o g), e)``: the error memory of a rotated block lives in the rotated
+  domain.  Steps 2 to 6 run on this ``m`` unchanged; an overflow inside the butterflies makes the block
+  non-finite like an inf in ``g``.
+* Step 7 forms ``acc`` as above (in the rotated domain), then ``a_t = d_t fmul(W(acc)_t, 2^-11)`` (one
+  transform per block, not per rank: ``W`` is linear) and goes on with ``a`` in the place of ``acc``.
+
 Device tensors run the native kernels, CPU tensors the twin; a device tensor the kernels cannot
 take (not fp32, not contiguous) is an error, never a fallback.
 """
@@ -41,12 +59,15 @@ import numpy as np
 import torch
 
 from ._ext import ext
+from .image_batch import _hash4_t
 from .signsgd import G, SignCore
 from .topk import fmaf32
 
-__all__ = ["QuantCore", "quant_word_shift", "QUANT_BITS"]
+__all__ = ["QuantCore", "quant_word_shift", "quant_fwht", "quant_rotate_signs", "QUANT_BITS", "QUANT_ROTATIONS"]
 
 QUANT_BITS = (2, 4, 8)
+QUANT_ROTATIONS = ("none", "hadamard")
+_ROT_TAG = 0x48414452  # csrc/quant.hip kRotTag
 _MAG, _INF, _NAN = 0x7FFFFFFF, 0x7F800000, 0x7FC00000
 
 
@@ -55,15 +76,37 @@ def quant_word_shift(bits, j, t):
     return 64 * bits * j + ((t * bits) >> 5), (t * bits) & 31
 
 
+def quant_fwht(v: torch.Tensor) -> torch.Tensor:
+    """``W`` over the last dimension (2048) of an fp32 tensor: the 11 stages in the rule's order."""
+    shape = v.shape
+    for k in range(11):
+        v = v.reshape(-1, G >> (k + 1), 2, 1 << k)
+        a, b = v[:, :, 0], v[:, :, 1]
+        v = torch.stack((a + b, a - b), dim=2)
+    return v.reshape(shape)
+
+
+def quant_rotate_signs(seed: int, j: int) -> torch.Tensor:
+    """``d`` of block ``j`` as fp32 ``[2048]`` of ``+1`` / ``-1`` (a product with it flips the sign bit)."""
+    words = _hash4_t(seed, j, torch.arange(G // 32), _ROT_TAG).view(-1, 1)
+    return (1 - 2 * ((words >> torch.arange(32)) & 1)).view(G).float()
+
+
 class QuantCore(SignCore):
     """:class:`SignCore`'s block table and interface with rows of ``words = row_words`` int32:
     ``out`` is this rank's row, ``gathered`` the ``[world, words]`` the update reads (``out`` itself
     when ``world == 1``); everything is allocated here, before any capture."""
 
-    def __init__(self, device, segments: Sequence[Tuple[int, int]], n: int, world: int = 1, bits: int = 4):
+    def __init__(self, device, segments: Sequence[Tuple[int, int]], n: int, world: int = 1, bits: int = 4,
+                 rotate: str = "none", rotate_seed: int = 0):
         if bits not in QUANT_BITS:
             raise ValueError(f"quant: bits must be one of {QUANT_BITS}, got {bits!r}")
+        if rotate not in QUANT_ROTATIONS:
+            raise ValueError(f"quant: rotate must be one of {QUANT_ROTATIONS}, got {rotate!r}")
+        if not 0 <= int(rotate_seed) < 2 ** 32:
+            raise ValueError(f"quant: 0 <= rotate_seed < 2^32 required, got {rotate_seed!r}")
         super().__init__(device, segments, n, world)
+        self.rotate, self.rotate_seed, self._rot = rotate, int(rotate_seed), None
         self.bits, self.levels = int(bits), 2 ** (int(bits) - 1) - 1
         self.code_words = 64 * self.bits * self.nb
         self.words = (self.code_words + self.nb + 3) // 4 * 4
@@ -71,15 +114,29 @@ class QuantCore(SignCore):
         self.out = torch.zeros(self.words, **i32)
         self.gathered = self.out.view(1, -1) if self.world == 1 else torch.zeros(self.world, self.words, **i32)
 
+    def _twin_rotation(self):
+        """``(rotated [nb, 1] bool, d [nb, G])`` of the twin; ``d`` is 1 in the blocks that are not rotated."""
+        if self._rot is None:
+            rotated = (self._host_table[:, 1:] == G) & (self.rotate == "hadamard")
+            d = torch.ones(self.nb, G)
+            for j in rotated.view(-1).nonzero().view(-1).tolist():
+                d[j] = quant_rotate_signs(self.rotate_seed, j)
+            self._rot = (rotated, d)
+        return self._rot
+
     def compress(self, g: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
         """Steps 1-6: ``e`` becomes the residual, ``out`` the row; returns ``out``."""
         self._check(g, e)
         nb, bits, L = self.nb, self.bits, self.levels
         if self.device.type == "cuda":
-            ext().quant_pack(g, e, self.table, nb, bits, self.out)
+            ext().quant_pack(g, e, self.table, nb, bits, self.out, self.rotate, self.rotate_seed)
             return self.out
         idx, valid = self._twin_index()
-        m = torch.where(valid, g[idx] + e[idx], torch.zeros(()))
+        y = g[idx]
+        if self.rotate != "none":
+            rotated, d = self._twin_rotation()
+            y = torch.where(rotated, quant_fwht(y * d), y)
+        m = torch.where(valid, y + e[idx], torch.zeros(()))
         A = (m.view(torch.int32) & _MAG).max(dim=1, keepdim=True).values
         s = A.view(torch.float32) / float(L)
         finite = A < _INF
@@ -107,7 +164,8 @@ class QuantCore(SignCore):
         if self.device.type == "cuda":
             if hyper is None and wd != 0.0:
                 raise ValueError("QuantCore.update: weight decay on the device goes through the hyper block")
-            ext().quant_update(x, b, self.table, nb, bits, gathered, N, float(lr), float(lam), hyper)
+            ext().quant_update(x, b, self.table, nb, bits, gathered, N, float(lr), float(lam), hyper, self.rotate,
+                               self.rotate_seed)
             return
         idx, valid = self._twin_index()
         o = self._decode(gathered)
@@ -119,7 +177,8 @@ class QuantCore(SignCore):
         x[idx[valid]], b[idx[valid]] = xv[valid], bv[valid]
 
     def _decode(self, gathered: torch.Tensor) -> torch.Tensor:
-        """The twin's ``o`` of step 7, ``[nb, G]``: the rank-ordered sum of the decoded codes, over ``N``."""
+        """The twin's ``o`` of step 7, ``[nb, G]``: the rank-ordered sum of the decoded codes (rotated back
+        where the block is rotated), over ``N``."""
         N, nb, bits = self.world, self.nb, self.bits
         rows = gathered.view(N, self.words)
         shifts = (torch.arange(32 // bits) * bits).to(torch.int32)
@@ -128,8 +187,12 @@ class QuantCore(SignCore):
             u = ((rows[r, : self.code_words].view(nb, 64 * bits, 1) >> shifts) & (2 ** bits - 1)).view(nb, G)
             scale = rows[r, self.code_words: self.code_words + nb].view(torch.float32).view(nb, 1)
             o = o + (u - self.levels).float() * scale
+        if self.rotate != "none":
+            rotated, d = self._twin_rotation()
+            o = torch.where(rotated, d * (quant_fwht(o) * 2.0 ** -11), o)
         return o / float(N) if N != 1 else o
 
     def _native_update_adam(self, x, m, v, gathered, lr, hyper, block, decays, beta1, beta2, eps):
         ext().quant_update_adam(x, m, v, self.table, decays, self.nb, self.bits, gathered, self.world, float(lr), hyper,
-                                block.dev, block.ctr, float(beta1), float(beta2), float(eps))
+                                block.dev, block.ctr, float(beta1), float(beta2), float(eps), self.rotate,
+                                self.rotate_seed)

@@ -204,7 +204,7 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
                     momentum: float = 0.9, rank: int = 4, bucket_mb: Optional[float] = None, seed: int = 714,
                     max_grad_norm: float = 0.0, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
                     decay_1d: bool = True, topk_ratio: float = 0.01, quant_bits: int = 4, lars_coef: float = 0.001,
-                    lars_eps: float = 1e-8, **kw):
+                    lars_eps: float = 1e-8, quant_rotate: str = "none", quant_rotate_seed: int = 0, **kw):
     comm = comm if comm is not None else Communicator()
     clip = {"max_grad_norm": max_grad_norm} if max_grad_norm else {}  # off: every constructor call as before
     if kind in LAYERWISE_SYNCS:
@@ -262,8 +262,9 @@ def build_grad_sync(kind: str, model: torch.nn.Module, comm: Optional[Communicat
     if kind == "signsgd":
         return SignSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), **clip, **adam)
     if kind == "quant":
+        rot = {"quant_rotate": quant_rotate, "quant_rotate_seed": quant_rotate_seed} if quant_rotate != "none" else {}
         return QuantSync(model, comm, lr=lr, momentum=momentum, overlap=kw.get("overlap"), quant_bits=quant_bits,
-                         **clip, **adam)
+                         **rot, **clip, **adam)
     raise ValueError(f"unknown grad sync {kind!r}")
 
 

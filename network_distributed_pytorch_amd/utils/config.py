@@ -125,6 +125,10 @@ class TrainConfig:
     topk_ratio: float = 0.01  # k = max(1, ceil(topk_ratio * parameters)), 0 < ratio <= 1
     # grad_sync="quant" (parallel/quant.py): bits per coordinate, 2 (ternary), 4 or 8
     quant_bits: int = 4
+    # "hadamard": a randomized Hadamard rotation of every full block before the quantisation (ops/quant.py);
+    # the seed fixes its signs and must be the same on every rank
+    quant_rotate: str = "none"
+    quant_rotate_seed: int = 0
     # grad_sync="dense-lars" (ops/layerwise.py): the trust coefficient eta and the eps of its denominator;
     # adam_beta1 / adam_beta2 / adam_eps / decay_1d serve grad_sync="dense-lamb"
     lars_coef: float = 0.001
@@ -243,6 +247,10 @@ def validate_config(config: Dict[str, Any], strict: bool = True) -> Dict[str, An
         raise ConfigError("grad_sync='signsgd' has no backward overlap (per-tensor packing is out of scope)")
     if base == "quant" and c["quant_bits"] not in (2, 4, 8):
         raise ConfigError(f"quant_bits = {c['quant_bits']} must be 2, 4 or 8")
+    if c["quant_rotate"] not in ("none", "hadamard"):
+        raise ConfigError(f"quant_rotate = {c['quant_rotate']!r}; allowed: ['none', 'hadamard']")
+    if not 0 <= c["quant_rotate_seed"] < 2 ** 32:
+        raise ConfigError(f"quant_rotate_seed = {c['quant_rotate_seed']} must lie in [0, 2^32)")
     if base == "quant" and c["overlap"]:
         raise ConfigError("grad_sync='quant' has no backward overlap (per-tensor packing is out of scope)")
     if not c["max_grad_norm"] >= 0:  # NaN fails the comparison too

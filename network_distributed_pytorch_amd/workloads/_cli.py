@@ -18,7 +18,8 @@ norm, ops/gradclip.py; ``inf`` only measures it), ``-label_smoothing`` (ops/loss
 ``-ema_decay`` / ``-ema_warmup`` (exponential moving average of the weights, ops/ema.py), ``-optimizer`` /
 ``-adam_beta1`` / ``-adam_beta2`` / ``-adam_eps`` / ``-decay_1d`` (fused AdamW behind the gradient sync,
 ops/adamw.py), ``-topk_ratio`` (the fraction of the parameters ``-grad_sync topk`` sends, parallel/topk.py),
-``-quant_bits`` (the code width of ``-grad_sync quant``, parallel/quant.py), ``-lars_coef`` / ``-lars_eps`` (the trust
+``-quant_bits`` (the code width of ``-grad_sync quant``, parallel/quant.py), ``-quant_rotate`` / ``-quant_rotate_seed``
+(its randomized Hadamard rotation, ops/quant.py), ``-lars_coef`` / ``-lars_eps`` (the trust
 coefficient and denominator eps of ``-grad_sync dense-lars``, ops/layerwise.py; ``-grad_sync dense-lamb`` takes the
 ``-adam_*`` and ``-decay_1d`` flags).
 """
@@ -106,6 +107,10 @@ def build_parser(default_world: int, world_required: bool = False) -> argparse.A
                    help="grad_sync topk: fraction of the parameters each rank sends per step, in (0, 1] (default 0.01)")
     p.add_argument("-quant_bits", type=int, default=None, choices=[None, 2, 4, 8],
                    help="grad_sync quant: bits per coordinate (default 4; 2 is ternary)")
+    p.add_argument("-quant_rotate", type=str, default=None, choices=[None, "none", "hadamard"],
+                   help="grad_sync quant: rotate every full block before quantising it (default none)")
+    p.add_argument("-quant_rotate_seed", type=int, default=None,
+                   help="grad_sync quant: seed of the rotation's signs, the same on every rank (default 0)")
     p.add_argument("-lars_coef", type=float, default=None,
                    help="grad_sync dense-lars: the trust coefficient eta > 0 (default 0.001)")
     p.add_argument("-lars_eps", type=float, default=None,
@@ -128,7 +133,8 @@ _MAP = {"epochs": "training_epochs", "steps": "max_steps_per_epoch", "model": "m
         "max_grad_norm": "max_grad_norm", "label_smoothing": "label_smoothing", "mix": "mix",
         "mix_prob": "mix_prob", "ema_decay": "ema_decay", "optimizer": "optimizer", "adam_beta1": "adam_beta1",
         "adam_beta2": "adam_beta2", "adam_eps": "adam_eps", "topk_ratio": "topk_ratio",
-        "quant_bits": "quant_bits", "lars_coef": "lars_coef", "lars_eps": "lars_eps"}
+        "quant_bits": "quant_bits", "quant_rotate": "quant_rotate", "quant_rotate_seed": "quant_rotate_seed",
+        "lars_coef": "lars_coef", "lars_eps": "lars_eps"}
 
 
 def apply_args(ddp_init: ModuleType, args, rank: int, world: int, cuda: Optional[int]):
